@@ -12,7 +12,17 @@ over 8 GiB of synthetic URL log lines per GPU.  The corpus and its newline index
 the timed region.  N > 1: every rank scans its own 8 GiB shard (weak scaling), no collective on the data path;
 torch.distributed (RCCL) is used only for the barrier and the max-over-ranks of the elapsed time.
 
-Prints ONE JSON line on rank 0 with the contract's fields plus "roofline" and "cpu_baseline".
+Prints ONE JSON line on rank 0 with the contract's fields plus "roofline" (from the timed launches).  A plain run sets up,
+warms up, times the steps and prints that line; --full adds what is measured beside the headline, in launches and runs of
+its own: the cold path and the one-shot entry ("cold"), the table-order A/B, the accepted-line count and "cpu_baseline".
+
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full
+    python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR
+
+--dump-outputs DIR writes what the last timed step computed (rank 0): DIR/accept_bits.npy, the accept bitmap a caller of
+rrx_match_corpus receives (uint32 words as float64, bit (i & 31) of word i >> 5 = line i accepted).  A bitmap of more than
+64 MB as float64 is written as a fixed, seeded sample of its words, with their indices in DIR/accept_bits_index.npy.
+The corpus is generated from fixed seeds, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -155,6 +165,25 @@ def cpu_baseline(pattern, host, target_seconds=12.0):
             "single_core_GBs": round(per_core / 1e9, 4)}
 
 
+DUMP_BYTES = 64 * 10**6      # --dump-outputs: at most this much in all
+CLOCK_WARM_S = 0.3           # setup of a plain run: back-to-back launches for this long before the warm-up steps
+
+
+def dump_outputs(d, bits):
+    """bits: the uint32 words of the accept bitmap -> d/accept_bits.npy as float64 (exact).  A bitmap too large for
+    DUMP_BYTES is written as a fixed, seeded sample of its words, their indices in d/accept_bits_index.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    index_path = os.path.join(d, "accept_bits_index.npy")
+    if bits.size * 8 > DUMP_BYTES - 4096:
+        idx = np.sort(np.random.default_rng(0).choice(bits.size, (DUMP_BYTES - 4096) // 16, replace=False))
+        bits = bits[idx]
+        np.save(index_path, idx.astype(np.float64))
+    elif os.path.exists(index_path):
+        os.remove(index_path)
+    np.save(os.path.join(d, "accept_bits.npy"), bits.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -163,7 +192,11 @@ def main():
     ap.add_argument("--workload", default="url", choices=sorted(WORKLOADS))
     ap.add_argument("--bytes", type=int, default=0, help="bytes per GPU (default: the BASELINE size)")
     ap.add_argument("--engine", default="auto", choices=sorted(ENGINES))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure beside the headline: cold path, one-shot entry, table-order A/B, accepted count, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the accept bitmap of the last timed step to DIR/accept_bits.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--stripe", type=int, default=0, help="bytes per GPU lane (0 = chosen from the corpus size)")
     ap.add_argument("--pcie", action="store_true", help="also time the host-buffer entry (upload + index + match + download)")
     ap.add_argument("--search", action="store_true", help="also time rrx_search_corpus (match offsets per line) on the same corpus")
@@ -173,6 +206,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     # N > 1 and nobody started the ranks for us: do it ourselves, as child processes, before any GPU call here.
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -289,47 +324,59 @@ def main():
     while (regex.table_order_pending or regex.sampled_table_pending) and time.perf_counter() - t_wait < 2.0:
         time.sleep(0.01)
     order_wait_ms = (time.perf_counter() - t_wait) * 1e3
-    # one-shot ("cold") rate: a corpus nobody has indexed yet — index build + one match, clocks warm, HIP events
-    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-    cold = []
-    for _ in range(3):
-        e0.record()
-        c2 = rr.Corpus(dev, stripe=args.stripe)       # no hint: what a first-time caller of rrx_corpus_create pays
-        e1.record()
-        regex.match_corpus_bits(c2, out=out)
-        e2.record()
+    # the clocks: after the launches above the GPU is still leaving its idle clocks.  With --full the cold path and the one-shot
+    # calls below keep it busy before the warm-up steps, as they always did; a plain run has no such work, and its timed launches
+    # started at 1.79 ms against 1.53 ms steady (URL config, 4 % low over 20 steps), so it keeps the kernel busy for CLOCK_WARM_S
+    clock_warm_launches = 0
+    t_warm = time.perf_counter()
+    while not args.full and time.perf_counter() - t_warm < CLOCK_WARM_S:
+        for _ in range(4):
+            regex.match_corpus_bits(corpus, out=out)
         torch.cuda.synchronize()
-        cold.append((e0.elapsed_time(e1), e1.elapsed_time(e2)))
-        del c2
-    cold_index_ms, cold_match_ms = min(cold, key=lambda p: p[0] + p[1])
-    # the same through the one-shot entry (rrx_match_device): with the stride-2 table the text is read once, the index is
-    # a by-product (per-stripe counts + scan + compaction of the lanes' verdict streams)
-    # (the entry is synchronous: it returns the line count.  Every call is listed; reported: the MEDIAN of the twelve and
-    # the worst call over the median - round 2 reported a mean, and one 10.6 ms call in twelve halved the figure.)
-    oneshot_ms = []
-    for _ in range(12):
-        e0.record()
-        _, n1 = regex.match_device_bits(dev, cap_lines=nlines + 64, out=out if out.numel() >= (nlines + 64 + 31) // 32 else None)
-        e1.record()
-        torch.cuda.synchronize()
-        assert n1 == nlines
-        oneshot_ms.append(e0.elapsed_time(e1))
-    # the same with a bound a first-time caller can know: no string shorter than four bytes on average, i.e. cap_lines = n / 4
-    # (the call clears cap_lines / 8 bytes of bitmap: 268 MB for 8 GiB) - the figure above sizes the bitmap from an index built earlier
-    apriori_ms = []
-    out4 = torch.empty((nbytes // 4 + 31) // 32, dtype=torch.int32, device=dev.device)
-    for _ in range(5):
-        e0.record()
-        _, n1 = regex.match_device_bits(dev, cap_lines=nbytes // 4, out=out4)
-        e1.record()
-        torch.cuda.synchronize()
-        assert n1 == nlines
-        apriori_ms.append(e0.elapsed_time(e1))
-    del out4
-    apriori_ms = sorted(apriori_ms)[2]
-    oneshot_all = [round(x, 4) for x in oneshot_ms]
-    oneshot_worst = max(oneshot_ms)
-    oneshot_ms = sorted(oneshot_ms)[len(oneshot_ms) // 2 - 1]          # lower median of twelve
+        clock_warm_launches += 4
+    # --full: the cold path and the one-shot entry, before the warm-up as always (they share `out` with the timed launches)
+    if args.full:
+        # one-shot ("cold") rate: a corpus nobody has indexed yet — index build + one match, clocks warm, HIP events
+        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        cold = []
+        for _ in range(3):
+            e0.record()
+            c2 = rr.Corpus(dev, stripe=args.stripe)       # no hint: what a first-time caller of rrx_corpus_create pays
+            e1.record()
+            regex.match_corpus_bits(c2, out=out)
+            e2.record()
+            torch.cuda.synchronize()
+            cold.append((e0.elapsed_time(e1), e1.elapsed_time(e2)))
+            del c2
+        cold_index_ms, cold_match_ms = min(cold, key=lambda p: p[0] + p[1])
+        # the same through the one-shot entry (rrx_match_device): with the stride-2 table the text is read once, the index is
+        # a by-product (per-stripe counts + scan + compaction of the lanes' verdict streams)
+        # (the entry is synchronous: it returns the line count.  Every call is listed; reported: the MEDIAN of the twelve and
+        # the worst call over the median - round 2 reported a mean, and one 10.6 ms call in twelve halved the figure.)
+        oneshot_ms = []
+        for _ in range(12):
+            e0.record()
+            _, n1 = regex.match_device_bits(dev, cap_lines=nlines + 64, out=out if out.numel() >= (nlines + 64 + 31) // 32 else None)
+            e1.record()
+            torch.cuda.synchronize()
+            assert n1 == nlines
+            oneshot_ms.append(e0.elapsed_time(e1))
+        # the same with a bound a first-time caller can know: no string shorter than four bytes on average, i.e. cap_lines = n / 4
+        # (the call clears cap_lines / 8 bytes of bitmap: 268 MB for 8 GiB) - the figure above sizes the bitmap from an index built earlier
+        apriori_ms = []
+        out4 = torch.empty((nbytes // 4 + 31) // 32, dtype=torch.int32, device=dev.device)
+        for _ in range(5):
+            e0.record()
+            _, n1 = regex.match_device_bits(dev, cap_lines=nbytes // 4, out=out4)
+            e1.record()
+            torch.cuda.synchronize()
+            assert n1 == nlines
+            apriori_ms.append(e0.elapsed_time(e1))
+        del out4
+        apriori_ms = sorted(apriori_ms)[2]
+        oneshot_all = [round(x, 4) for x in oneshot_ms]
+        oneshot_worst = max(oneshot_ms)
+        oneshot_ms = sorted(oneshot_ms)[len(oneshot_ms) // 2 - 1]          # lower median of twelve
     for _ in range(args.warmup):
         regex.match_corpus_bits(corpus, out=out)
     barrier()
@@ -353,13 +400,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         per_rank = [round(nbytes * args.steps / float(x.item()) / 1e9, 2) for x in every]
+    # `out` still holds the bitmap of the last timed step: written out before anything else launches into it
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out[:(nlines + 31) // 32].cpu().numpy().view(np.uint32))
 
-    accepted = int(regex.match_corpus(corpus).sum(dtype=torch.int64).item())
+    accepted = int(regex.match_corpus(corpus).sum(dtype=torch.int64).item()) if args.full else None
     # the same launches on the stride-2 table AS NUMBERED (a second regex that is forbidden the order search), so that the record
     # carries what the profiled order is worth on this box: three alternating rounds of ten launches each, after the
     # timed region; rank 0 at N = 1 only
     order_ab = None
-    if rank == 0 and world == 1 and regex.table_order is not None:
+    if args.full and rank == 0 and world == 1 and regex.table_order is not None:
         plain = rr.RRegex(pattern, getattr(rr, ENGINES[args.engine]), device=local_rank)
         plain.set_background_order(False)
         for _ in range(10):                                # (the GPU idled while `plain` was compiled on the host: both tables warm before the rounds)
@@ -386,7 +436,6 @@ def main():
     if rank == 0:
         avg_kernel_s = sum(kernel_ms) / len(kernel_ms) / 1e3
         achieved = nbytes / avg_kernel_s / 1e9
-        cold_GBs = nbytes / ((cold_index_ms + cold_match_ms) / 1e3) / 1e9
         res = {
             "metric": "GB/s input scanned (whole job), 256-state regex" if args.workload == "url" else "GB/s input scanned (whole job)",
             "value": round(world * nbytes * args.steps / elapsed / 1e9, 2),
@@ -401,6 +450,7 @@ def main():
             "vs_baseline": None,
             "dtype": "u32",
             "data": "synthetic",
+            "full": args.full,
             "config": {"workload": "BASELINE %s (%d reference states, %s class) over %.2f GiB synthetic lines per GPU"
                                    % (config_name, regex.states_n, "BitSet<%d>" % regex.set_class if regex.set_class else "Roaring", nbytes / 2**30),
                        "pattern_states": regex.states_n, "useful_states": regex.useful_states, "engine": regex.engine_name,
@@ -417,18 +467,20 @@ def main():
                          "frac_of_read_stream_6.4TBs": round(achieved / HBM_ACHIEVABLE_GBS, 4),
                          "kernel_ms_avg": round(avg_kernel_s * 1e3, 4), "kernel_ms_median": round(sorted(kernel_ms)[len(kernel_ms) // 2], 4),
                          "kernel_ms_min": round(min(kernel_ms), 4), "kernel_ms_each_launch": [round(x, 4) for x in kernel_ms],
-                         "launches_before_the_timed_region": 8 + 3 + args.warmup,
+                         "launches_before_the_timed_region": 8 + clock_warm_launches + (3 if args.full else 0) + args.warmup,
                          "algorithmic_bytes_per_launch": nbytes},
-            # the same corpus met for the first time: newline index + one match (nothing reused); never the headline
-            "cold": {"index_ms": round(cold_index_ms, 4), "match_ms": round(cold_match_ms, 4), "GBs": round(cold_GBs, 2),
-                     "frac": round(cold_GBs / HBM_PEAK_GBS, 4),
-                     "one_shot_ms": round(oneshot_ms, 4), "one_shot_GBs": round(nbytes / oneshot_ms / 1e6, 2),
-                     "one_shot_frac": round(nbytes / oneshot_ms / 1e6 / HBM_PEAK_GBS, 4), "one_shot_statistic": "median of 12 calls",
-                     "one_shot_worst_over_median": round(oneshot_worst / oneshot_ms, 3), "one_shot_ms_each_call": oneshot_all,
-                     "one_shot_bitmap": "sized from the line count of an index built earlier (+64)",
-                     "one_shot_cap_n_over_4_ms": round(apriori_ms, 4), "one_shot_cap_n_over_4_frac": round(nbytes / apriori_ms / 1e6 / HBM_PEAK_GBS, 4)},
             "setup": {"generate_s": round(gen_s, 2), "index_ms": round(index_ms, 3)},
         }
+        if args.full:
+            # the same corpus met for the first time: newline index + one match (nothing reused); never the headline
+            cold_GBs = nbytes / ((cold_index_ms + cold_match_ms) / 1e3) / 1e9
+            res["cold"] = {"index_ms": round(cold_index_ms, 4), "match_ms": round(cold_match_ms, 4), "GBs": round(cold_GBs, 2),
+                           "frac": round(cold_GBs / HBM_PEAK_GBS, 4),
+                           "one_shot_ms": round(oneshot_ms, 4), "one_shot_GBs": round(nbytes / oneshot_ms / 1e6, 2),
+                           "one_shot_frac": round(nbytes / oneshot_ms / 1e6 / HBM_PEAK_GBS, 4), "one_shot_statistic": "median of 12 calls",
+                           "one_shot_worst_over_median": round(oneshot_worst / oneshot_ms, 3), "one_shot_ms_each_call": oneshot_all,
+                           "one_shot_bitmap": "sized from the line count of an index built earlier (+64)",
+                           "one_shot_cap_n_over_4_ms": round(apriori_ms, 4), "one_shot_cap_n_over_4_frac": round(nbytes / apriori_ms / 1e6 / HBM_PEAK_GBS, 4)}
         if args.pcie:
             sample = host[:min(nbytes, 4 << 30)]
             regex.match_host(sample[:1 << 20])
@@ -463,7 +515,7 @@ def main():
             torch.cuda.synchronize()
             res["search"]["all_matches_one_call"] = {"GBs": round(3 * nbytes / (time.perf_counter() - t0) / 1e9, 2), "matches": int(s.numel())}
             del first, s, e
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(pattern, host)
         print(json.dumps(res), flush=True)
     if dist is not None:

@@ -1,6 +1,7 @@
+PROBE_OUT=${PROBE_OUT:-probe_out}         # results, relative to the repository root
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-OUT=$R/gpurun_out/fetch_kw; rm -rf $OUT; mkdir -p $OUT; cd $R
+OUT=$R/$PROBE_OUT/fetch_kw; rm -rf $OUT; mkdir -p $OUT; cd $R
 timeout -k 10 150 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/f -- python3 bench.py --steps 2 --warmup 0 --no-cpu-baseline --workload kwlines > $OUT/f.log 2>&1 || exit 1
 python3 - <<PY
 import csv, glob

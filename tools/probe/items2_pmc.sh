@@ -1,7 +1,8 @@
 #!/bin/bash
 # fetched / written bytes and LDS / VALU activity of the indexed items kernels.  usage: items2_pmc.sh <tag> <workload>
+PROBE_OUT=${PROBE_OUT:-probe_out}         # results, relative to the repository root
 tag=${1:-items2pmc}; w=${2:-url}
-out=$PWD/gpurun_out/$tag
+out=$PWD/$PROBE_OUT/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for on in 1 0; do

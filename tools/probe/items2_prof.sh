@@ -1,7 +1,8 @@
 #!/bin/bash
 # kernel trace of tools/probe/items2_ab.py on one workload.  usage: items2_prof.sh <tag> <workload>
+PROBE_OUT=${PROBE_OUT:-probe_out}         # results, relative to the repository root
 tag=${1:-items2}; w=${2:-url}
-out=$PWD/gpurun_out/$tag
+out=$PWD/$PROBE_OUT/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o items -- python3 $GRAFT_REPO_ROOT/tools/probe/items2_ab.py $w > $out/run.log 2>&1

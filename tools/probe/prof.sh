@@ -1,9 +1,10 @@
 #!/bin/bash
 # rocprofv3 passes for the batch kernel (kernel trace; SQ/LDS counters; HBM bytes).  Usage: prof.sh <tag> [bench args]
+PROBE_OUT=${PROBE_OUT:-probe_out}         # results, relative to the repository root
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 TAG=$1; shift
-OUT=$R/gpurun_out/prof_$TAG
+OUT=$R/$PROBE_OUT/prof_$TAG
 mkdir -p $OUT
 cd $R
 timeout -k 10 150 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline "$@" > $OUT/kt.log 2>&1 || exit 1

@@ -1,9 +1,10 @@
 #!/bin/bash
 # rocprofv3 of the first-match search kernel: r04_search_prof.sh <tag> <workload> <bytes>
+PROBE_OUT=${PROBE_OUT:-probe_out}         # results, relative to the repository root
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 TAG=$1; W=$2; N=$3
-OUT=$R/gpurun_out/prof_$TAG; rm -rf $OUT; mkdir -p $OUT; cd $R
+OUT=$R/$PROBE_OUT/prof_$TAG; rm -rf $OUT; mkdir -p $OUT; cd $R
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 tools/probe/search_run.py $W $N 5 > $OUT/kt.log 2>&1 || { tail -5 $OUT/kt.log; exit 1; }
 timeout -k 10 200 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d $OUT/pmc_sq -- python3 tools/probe/search_run.py $W $N 1 > $OUT/pmc_sq.log 2>&1 || { tail -5 $OUT/pmc_sq.log; exit 1; }
 timeout -k 10 200 rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SMEM SQ_WAVES --kernel-trace --output-format csv -d $OUT/pmc_sq2 -- python3 tools/probe/search_run.py $W $N 1 > $OUT/pmc_sq2.log 2>&1 || { tail -5 $OUT/pmc_sq2.log; exit 1; }

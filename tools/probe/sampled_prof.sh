@@ -1,7 +1,8 @@
 #!/bin/bash
+PROBE_OUT=${PROBE_OUT:-probe_out}         # results, relative to the repository root
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
-cd $R; O=$R/gpurun_out/sampled_prof; rm -rf $O; mkdir -p $O
+cd $R; O=$R/$PROBE_OUT/sampled_prof; rm -rf $O; mkdir -p $O
 for w in urltail urlalt; do
   timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$w -- python3 bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline > $O/$w.log 2>&1 || { tail -5 $O/$w.log; exit 1; }
   python3 - <<PY

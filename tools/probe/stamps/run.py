@@ -42,7 +42,9 @@ S = S[S[:, 0, 0] != 0]
 names = ["entry", "tables loaded", "first round done", "main loop done", "follow done", "window out"]
 t0 = S[:, :, 0].min()
 T = (S[:, :, :6] - t0) / 100.0            # 100 MHz -> us ; [wg][wave][phase]
-np.save(os.path.join(ROOT, "gpurun_out", "stamps_%s_%d.npy" % (workload, nbytes >> 20)), S)
+out_dir = os.path.join(ROOT, os.environ.get("PROBE_OUT", "probe_out"))          # results
+os.makedirs(out_dir, exist_ok=True)
+np.save(os.path.join(out_dir, "stamps_%s_%d.npy" % (workload, nbytes >> 20)), S)
 print("== units/wg %d" % units)
 print("== workload %s  %d MiB  stripe %d  workgroups %d  event time %.1f us  stamped span %.1f us" % (workload, nbytes >> 20, corpus.stripe, len(S), ms * 1e3, T[:, :, 5].max()))
 def q(a): return "min %7.1f  med %7.1f  p90 %7.1f  max %7.1f" % (a.min(), np.median(a), np.percentile(a, 90), a.max())

@@ -1,9 +1,10 @@
 #!/bin/bash
 # FETCH_SIZE / WRITE_SIZE (separate passes) of the search kernels and of the one-shot entry on one workload: traffic_check.sh <tag> <workload> <bytes>
+PROBE_OUT=${PROBE_OUT:-probe_out}         # results, relative to the repository root
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 TAG=$1; W=$2; N=$3
-OUT=$R/gpurun_out/traffic_$TAG; rm -rf $OUT; mkdir -p $OUT; cd $R
+OUT=$R/$PROBE_OUT/traffic_$TAG; rm -rf $OUT; mkdir -p $OUT; cd $R
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 100 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/first_$c -- python3 tools/probe/search_run.py $W $N 1 > $OUT/first_$c.log 2>&1 || { tail -5 $OUT/first_$c.log; exit 1; }
   timeout -k 10 100 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/all_$c -- python3 tools/probe/search_all_run.py $W $N 1 > $OUT/all_$c.log 2>&1 || { tail -5 $OUT/all_$c.log; exit 1; }

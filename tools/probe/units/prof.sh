@@ -1,7 +1,8 @@
 #!/bin/bash
+PROBE_OUT=${PROBE_OUT:-probe_out}         # results, relative to the repository root
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
-cd $R; O=$R/gpurun_out/units_prof; rm -rf $O; mkdir -p $O
+cd $R; O=$R/$PROBE_OUT/units_prof; rm -rf $O; mkdir -p $O
 G=$((1<<30)); M2=$((2<<20))
 for v in 0 16 $((M2+16)); do
   timeout -k 10 120 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $O/a_$v -- python3 tools/probe/units/one.py arepeat $G 4096 $v > $O/a_$v.log 2>&1 || { tail -5 $O/a_$v.log; exit 1; }
