@@ -15,6 +15,7 @@
 #include "device.hpp"
 #include "frontend.hpp"
 #include "lower.hpp"
+#include "pack.hpp"
 
 using namespace rrx;
 
@@ -30,30 +31,35 @@ int hip_fail(hipError_t e, const char *what) {
 
 constexpr uint32_t kMaxSubsetStates = 16384;   // subset construction is abandoned beyond this
 
-struct DeviceTables {
-    void *blob = nullptr;
-    dev::NfaDevice nfa;
-    dev::DfaDevice dfa;          // plain form (extents kernel)
-    dev::LineDfaDevice line;     // line-mode form (batch kernel)
-    dev::GroupNfaDevice group;   // group-cooperative NFA (16/32 lanes per string)
-    dev::Dfa2Device dfa2;        // stride-2 line-mode table (corpora without bytes >= 0x80)
-    dev::WaveNfaDevice block;    // wave-resident NFA (up to 65536 positions)
+// One device allocation, freed on its own device.
+struct DeviceAlloc {
+    int device = -1;
+    void *p = nullptr;
+    DeviceAlloc() = default;
+    DeviceAlloc(DeviceAlloc &&o) noexcept : device(o.device), p(o.p) { o.p = nullptr; }
+    ~DeviceAlloc() { reset(); }
+    void reset() { if (p) { (void)hipSetDevice(device); (void)hipFree(p); p = nullptr; } }
+    hipError_t alloc(int dev, size_t bytes) {            // (leaves `dev` the current device)
+        reset(); device = dev;
+        hipError_t e = hipSetDevice(dev);
+        if (e == hipSuccess && (e = hipMalloc(&p, bytes)) != hipSuccess) p = nullptr;
+        return e;
+    }
 };
 
-// The plain table in the wide line-table format with one more column: 0..127 byte values ('\n' an ordinary byte), 128 =
-// any byte >= 0x80, 129 = END OF ITEM (verdict of the row, back to the start row).  For explicit items stepped stripe-wise.
-struct ItemsTableOnDevice {
-    void *blob = nullptr;
-    dev::LineDfaDevice line;
-};
-struct Items2TableOnDevice {
-    void *blob = nullptr;
-    dev::Dfa2Device dfa2;
-};
-struct SearchTablesOnDevice {
-    void *blob = nullptr;
-    dev::SearchChunkDevice chunk;      // the stripe-wise kernel's tables (device.hpp)
-};
+// An image uploaded to a device, and the descriptor(s) of it that the kernels take.
+template <class D> struct OnDevice { DeviceAlloc mem; D d; };      // (mem.p == nullptr: a miss cached by items_table / items2_table)
+
+// The only upload of program tables: `img` into a fresh allocation on `device` (16 bytes of tail beyond the image), its
+// descriptors bound to it.  stream == nullptr: a synchronous copy; otherwise the copy is queued on `stream` and waited for.
+hipError_t upload(int device, const Image &img, DeviceAlloc &out, hipStream_t stream = nullptr) {
+    const std::vector<uint8_t> &b = img.bytes;
+    hipError_t e = out.alloc(device, b.size() + 16);
+    if (e == hipSuccess) e = stream ? hipMemcpyAsync(out.p, b.data(), b.size(), hipMemcpyHostToDevice, stream) : hipMemcpy(out.p, b.data(), b.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && stream) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) img.bind(out.p); else out.reset();
+    return e;
+}
 
 // Small results a call has to hand back to the host (line totals, flags) are written by the call's last kernel into a slot
 // of pinned, device-mapped host memory; the host then only waits for the stream.  (Round 2 read them with three
@@ -104,8 +110,6 @@ struct MailboxGuard {
     }
 };
 
-int instantiated_width(uint32_t W) { return W <= 4 ? (int)W : W <= 6 ? 6 : W <= 8 ? 8 : W <= 12 ? 12 : 16; }
-
 }  // namespace
 
 struct rrx_regex {
@@ -141,8 +145,7 @@ struct rrx_regex {
     mutable DfaProgram sampled_dfa;
     mutable Dfa2Program sampled_dfa2;
     mutable SampledTableStats sampled_stats;
-    struct SampledOnDevice { void *blob = nullptr; dev::Dfa2Device d; };
-    mutable std::map<int, const void *> sampled_counter;   // device -> where the last launch counted its escaped lines (under onepass_mu)
+    mutable std::map<int, DeviceAlloc> sampled_escapes;    // device -> 16 bytes: the last launch's count of its escaped lines (under onepass_mu)
     // The same count, copied by every sampled launch into pinned host memory behind its kernels.
     // The NEXT launch looks at it without waiting (it shows the last launch that has finished): a corpus that escapes from the table
     // - not the text it was learnt from - retires the table (sampled_retired), the regex is back on the NFA engine at its own rate.
@@ -151,13 +154,12 @@ struct rrx_regex {
     mutable std::atomic<bool> sampled_retired{false};
     // (r4) A retired table is LEARNT AGAIN, from the sample of the corpus that retired it (the first one that carries a sample), up to
     // kSampledRelearns times: the build runs like the first one (beside the caller unless RRX_OPT_BACKGROUND_ORDER is 0), the regex stays
-    // on the NFA engine meanwhile, and the new table is subject to the same two guards.  The old device tables are kept until rrx_free
-    // (a launch queued on them may still be running).
+    // on the NFA engine meanwhile, and the new table is subject to the same two guards.  The old device tables are kept (`kept`) until
+    // rrx_free (a launch queued on them may still be running).
     static constexpr uint32_t kSampledRelearns = 3;
     mutable uint32_t sampled_gen = 0;                      // generation of the table in use (under onepass_mu; slot of h_sampled_seen)
     mutable std::vector<std::unique_ptr<OnceTask>> sampled_relearn;      // (under onepass_mu)
-    mutable std::vector<std::pair<int, void *>> sampled_old_blobs;       // (under mu)
-    mutable std::map<int, SampledOnDevice> sampled_on_device;
+    mutable std::map<int, OnDevice<dev::Dfa2Device>> sampled_on_device;
     bool sampled_eligible() const { return requested_engine == RRX_ENGINE_AUTO && engine == RRX_ENGINE_NFA && !has_dfa && has_nfa; }
     // pieces x piece_bytes of text -> the table; false: nothing usable came out (the engine stays as it is)
     bool build_sampled(const uint8_t *text, uint32_t pieces, uint32_t piece_bytes, bool replace = false) const {
@@ -179,7 +181,7 @@ struct rrx_regex {
             // no sampled launch is being queued while the programs change (onepass_mu, taken before mu as match_corpus_sampled does)
             std::lock_guard<std::mutex> launches(onepass_mu);
             std::lock_guard<std::mutex> lock(mu);
-            for (auto &kv : sampled_on_device) if (kv.second.blob) sampled_old_blobs.emplace_back(kv.first, kv.second.blob);
+            for (auto &kv : sampled_on_device) kept.push_back(std::move(kv.second.mem));
             sampled_on_device.clear();
             sampled_dfa = std::move(d); sampled_dfa2 = std::move(d2); sampled_stats = st;
             sampled_gen++;                               // (its own slot of h_sampled_seen: a late count of the old table's launches does not reach it)
@@ -209,55 +211,14 @@ struct rrx_regex {
     }
     int sampled_tables(int device, dev::Dfa2Device *out) const {
         std::lock_guard<std::mutex> lock(mu);
-        auto it = sampled_on_device.find(device);
-        if (it != sampled_on_device.end()) { *out = it->second.d; return RRX_OK; }
-        HIP_TRY(hipSetDevice(device));
-        std::vector<uint32_t> T2;
-        std::vector<uint16_t> P;
-        SampledOnDevice t;
-        build_dfa2_arrays_of(sampled_dfa2, {}, {}, T2, P, t.d);
-        const size_t pb = (P.size() * 2 + 15) & ~(size_t)15;
-        HIP_TRY(hipMalloc(&t.blob, pb + T2.size() * 4 + 16));
-        hipError_t e = hipMemcpy(t.blob, P.data(), P.size() * 2, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(static_cast<uint8_t *>(t.blob) + pb, T2.data(), T2.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(t.blob); return hip_fail(e, "sampled table upload"); }
-        t.d.P = static_cast<const uint16_t *>(t.blob);
-        t.d.T2 = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(t.blob) + pb);
-        sampled_on_device.emplace(device, t);
-        *out = t.d;
-        return RRX_OK;
+        const dev::Dfa2Device *d = nullptr;
+        const int rc = upload_once(sampled_on_device, device, false, [&](Image &img, dev::Dfa2Device &t) { return pack_dfa2(sampled_dfa2, {}, {}, img, t); }, &d);
+        if (!rc) *out = *d;
+        return rc;
     }
-    mutable std::vector<std::pair<int, void *>> t2_extra_blobs;      // tables uploaded again in the profiled order (device, blob)
-    // The stride-2 tables as they go to the device, in the current order: T2 rows of `ncols | 1` entries (odd), R interleaved
-    // copies, entry = LDS byte offset of the next row | lines << 16 | verdicts << 24; P = pair -> byte offset of its column.
-    // `rows` / `cols`: an order to build for (else the current one: call with `mu` held)
-    void build_dfa2_arrays(std::vector<uint32_t> &T2, std::vector<uint16_t> &P, dev::Dfa2Device &d, const std::vector<uint32_t> *rows = nullptr,
-                           const std::vector<uint32_t> *cols = nullptr) const {
-        build_dfa2_arrays_of(dfa2, rows ? *rows : t2_row_slot, cols ? *cols : t2_col_slot, T2, P, d);
-    }
-    static void build_dfa2_arrays_of(const Dfa2Program &dfa2, const std::vector<uint32_t> &rs, const std::vector<uint32_t> &cs, std::vector<uint32_t> &T2,
-                                     std::vector<uint16_t> &P, dev::Dfa2Device &d) {
-        const uint32_t D2 = dfa2.nstates, C2 = dfa2.ncols;
-        const uint32_t s2 = C2 | 1u;
-        uint32_t rep2 = 0;
-        while (rep2 < 5 && (size_t)D2 * s2 * 4 * (2u << rep2) <= dev::kDfa2TableBudget && (size_t)C2 * 4 * (2u << rep2) <= 65535) rep2++;
-        const uint32_t R2 = 1u << rep2;
-        T2.assign((size_t)D2 * s2 * R2, 0);
-        const bool ordered = rs.size() == D2 && cs.size() == C2 && rs[0] == 0;
-        auto row_slot = [&](uint32_t st) { return ordered ? rs[st] : st; };
-        auto col_slot = [&](uint32_t col) { return ordered ? cs[col] : col; };
-        for (uint32_t st = 0; st < D2; st++)
-            for (uint32_t col = 0; col < C2; col++) {
-                const uint32_t v = dfa2.next2[(size_t)st * C2 + col];
-                const uint32_t row_off = row_slot(v & 0xffffu) * s2 * 4 * R2;
-                for (uint32_t k = 0; k < R2; k++) T2[((size_t)row_slot(st) * s2 + col_slot(col)) * R2 + k] = (row_off + 4 * k) | (v & 0xffff0000u);
-            }
-        const unsigned dim = dfa2.pair_dim;                 // 128; items form: 129 (code 128 = END OF ITEM: a row more, and the pad column 128)
-        P.assign(dim * dev::kDfa2PStride, 0);
-        for (unsigned c1 = 0; c1 < dim; c1++)
-            for (unsigned c2 = 0; c2 < dim; c2++) P[c1 * dev::kDfa2PStride + c2] = (uint16_t)(col_slot(dfa2.pair_col[c1 * dim + c2]) * 4 * R2);
-        d.nrows = D2; d.stride = s2 * R2; d.start_off = row_slot(dfa2.start) * s2 * 4 * R2; d.rep_log2 = rep2;
-    }
+    // Device memory that launches may still be reading, kept until rrx_free: the sampled tables of earlier generations, the
+    // stride-2 tables uploaded again in the profiled order (under `mu`)
+    mutable std::vector<DeviceAlloc> kept;
     bool t2_order_applies() const {                      // single-copy tables only: interleaved copies already keep lanes apart
         return has_dfa2 && (size_t)dfa2.nstates * (dfa2.ncols | 1u) * 4 * 2 > dev::kDfa2TableBudget;
     }
@@ -266,40 +227,28 @@ struct rrx_regex {
     // to read which devices are up, and to swap the slot vectors and the descriptors.  A device that comes up in between gets the
     // numbered order and keeps it (its own arrays agree with each other; results never depend on the order).
     void apply_t2_order(std::vector<uint32_t> &&rows, std::vector<uint32_t> &&cols, const Dfa2OrderStats &st) const {
-        std::vector<std::pair<int, dev::Dfa2Device>> up;
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            for (auto &kv : on_device) up.emplace_back(kv.first, kv.second.dfa2);
-        }
-        struct Uploaded { int device; void *blob; dev::Dfa2Device d; };
-        std::vector<Uploaded> done;
-        for (auto &kv : up) {
-            std::vector<uint32_t> T2;
-            std::vector<uint16_t> P;
-            dev::Dfa2Device d = kv.second;
-            build_dfa2_arrays(T2, P, d, &rows, &cols);
-            const size_t pb = (P.size() * 2 + 15) & ~(size_t)15;
-            void *blob = nullptr;
+        std::vector<int> up;
+        { std::lock_guard<std::mutex> lock(mu); for (auto &kv : on_device) up.push_back(kv.first); }
+        std::vector<std::pair<int, OnDevice<dev::Dfa2Device>>> done;
+        for (int device : up) {
+            Image img;
+            OnDevice<dev::Dfa2Device> t;
+            (void)pack_dfa2(dfa2, rows, cols, img, t.d);
             hipStream_t st2 = nullptr;
-            bool ok = hipSetDevice(kv.first) == hipSuccess && hipMalloc(&blob, pb + T2.size() * 4) == hipSuccess &&
-                      hipStreamCreateWithFlags(&st2, hipStreamNonBlocking) == hipSuccess;
-            if (ok) ok = hipMemcpyAsync(blob, P.data(), P.size() * 2, hipMemcpyHostToDevice, st2) == hipSuccess &&
-                         hipMemcpyAsync(static_cast<uint8_t *>(blob) + pb, T2.data(), T2.size() * 4, hipMemcpyHostToDevice, st2) == hipSuccess &&
-                         hipStreamSynchronize(st2) == hipSuccess;
+            bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&st2, hipStreamNonBlocking) == hipSuccess &&
+                      upload(device, img, t.mem, st2) == hipSuccess;
             if (st2) (void)hipStreamDestroy(st2);
-            if (!ok) { (void)hipGetLastError(); if (blob) (void)hipFree(blob); continue; }       // (that device keeps the numbered order)
-            d.P = static_cast<const uint16_t *>(blob);
-            d.T2 = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(blob) + pb);
-            done.push_back(Uploaded{kv.first, blob, d});
+            if (!ok) { (void)hipGetLastError(); continue; }                                    // (that device keeps the numbered order)
+            done.emplace_back(device, std::move(t));
         }
         std::lock_guard<std::mutex> lock(mu);
         rrx_regex *self = const_cast<rrx_regex *>(this);
         self->t2_row_slot.swap(rows); self->t2_col_slot.swap(cols);
         t2_order_stats = st;
-        for (const Uploaded &u : done) {
-            t2_extra_blobs.emplace_back(u.device, u.blob);
-            auto it = on_device.find(u.device);
-            if (it != on_device.end()) it->second.dfa2 = u.d;
+        for (auto &u : done) {
+            auto it = on_device.find(u.first);
+            if (it != on_device.end()) it->second.d.dfa2 = u.second.d;
+            kept.push_back(std::move(u.second.mem));
         }
     }
     // First match against a corpus that carries a text sample: start the search in the background (the match itself, and the
@@ -319,7 +268,7 @@ struct rrx_regex {
     bool line_wide = false;      // DFA engine: byte-indexed rows (<= kWideMaxStates states) or class-indexed rows
     bool line_global = false;    // DFA engine: class-indexed table too large for LDS, kept in global memory
     mutable std::mutex mu;
-    mutable std::map<int, DeviceTables> on_device;
+    mutable std::map<int, OnDevice<DeviceTables>> on_device;
     // search (built on first use): the forward "anything, then the pattern" DFA and the reverse DFA
     mutable int search_state = 0;        // 0 = not built, 1 = built, -1 = does not fit
     mutable DfaProgram search_fwd, search_rev;
@@ -327,28 +276,30 @@ struct rrx_regex {
     mutable SearchLine2Program search_line2;    // its stride-2 form, what the stripe-wise kernel runs (nrows = 0: not built)
     mutable dev::SearchChunkDevice chunk_proto; // its layout on the device, without the pointers (nrows = 0: the line-per-lane kernels)
     mutable bool search_nullable = false;       // the pattern accepts the empty string: every offset is a match, no table (empty_matches)
-    mutable std::map<int, SearchTablesOnDevice> search_on_device;
-    mutable std::map<int, ItemsTableOnDevice> items_on_device;
-    mutable std::map<int, Items2TableOnDevice> items2_on_device;
+    mutable std::map<int, OnDevice<dev::SearchChunkDevice>> search_on_device;
+    // The plain table in the wide line-table format with one more column: 0..127 byte values ('\n' an ordinary byte), 128 = any
+    // byte >= 0x80, 129 = END OF ITEM (verdict of the row, back to the start row).  For explicit items stepped stripe-wise.
+    mutable std::map<int, OnDevice<dev::LineDfaDevice>> items_on_device;
+    mutable std::map<int, OnDevice<dev::Dfa2Device>> items2_on_device;
     mutable Dfa2Program items2_prog;                   // lowered at the first batch of items with separators
     mutable int items2_state = 0;                      // 0 not tried, 1 there, 2 does not fit
     std::atomic<int> items_stride2{1};                 // RRX_OPT_ITEMS_STRIDE2 (0: the byte-stride items kernel for trim 1 as well)
     // Scratch of the single-string entries (rrx_match_string / rrx_match_cstr): one grow-only device buffer per device,
     // kept across calls (a hipMalloc + hipFree pair per string cost more than the match itself).  `scratch_mu` is held
     // for the whole call: those entries are synchronous, concurrent callers of one regex take turns.
-    struct Scratch { void *p = nullptr; size_t cap = 0; };
+    struct Scratch { DeviceAlloc mem; size_t cap = 0; };
     mutable std::mutex scratch_mu;
     mutable std::map<int, Scratch> scratch;
     int scratch_for(int device, size_t bytes, void **out) const {      // call with `scratch_mu` held
         Scratch &sc = scratch[device];
         if (sc.cap < bytes) {
-            if (sc.p) { (void)hipFree(sc.p); sc.p = nullptr; sc.cap = 0; }
+            sc.cap = 0;
             const size_t want = bytes < 4096 ? 4096 : bytes + bytes / 4;
-            hipError_t e = hipMalloc(&sc.p, want);
-            if (e != hipSuccess) { sc.p = nullptr; return hip_fail(e, "hipMalloc(single-string scratch)"); }
+            hipError_t e = sc.mem.alloc(device, want);
+            if (e != hipSuccess) return hip_fail(e, "hipMalloc(single-string scratch)");
             sc.cap = want;
         }
-        *out = sc.p;
+        *out = sc.mem.p;
         return RRX_OK;
     }
 
@@ -357,7 +308,10 @@ struct rrx_regex {
     // Users on different streams are ordered on the DEVICE by an event recorded after each use (the host never waits):
     // onepass_for(..., stream) makes `stream` wait for the last user, onepass_done(stream) marks the new last use; both under
     // `onepass_mu`, held from the one to the other.
-    struct EventScratch { void *p = nullptr; size_t cap = 0; hipEvent_t last = nullptr; bool used = false; };
+    struct EventScratch {                                // (the last user has finished before `mem` is freed)
+        DeviceAlloc mem; size_t cap = 0; hipEvent_t last = nullptr; bool used = false;
+        ~EventScratch() { if (last) { (void)hipSetDevice(mem.device); (void)hipEventSynchronize(last); (void)hipEventDestroy(last); } }
+    };
     mutable std::mutex onepass_mu;
     mutable std::map<int, EventScratch> onepass_scratch;
     int onepass_for(int device, size_t bytes, void **out, hipStream_t stream) const {      // call with `onepass_mu` held
@@ -367,16 +321,16 @@ struct rrx_regex {
             if (e != hipSuccess) { sc.last = nullptr; return hip_fail(e, "hipEventCreate(scratch)"); }
         }
         if (sc.cap < bytes) {
-            if (sc.p) { (void)hipEventSynchronize(sc.last); (void)hipFree(sc.p); sc.p = nullptr; sc.cap = 0; sc.used = false; }
-            hipError_t e = hipMalloc(&sc.p, bytes);
-            if (e != hipSuccess) { sc.p = nullptr; return hip_fail(e, "hipMalloc(one-pass scratch)"); }
+            if (sc.mem.p) { (void)hipEventSynchronize(sc.last); sc.mem.reset(); sc.cap = 0; sc.used = false; }
+            hipError_t e = sc.mem.alloc(device, bytes);
+            if (e != hipSuccess) return hip_fail(e, "hipMalloc(one-pass scratch)");
             sc.cap = bytes;
         }
         if (sc.used) {
             hipError_t e = hipStreamWaitEvent(stream, sc.last, 0);
             if (e != hipSuccess) return hip_fail(e, "hipStreamWaitEvent(scratch)");
         }
-        *out = sc.p;
+        *out = sc.mem.p;
         return RRX_OK;
     }
     int onepass_done(int device, hipStream_t stream) const {                               // call with `onepass_mu` held
@@ -387,28 +341,15 @@ struct rrx_regex {
         return RRX_OK;
     }
 
+    // (device memory is freed by its owners, DeviceAlloc and EventScratch, once the body has waited for what may still use it)
     ~rrx_regex() {
         t2_order.wait();
         sampled_build.wait();
         for (auto &task : sampled_relearn) task->wait();
         if (h_sampled_seen) {                            // (a copy into it may still be queued on the devices that ran the sampled table)
-            for (auto &kv : sampled_on_device) { (void)hipSetDevice(kv.first); (void)hipDeviceSynchronize(); }
-            for (auto &kv : sampled_old_blobs) { (void)hipSetDevice(kv.first); (void)hipDeviceSynchronize(); }
+            for (auto &kv : sampled_escapes) { (void)hipSetDevice(kv.first); (void)hipDeviceSynchronize(); }
             (void)hipHostFree(h_sampled_seen);
         }
-        for (auto &kv : sampled_on_device) if (kv.second.blob) { (void)hipSetDevice(kv.first); (void)hipFree(kv.second.blob); }
-        for (auto &kv : sampled_old_blobs) { (void)hipSetDevice(kv.first); (void)hipFree(kv.second); }
-        for (auto &kv : t2_extra_blobs) { (void)hipSetDevice(kv.first); (void)hipFree(kv.second); }
-        for (auto &kv : scratch) if (kv.second.p) { (void)hipSetDevice(kv.first); (void)hipFree(kv.second.p); }
-        for (auto &kv : onepass_scratch) {
-            (void)hipSetDevice(kv.first);
-            if (kv.second.last) { (void)hipEventSynchronize(kv.second.last); (void)hipEventDestroy(kv.second.last); }
-            if (kv.second.p) (void)hipFree(kv.second.p);
-        }
-        for (auto &kv : on_device) if (kv.second.blob) { (void)hipSetDevice(kv.first); (void)hipFree(kv.second.blob); }
-        for (auto &kv : search_on_device) if (kv.second.blob) { (void)hipSetDevice(kv.first); (void)hipFree(kv.second.blob); }
-        for (auto &kv : items_on_device) if (kv.second.blob) { (void)hipSetDevice(kv.first); (void)hipFree(kv.second.blob); }
-        for (auto &kv : items2_on_device) if (kv.second.blob) { (void)hipSetDevice(kv.first); (void)hipFree(kv.second.blob); }
     }
     // The stride-2 table of explicit items with a separator byte each (trim 1; lower_dfa2's items form): nullptr where the regex
     // has no stride-2 table or the items form - one symbol more - does not fit the same LDS region.
@@ -420,62 +361,35 @@ struct rrx_regex {
         return items2_state == 1;
     }
     bool items2_program() const { std::lock_guard<std::mutex> lock(mu); return items2_program_locked(); }
+    // The image that `pack` fills (false: none) on `device`, uploaded at the first use (call with `mu` held).  No image or a failed
+    // upload: an error, tried again at the next call - or with `keep_miss` a miss cached for good (*out = nullptr, RRX_OK).
+    template <class D, class Pack> int upload_once(std::map<int, OnDevice<D>> &cache, int device, bool keep_miss, Pack pack, const D **out) const {
+        auto it = cache.find(device);
+        if (it == cache.end()) {
+            Image img;
+            OnDevice<D> t;
+            const bool packed = pack(img, t.d);
+            const hipError_t e = packed ? upload(device, img, t.mem) : hipSuccess;
+            if (!keep_miss && !packed) return fail(RRX_ERR_UNSUPPORTED, "automaton too large for the device tables of its engine");
+            if (!keep_miss && e != hipSuccess) return hip_fail(e, "device table upload");
+            it = cache.emplace(device, std::move(t)).first;
+        }
+        *out = it->second.mem.p ? &it->second.d : nullptr;
+        return RRX_OK;
+    }
+    // The items tables: nullptr where the regex has none that fits (the caller runs the other kernel)
     const dev::Dfa2Device *items2_table(int device) const {
         std::lock_guard<std::mutex> lock(mu);
-        auto it = items2_on_device.find(device);
-        if (it != items2_on_device.end()) return it->second.blob ? &it->second.dfa2 : nullptr;
-        Items2TableOnDevice t;
-        if (items2_program_locked() && hipSetDevice(device) == hipSuccess) {
-            std::vector<uint32_t> T2;
-            std::vector<uint16_t> P;
-            build_dfa2_arrays_of(items2_prog, std::vector<uint32_t>(), std::vector<uint32_t>(), T2, P, t.dfa2);
-            const size_t pb = (P.size() * 2 + 15) & ~(size_t)15;
-            if (pb <= dev::kDfa2PItemsBytes && hipMalloc(&t.blob, dev::kDfa2PItemsBytes + T2.size() * 4) == hipSuccess) {
-                if (hipMemset(t.blob, 0, dev::kDfa2PItemsBytes) != hipSuccess ||
-                    hipMemcpy(t.blob, P.data(), P.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(static_cast<uint8_t *>(t.blob) + dev::kDfa2PItemsBytes, T2.data(), T2.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-                    (void)hipFree(t.blob); t.blob = nullptr;
-                }
-            }
-            t.dfa2.P = static_cast<const uint16_t *>(t.blob);
-            t.dfa2.T2 = t.blob ? reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(t.blob) + dev::kDfa2PItemsBytes) : nullptr;
-        }
-        auto ins = items2_on_device.emplace(device, t);
-        return ins.first->second.blob ? &ins.first->second.dfa2 : nullptr;
+        const dev::Dfa2Device *d = nullptr;
+        auto pack = [&](Image &img, dev::Dfa2Device &t) { return items2_program_locked() && pack_dfa2(items2_prog, {}, {}, img, t, dev::kDfa2PItemsBytes); };
+        (void)upload_once(items2_on_device, device, true, pack, &d);
+        return d;
     }
-    // nullptr: the plain table has too many states for 16-bit row offsets (or there is none)
-    const dev::LineDfaDevice *items_table(int device) const {
+    const dev::LineDfaDevice *items_table(int device) const {       // (none: more states than 16-bit row offsets allow)
         std::lock_guard<std::mutex> lock(mu);
-        auto it = items_on_device.find(device);
-        if (it != items_on_device.end()) return it->second.blob ? &it->second.line : nullptr;
-        ItemsTableOnDevice t;
-        // rows of kItemColumns entries (odd: a column's entries of different rows spread over all LDS banks), R interleaved
-        // copies like the wide line table (lane l reads copy l % R: only banks congruent to l mod R)
-        const uint32_t D = dfa.nstates, stride = dev::kItemColumns;
-        uint32_t rep = 0;
-        while (rep < 3 && (size_t)D * stride * 4 * (2u << rep) <= 60 * 1024) rep++;
-        const uint32_t R = 1u << rep, row_bytes = stride * 4 * R;
-        if (D && (size_t)D * row_bytes <= 65535 && hipSetDevice(device) == hipSuccess) {
-            std::vector<uint32_t> T((size_t)D * stride * R, 0);
-            for (uint32_t q = 0; q < D; q++)
-                for (uint32_t c = 0; c < stride; c++) {
-                    uint32_t v;
-                    if (c <= 128) {                                                      // byte 2, bit 7: the row it leads to is accepting (what a trim-0
-                        const uint32_t nx = dfa.next[(size_t)q * dfa.ncls + dfa.cls[c]];  // item that ends on this byte reports; as a shift count it is 0)
-                        v = nx * row_bytes | (dfa.accepting[nx] ? 0x80u << 16 : 0u);
-                    }
-                    else if (c == dev::kItemEndColumn) v = dfa.start * row_bytes | 1u << 16 | (dfa.accepting[q] ? 1u << 24 : 0u);
-                    else v = 0;                                                          // padding column: never read
-                    for (uint32_t k = 0; k < R; k++) T[((size_t)q * stride + c) * R + k] = (v & 0xffff0000u) | ((v & 0xffffu) + 4 * k);
-                }
-            if (hipMalloc(&t.blob, T.size() * 4 + 16) == hipSuccess) {
-                if (hipMemcpy(t.blob, T.data(), T.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(t.blob); t.blob = nullptr; }
-            }
-            t.line.nrows = D; t.line.stride = stride * R; t.line.start_off = dfa.start * row_bytes; t.line.wide = 1; t.line.rep_log2 = rep; t.line.in_global = 0;
-            t.line.table = static_cast<const uint32_t *>(t.blob);
-        }
-        auto ins = items_on_device.emplace(device, t);
-        return ins.first->second.blob ? &ins.first->second.line : nullptr;
+        const dev::LineDfaDevice *d = nullptr;
+        (void)upload_once(items_on_device, device, true, [&](Image &img, dev::LineDfaDevice &t) { return pack_items(dfa, img, t); }, &d);
+        return d;
     }
 
     // Host side of the search tables (call with `mu` held).  RRX_OK also for a pattern that accepts the empty string: it needs
@@ -505,15 +419,10 @@ struct rrx_regex {
             // window, else HBM/L2 (device.hpp: SearchChunkDevice)
             const SearchLine2Program &s2 = search_line2;
             if (s2.nrows && search_fwd.ncls < 128) {
-                dev::SearchChunkDevice c;
-                c.nrows = s2.nrows; c.ncols2 = s2.ncols; c.start_row = s2.start; c.skip_row = s2.skip;
-                c.nr = search_rev.nstates; c.ncls = search_fwd.ncls; c.start_r = search_rev.start;
-                uint32_t rb = (2 * s2.ncols + 3) & ~3u;
-                if (((rb >> 2) & 1u) == 0) rb += 4;                           // an odd number of dwords per row: rows spread over the LDS banks
-                c.row_bytes = rb; c.base_row = (dev::kSearchP8Bytes + rb - 1) / rb; c.in_global = 0;
+                dev::SearchChunkDevice c = search_chunk_layout(s2, search_fwd, search_rev, /*in_global=*/false);
                 bool fits = s2.ncols <= 127 && c.base_row + s2.nrows <= 4096 && dev::search_chunks_lds_bytes(c) <= dev::kSearchChunkLdsBudget;
                 if (!fits) {
-                    c.row_bytes = 0; c.base_row = 0; c.in_global = 1;
+                    c = search_chunk_layout(s2, search_fwd, search_rev, /*in_global=*/true);
                     fits = dev::search_chunks_lds_bytes(c) <= dev::kSearchChunkLdsBudget;      // (the reverse table has no global form)
                 }
                 if (fits) chunk_proto = c;
@@ -531,268 +440,26 @@ struct rrx_regex {
         if (rc) return rc;
         *out = nullptr;
         if (search_nullable) return RRX_OK;
-        auto it = search_on_device.find(device);
-        if (it != search_on_device.end()) { *out = &it->second.chunk; return RRX_OK; }
-        HIP_TRY(hipSetDevice(device));
-        std::vector<uint8_t> host;
-        auto put = [&](const void *p, size_t n) { size_t off = (host.size() + 15) & ~(size_t)15; host.resize(off + n); std::memcpy(host.data() + off, p, n); return off; };
-        const size_t oC = put(search_fwd.cls, 256);
-        SearchTablesOnDevice t;
-        // The line-mode product table in its stride-2 form (lower_search_line2), laid out for LDS (16-bit entries, a byte-wide
-        // pair table) or for HBM/L2 (32-bit entries, a 16-bit pair table in LDS): device.hpp, SearchChunkDevice.
-        size_t oP = 0, oT = 0, oTA = 0, oRV = 0;
-        const uint32_t K = search_fwd.ncls, NR = search_rev.nstates;
-        const SearchLine2Program &s2 = search_line2;
-        t.chunk = chunk_proto;
-        if (!t.chunk.in_global) {
-            const uint32_t rb = t.chunk.row_bytes, br = t.chunk.base_row;
-            std::vector<uint8_t> p8(dev::kSearchP8Bytes, 0);
-            for (unsigned c1 = 0; c1 < 128; c1++)
-                for (unsigned c2 = 0; c2 < 128; c2++) p8[c1 * dev::kSearchP8Stride + c2] = (uint8_t)(2 * s2.pair_col[c1 * 128 + c2]);
-            auto lay = [&](const std::vector<uint32_t> &src) {
-                std::vector<uint16_t> T((size_t)s2.nrows * (rb / 2), 0);
-                for (uint32_t r = 0; r < s2.nrows; r++)
-                    for (uint32_t c = 0; c < s2.ncols; c++) {
-                        const uint32_t v = src[(size_t)r * s2.ncols + c];
-                        T[(size_t)r * (rb / 2) + c] = (uint16_t)((br + (v & 0xffffffu)) << 4 | (v >> 24));
-                    }
-                return T;
-            };
-            const std::vector<uint16_t> T = lay(s2.first), TA = lay(s2.all);
-            oP = put(p8.data(), p8.size());
-            oT = put(T.data(), T.size() * 2);
-            oTA = put(TA.data(), TA.size() * 2);
-        } else {
-            std::vector<uint16_t> p16((size_t)128 * dev::kSearchP16Stride, 0);
-            for (unsigned c1 = 0; c1 < 128; c1++)
-                for (unsigned c2 = 0; c2 < 128; c2++) p16[c1 * dev::kSearchP16Stride + c2] = (uint16_t)(4 * s2.pair_col[c1 * 128 + c2]);
-            auto lay = [&](const std::vector<uint32_t> &src) {
-                std::vector<uint32_t> T(src.size());
-                for (size_t i = 0; i < src.size(); i++) T[i] = (src[i] & 0xffffffu) * s2.ncols * 4u | (src[i] >> 24) << 28;
-                return T;
-            };
-            const std::vector<uint32_t> T = lay(s2.first), TA = lay(s2.all);
-            oP = put(p16.data(), p16.size() * 2);
-            oT = put(T.data(), T.size() * 4);
-            oTA = put(TA.data(), TA.size() * 4);
-        }
-        {
-            std::vector<uint16_t> rv(((size_t)NR * K + 1) & ~(size_t)1, 0);
-            for (size_t i = 0; i < (size_t)NR * K; i++) { const uint16_t nx = search_rev.next[i]; rv[i] = (uint16_t)(nx | (search_rev.accepting[nx] ? 0x8000u : 0u)); }
-            oRV = put(rv.data(), rv.size() * 2);
-        }
-        HIP_TRY(hipMalloc(&t.blob, host.size() + 16));
-        hipError_t e = hipMemcpy(t.blob, host.data(), host.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(t.blob); return hip_fail(e, "search table upload"); }
-        const uint8_t *base = static_cast<const uint8_t *>(t.blob);
-        if (t.chunk.in_global) {
-            t.chunk.P16 = reinterpret_cast<const uint16_t *>(base + oP);
-            t.chunk.G2 = reinterpret_cast<const uint32_t *>(base + oT); t.chunk.G2_all = reinterpret_cast<const uint32_t *>(base + oTA);
-        } else {
-            t.chunk.P8 = base + oP;
-            t.chunk.T2 = reinterpret_cast<const uint16_t *>(base + oT); t.chunk.T2_all = reinterpret_cast<const uint16_t *>(base + oTA);
-        }
-        t.chunk.rev = reinterpret_cast<const uint16_t *>(base + oRV);
-        t.chunk.cls = base + oC;
-        auto ins = search_on_device.emplace(device, t);
-        *out = &ins.first->second.chunk;
-        return RRX_OK;
+        auto pack = [&](Image &img, dev::SearchChunkDevice &t) { pack_search(search_line2, search_fwd, search_rev, chunk_proto, img, t); return true; };
+        return upload_once(search_on_device, device, false, pack, out);
     }
 
     // Upload the program for `device` once; returns the device-side descriptors.
     int tables(int device, const DeviceTables **out) const {
         std::lock_guard<std::mutex> lock(mu);
-        auto it = on_device.find(device);
-        if (it != on_device.end()) { *out = &it->second; return RRX_OK; }
-        HIP_TRY(hipSetDevice(device));
-        DeviceTables t;
-        std::vector<uint8_t> host;
-        auto put = [&](const void *p, size_t n) { size_t off = (host.size() + 15) & ~(size_t)15; host.resize(off + n); std::memcpy(host.data() + off, p, n); return off; };
-        size_t oB = 0, oX = 0, oC = 0, oN = 0, oA = 0, oT = 0, oL = 0, oP2 = 0, oT2 = 0;
-        size_t oM = 0;
-        size_t oCL = 0, oCP = 0, oXI = 0, oXO = 0, oXT = 0;
-        if (engine == RRX_ENGINE_NFA_BLOCK || engine == RRX_ENGINE_NFA_SPARSE) {
-            // wave-resident form: 64 lanes x WL words, a B row per byte value (+ the line-mode '\n' row), exception edges as CSR
-            const uint32_t W = nfa_block.W, N = nfa_block.nbits;
-            // (word w of the set sits at flat index w - dense form: lane w / WL, index w % WL; sparse form: row w / 64, lane w % 64)
-            const uint32_t WL = engine == RRX_ENGINE_NFA_SPARSE ? dev::sparse_rows(W) : dev::wave_words_per_lane(W);
-            const uint32_t WP = 64 * WL;
-            std::vector<uint32_t> M((size_t)3 * WP, 0), B((size_t)257 * WP, 0);
-            const std::vector<uint32_t> *src[3] = {&nfa_block.fin, &nfa_block.self, &nfa_block.excm};
-            for (int k = 0; k < 3; k++) for (uint32_t w = 0; w < W; w++) M[(size_t)k * WP + w] = (*src[k])[w];
-            for (uint32_t c = 1; c < 128; c++)                            // 0x00 and >= 0x80: empty rows
-                for (uint32_t w = 0; w < W; w++) B[(size_t)c * WP + w] = nfa_block.B[(size_t)c * W + w];
-            B[(size_t)256 * WP] = 1u;                                     // '\n' in line mode: {position 0}
-            std::vector<uint32_t> xt = nfa_block.xtgt;
-            if (xt.empty()) xt.push_back(0);
-            oM = put(M.data(), M.size() * 4);
-            oB = put(B.data(), B.size() * 4);
-            oXO = put(nfa_block.xoff.data(), nfa_block.xoff.size() * 4);
-            oXT = put(xt.data(), xt.size() * 4);
-            t.block.WL = WL; t.block.nbits = N;
-            if (engine == RRX_ENGINE_NFA_SPARSE) {                        // rows per byte class too (LDS-resident when they fit)
-                const uint32_t K = trimmed.ncls;
-                std::vector<uint32_t> BC((size_t)K * WP, 0);
-                for (uint32_t k = 1; k < K; k++)
-                    for (uint32_t w = 0; w < W; w++) BC[(size_t)k * WP + w] = nfa_block.B[(size_t)trimmed.cls_rep[k] * W + w];
-                oCL = put(BC.data(), BC.size() * 4);
-                oCP = put(trimmed.cls, 256);
-                t.block.ncls = K;
+        return upload_once(on_device, device, false, [&](Image &img, DeviceTables &t) {
+            if (engine == RRX_ENGINE_NFA_BLOCK || engine == RRX_ENGINE_NFA_SPARSE) {
+                const bool sparse = engine == RRX_ENGINE_NFA_SPARSE;
+                pack_wave_nfa(nfa_block, trimmed, sparse ? dev::sparse_rows(nfa_block.W) : dev::wave_words_per_lane(nfa_block.W), sparse, img, t.block);
+            } else if (engine == RRX_ENGINE_NFA_WAVE) {
+                return pack_group_nfa(nfa_wave, trimmed, img, t.group);      // (false: beyond the group-cooperative engine)
+            } else if (engine == RRX_ENGINE_NFA) {
+                pack_lane_nfa(nfa, img, t.nfa);
+            } else {
+                pack_dfa_tables(dfa, line_wide, line_global, has_dfa2 ? &dfa2 : nullptr, t2_row_slot, t2_col_slot, img, t);
             }
-            for (uint32_t w = 0; w < W; w++) {
-                if (nfa_block.self[w]) t.block.self_words |= 1u << (w % WL);
-                if (nfa_block.excm[w]) t.block.exc_words |= 1u << (w % WL);
-            }
-        } else if (engine == RRX_ENGINE_NFA_WAVE) {
-            // group-cooperative form: G lanes x K words (device.hpp: group_geometry), a B row per byte CLASS
-            const uint32_t W = nfa_wave.W, N = nfa_wave.nbits;
-            uint32_t G = 0, K = 0;
-            if (!dev::group_geometry(N, &G, &K)) return fail(RRX_ERR_UNSUPPORTED, "automaton too large for the group-cooperative engine");
-            const uint32_t WP = G * K, NC = trimmed.ncls;
-            std::vector<uint32_t> M((size_t)3 * WP, 0), B((size_t)NC * WP, 0);
-            const std::vector<uint32_t> *src[3] = {&nfa_wave.fin, &nfa_wave.self, &nfa_wave.excm};
-            for (int k = 0; k < 3; k++) for (uint32_t w = 0; w < W; w++) M[(size_t)k * WP + w] = (*src[k])[w];
-            for (uint32_t cl = 1; cl < NC; cl++) {                        // class 0 (0x00, >= 0x80, bytes nothing moves on): empty row
-                const uint32_t c = trimmed.cls_rep[cl];
-                for (uint32_t w = 0; w < W; w++) B[(size_t)cl * WP + w] = nfa_wave.B[(size_t)c * W + w];
-            }
-            uint8_t cmap[256];
-            for (int c = 0; c < 256; c++) cmap[c] = (c == 0 || c >= 128) ? 0 : trimmed.cls[c];
-            // slots (word index within a lane) that carry masks at all: a slot whose B rows are all ones on every POSITION IN USE for
-            // every class >= 1 needs no AND (positions beyond nbits are never set: their row bits do not matter)
-            uint32_t self_slots = 0, b_slots = 0, exc_slots = 0;
-            for (uint32_t w = 0; w < WP; w++) {
-                const uint32_t used = w * 32 >= N ? 0u : (N - w * 32 >= 32 ? 0xffffffffu : (1u << (N - w * 32)) - 1u);
-                if (w < W && nfa_wave.self[w]) self_slots |= 1u << (w % K);
-                if (w < W && nfa_wave.excm[w]) exc_slots |= 1u << (w % K);
-                for (uint32_t cl = 1; cl < NC; cl++)
-                    if ((B[(size_t)cl * WP + w] & used) != used) b_slots |= 1u << (w % K);
-            }
-            std::vector<uint16_t> xidx(N, 0xffff);
-            std::vector<uint32_t> X;
-            uint32_t rows = 0;
-            for (uint32_t b = 0; b < N; b++) {
-                if (!((nfa_wave.excm[b >> 5] >> (b & 31)) & 1u)) continue;
-                xidx[b] = (uint16_t)rows++;
-                X.resize((size_t)rows * WP, 0);
-                for (uint32_t i = nfa_wave.xoff[b]; i < nfa_wave.xoff[b + 1]; i++) {      // (the CSR lists exist at every size, dense rows only up to 4096 positions)
-                    const uint32_t tv = nfa_wave.xtgt[i];
-                    X[(size_t)(rows - 1) * WP + (tv >> 5)] |= 1u << (tv & 31);
-                }
-            }
-            if (X.empty()) X.assign(WP, 0);
-            oM = put(M.data(), M.size() * 4);
-            oB = put(B.data(), B.size() * 4);
-            oX = put(X.data(), X.size() * 4);
-            oXI = put(xidx.data(), xidx.size() * 2);
-            oCP = put(cmap, 256);
-            t.group.G = G; t.group.K = K; t.group.nbits = N; t.group.n_exc = rows; t.group.ncls = NC;
-            t.group.self_slots = self_slots; t.group.b_slots = b_slots; t.group.exc_slots = exc_slots;
-            t.group.exc_mode = (rows == 1 && xidx[0] == 0) ? 2 : 0;
-        } else if (engine == RRX_ENGINE_NFA) {
-            const uint32_t W = nfa.W, WP = (uint32_t)instantiated_width(W);
-            std::vector<uint32_t> B((size_t)256 * WP, 0), X((size_t)nfa.nbits * WP, 0);
-            for (uint32_t c = 0; c < 256; c++) for (uint32_t w = 0; w < W; w++) B[(size_t)c * WP + w] = nfa.B[(size_t)c * W + w];
-            for (uint32_t b = 0; b < nfa.nbits; b++) for (uint32_t w = 0; w < W; w++) X[(size_t)b * WP + w] = nfa.X[(size_t)b * W + w];
-            oB = put(B.data(), B.size() * 4);
-            oX = put(X.data(), X.size() * 4);
-            t.nfa.W = WP; t.nfa.nbits = nfa.nbits; t.nfa.any_exc = nfa.n_exc ? 1 : 0; t.nfa.any_carry = nfa.n_carry ? 1 : 0;
-            for (uint32_t w = 0; w < W; w++) if (nfa.self[w]) t.nfa.any_self = 1;
-            std::memset(&t.nfa.masks, 0, sizeof t.nfa.masks);
-            for (uint32_t w = 0; w < W; w++) {
-                t.nfa.masks.init[w] = nfa.init[w]; t.nfa.masks.fin[w] = nfa.fin[w]; t.nfa.masks.chain[w] = nfa.chain[w];
-                t.nfa.masks.self[w] = nfa.self[w]; t.nfa.masks.excm[w] = nfa.excm[w];
-                t.nfa.masks.cgrp[w] = nfa.cgrp[w]; t.nfa.masks.ctgt[w] = nfa.ctgt[w];
-            }
-        } else {
-            oC = put(dfa.cls, 256);
-            oN = put(dfa.next.data(), dfa.next.size() * 2);
-            oA = put(dfa.accepting.data(), dfa.accepting.size());
-            t.dfa.nstates = dfa.nstates; t.dfa.ncls = dfa.ncls; t.dfa.start = dfa.start;
-            // line-mode table: entry = next row byte offset (16 bits) | nl << 16 | accept << 24; the '\n' column of
-            // every row goes to the start row and carries the verdict of the line that just ended.
-            const uint32_t D = dfa.nstates, K = dfa.ncls;
-            const bool wide = line_wide;
-            uint32_t stride = wide ? dev::kWideColumns : (K + 1);
-            if (!wide && !(stride & 1)) stride++;                       // odd row stride spreads rows over LDS banks
-            // Wide form: R = 2^rep interleaved copies (copy k of logical dword i at dword i*R + k), lane l reads copy
-            // l % R: its reads only touch LDS banks = l (mod R), so a half-wave splits into R groups that cannot
-            // conflict with each other.  Row byte offsets must stay 16-bit: D * stride * 4 * R <= 65536.
-            uint32_t rep = 0;
-            if (wide && !line_global) while (rep < 5 && (size_t)D * stride * 4 * (2u << rep) <= 65536) rep++;
-            const uint32_t R = 1u << rep;
-            std::vector<uint32_t> T((size_t)D * stride, 0);
-            uint8_t lcls[256];
-            for (int c = 0; c < 256; c++) lcls[c] = dfa.cls[c];
-            lcls['\n'] = (uint8_t)K;                                     // own column for the line terminator
-            const uint32_t row_bytes = line_global ? stride : stride * 4;   // global form: entry indices, not byte offsets
-            const int nl_bit = line_global ? 30 : 16, acc_bit = line_global ? 31 : 24;
-            for (uint32_t d = 0; d < D; d++) {
-                uint32_t *row = &T[(size_t)d * stride];
-                const uint32_t nl_entry = dfa.start * row_bytes | 1u << nl_bit | (dfa.accepting[d] ? 1u << acc_bit : 0u);
-                if (wide) {
-                    for (uint32_t c = 0; c < 128; c++) row[c] = (uint32_t)dfa.next[(size_t)d * K + dfa.cls[c]] * row_bytes;
-                    row['\n'] = nl_entry;
-                    row[128] = 0;
-                } else {
-                    for (uint32_t k = 0; k < K; k++) row[k] = (uint32_t)dfa.next[(size_t)d * K + k] * row_bytes;
-                    row[K] = nl_entry;
-                }
-            }
-            if (R > 1) {                                                 // interleave the copies; offsets scale by R
-                std::vector<uint32_t> TR(T.size() * R);
-                for (size_t i = 0; i < T.size(); i++)
-                    for (uint32_t k = 0; k < R; k++) TR[i * R + k] = (T[i] & 0xffffu) * R + 4 * k + (T[i] & 0xffff0000u);
-                T.swap(TR);
-            }
-            oT = put(T.data(), T.size() * 4);
-            oL = put(lcls, 256);
-            if (has_dfa2) {
-                std::vector<uint32_t> T2;
-                std::vector<uint16_t> P;
-                build_dfa2_arrays(T2, P, t.dfa2);
-                oP2 = put(P.data(), P.size() * 2);
-                oT2 = put(T2.data(), T2.size() * 4);
-            }
-            t.line.nrows = D; t.line.stride = stride * R; t.line.start_off = dfa.start * row_bytes * R; t.line.wide = wide ? 1 : 0;
-            t.line.rep_log2 = rep;
-            t.line.in_global = line_global ? 1 : 0;
-        }
-        HIP_TRY(hipMalloc(&t.blob, host.size() + 16));
-        {
-            const hipError_t up = hipMemcpy(t.blob, host.data(), host.size(), hipMemcpyHostToDevice);
-            if (up != hipSuccess) { (void)hipFree(t.blob); return hip_fail(up, "device program upload"); }
-        }
-        const uint8_t *base = static_cast<const uint8_t *>(t.blob);
-        if (engine == RRX_ENGINE_NFA_BLOCK || engine == RRX_ENGINE_NFA_SPARSE) {
-            t.block.masks = reinterpret_cast<const uint32_t *>(base + oM);
-            t.block.Bbyte = reinterpret_cast<const uint32_t *>(base + oB);
-            if (engine == RRX_ENGINE_NFA_SPARSE) { t.block.Bcls = reinterpret_cast<const uint32_t *>(base + oCL); t.block.cls = base + oCP; }
-            t.block.xoff = reinterpret_cast<const uint32_t *>(base + oXO);
-            t.block.xtgt = reinterpret_cast<const uint32_t *>(base + oXT);
-        } else if (engine == RRX_ENGINE_NFA_WAVE) {
-            t.group.masks = reinterpret_cast<const uint32_t *>(base + oM);
-            t.group.Bcls = reinterpret_cast<const uint32_t *>(base + oB);
-            t.group.cls = base + oCP;
-            t.group.X = reinterpret_cast<const uint32_t *>(base + oX);
-            t.group.xidx = reinterpret_cast<const uint16_t *>(base + oXI);
-        } else if (engine == RRX_ENGINE_NFA) {
-            t.nfa.B = reinterpret_cast<const uint32_t *>(base + oB);
-            t.nfa.X = reinterpret_cast<const uint32_t *>(base + oX);
-        } else {
-            t.dfa.cls = base + oC;
-            t.dfa.next = reinterpret_cast<const uint16_t *>(base + oN);
-            t.dfa.acc = base + oA;
-            t.line.table = reinterpret_cast<const uint32_t *>(base + oT);
-            t.line.cls = base + oL;
-            if (has_dfa2) {
-                t.dfa2.P = reinterpret_cast<const uint16_t *>(base + oP2);
-                t.dfa2.T2 = reinterpret_cast<const uint32_t *>(base + oT2);
-            }
-        }
-        auto ins = on_device.emplace(device, t);
-        *out = &ins.first->second;
-        return RRX_OK;
+            return true;
+        }, out);
     }
 };
 
@@ -947,11 +614,11 @@ int rrx_sampled_escapes(const rrx_regex *re, int device, uint64_t *lines) {
     if (!re || !lines) return fail(RRX_ERR_ARG, "null argument");
     *lines = 0;
     std::lock_guard<std::mutex> lock(re->onepass_mu);
-    auto it = re->sampled_counter.find(device);
-    if (it == re->sampled_counter.end() || !it->second) return RRX_OK;            // no sampled-table launch on this device yet
+    auto it = re->sampled_escapes.find(device);
+    if (it == re->sampled_escapes.end() || !it->second.p) return RRX_OK;          // no sampled-table launch on this device yet
     HIP_TRY(hipSetDevice(device));
     unsigned long long v = 0;
-    HIP_TRY(hipMemcpy(&v, it->second, sizeof v, hipMemcpyDeviceToHost));            // (synchronous: behind everything queued on the device)
+    HIP_TRY(hipMemcpy(&v, it->second.p, sizeof v, hipMemcpyDeviceToHost));          // (synchronous: behind everything queued on the device)
     *lines = v;
     return RRX_OK;
 }
@@ -1150,8 +817,9 @@ void rrx_corpus_free(rrx_corpus *c) {
 size_t rrx_corpus_bitmap_words(const rrx_corpus *c) { return (c->nlines + 31) / 32; }
 
 // The batch entry on the sampled table: the stride-2 kernel with two result bits per line (accepted, escaped), the two bitmaps
-// taken apart, the escaped lines decided by the NFA lane engine.  Scratch (the wide bitmap, the escaped bitmap, a counter) is
-// the regex' event-ordered per-device buffer; everything is queued on `stream`, nothing is read back.
+// taken apart, the escaped lines decided by the NFA lane engine.  Scratch (the wide bitmap, the escaped bitmap, the list) is the
+// regex' event-ordered per-device buffer, the count of escaped lines its own 16 bytes per device (sampled_escapes: read by
+// rrx_sampled_escapes); everything is queued on `stream`, nothing is read back.
 static int match_corpus_sampled(const rrx_regex *re, const rrx_corpus *c, const DeviceTables *t, uint32_t *d_accept_bits, void *stream) {
     dev::Dfa2Device d2;
     int rc = re->sampled_tables(c->device, &d2);
@@ -1162,13 +830,14 @@ static int match_corpus_sampled(const rrx_regex *re, const rrx_corpus *c, const 
     const size_t cap = std::max<size_t>(words / 2, 1024);                        // listed escaped lines: 1.5 % of the lines (then: the walk over the stripes)
     std::lock_guard<std::mutex> lock(re->onepass_mu);
     void *buf = nullptr;
-    rc = re->onepass_for(c->device, wide_bytes + esc_bytes + 16 + cap * sizeof(uint64_t), &buf, st);
+    rc = re->onepass_for(c->device, wide_bytes + esc_bytes + cap * sizeof(uint64_t), &buf, st);
     if (rc) return rc;
     uint32_t *wide = static_cast<uint32_t *>(buf);
     uint32_t *escaped = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(buf) + wide_bytes);
-    unsigned long long *total = reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(buf) + wide_bytes + esc_bytes);
-    uint64_t *list = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(buf) + wide_bytes + esc_bytes + 16);
-    re->sampled_counter[c->device] = total;
+    uint64_t *list = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(buf) + wide_bytes + esc_bytes);
+    DeviceAlloc &count = re->sampled_escapes[c->device];
+    if (!count.p) HIP_TRY(count.alloc(c->device, 16));
+    unsigned long long *total = static_cast<unsigned long long *>(count.p);
     constexpr uint32_t kSlots = rrx_regex::kSampledRelearns + 1;
     if (!re->h_sampled_seen && hipHostMalloc(reinterpret_cast<void **>(&re->h_sampled_seen), kSlots * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess)
         for (uint32_t k = 0; k < kSlots; k++) re->h_sampled_seen[k] = 0;

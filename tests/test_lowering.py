@@ -344,9 +344,10 @@ def random_pattern_text(rng, p):
 
 
 def test_host_pipeline_is_clean_under_asan_and_ubsan(tmp_path):
-    """Sanitizers run on the CPU build only: the host compile pipeline (front end + every lowering) is plain C++, so
-    it is built here with g++ -fsanitize=address,undefined and driven with the known answers, the big configs, broken
-    patterns and random patterns.  Any report aborts the driver (-fno-sanitize-recover)."""
+    """Sanitizers run on the CPU build only: the host compile pipeline (front end + every lowering + the packing of every
+    device image) is plain C++, so it is built here with g++ -fsanitize=address,undefined and driven with the known answers,
+    the big configs, broken patterns and random patterns.  Any report aborts the driver (-fno-sanitize-recover), and so does
+    a packed image that does not decode back to its program."""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -354,7 +355,7 @@ def test_host_pipeline_is_clean_under_asan_and_ubsan(tmp_path):
     exe = str(tmp_path / "host_pipeline_asan")
     subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc,
                            os.path.join(root, "tests", "cpp", "host_pipeline_driver.cpp"), os.path.join(csrc, "frontend.cpp"),
-                           os.path.join(csrc, "lower.cpp"), "-o", exe])
+                           os.path.join(csrc, "lower.cpp"), os.path.join(csrc, "pack.cpp"), "-o", exe])
     rng = random.Random(2024)
     pats = [k["pattern"] for k in KAT["kat"]] + [b["pattern"] for b in KAT["big_states"]]
     pats += [EMAIL, U2, "a{1,300}", "(a|b)*a(a|b){12}", "(a|b)*a(a|b){40}", K1000_CONTAINS]
@@ -365,6 +366,9 @@ def test_host_pipeline_is_clean_under_asan_and_ubsan(tmp_path):
     assert out.returncode == 0, out.stderr.decode("latin-1")[-3000:]
     lines = out.stdout.decode("latin-1").splitlines()
     assert lines[-1].startswith("done %d " % len(pats)), lines[-1]
+    # every device image form was packed, bound to a host copy and decoded back against its program at least once
+    packed = lines[-2].split()
+    assert packed[0] == "packed" and all(int(v) >= 1 for v in packed[2::2]), lines[-2]
     # the sanitized build must agree with the shipped library on what compiles
     for p, line in zip(pats, lines):
         try:
