@@ -127,6 +127,11 @@ public:
         auto *f = static_cast<DeviceIterFactory *>(iter_factory.get());
         if (rrx_match_corpus(f->handle(), corpus, d_accept_bits, stream) != RRX_OK) throw std::runtime_error(rrx_last_error());
     }
+    // which strings CONTAIN a match (rrx_contains_corpus): the same bitmap layout, bytes >= 0x80 and NUL are ordinary text
+    void contains_corpus(const rrx_corpus *corpus, uint32_t *d_bits, void *stream = nullptr) {
+        auto *f = static_cast<DeviceIterFactory *>(iter_factory.get());
+        if (rrx_contains_corpus(f->handle(), corpus, d_bits, stream) != RRX_OK) throw std::runtime_error(rrx_last_error());
+    }
     // the same for a device buffer that has no rrx_corpus yet: ONE pass over the text (no index pass); returns the number
     // of strings; d_accept_bits holds cap_words words.  Synchronous.
     size_t match_device(const void *d_bytes, size_t nbytes, uint32_t *d_accept_bits, size_t cap_words, void *stream = nullptr) {

@@ -137,6 +137,8 @@ int         rrx_accepts_empty(const rrx_regex *re); /* Processor::operator*() on
                                     [nstates, ncols, start, accepts_empty, 129, column of the code pair[129][129], next2[nstates][ncols]] - codes
                                     0 ... 127 the byte values ('\n' an ordinary byte), 128 END OF ITEM; entries as in the DFA2 layout.  0 words
                                     where the regex has no stride-2 table or this form does not fit beside the pair table              */
+#define RRX_PROGRAM_CONTAINS_DFA 16  /* the contains table (rrx_contains_corpus), DFA layout: state 0 = SKIP, class 0 a live column   */
+#define RRX_PROGRAM_CONTAINS_DFA2 17 /* its stride-2 form, DFA2 layout; 0 words where it does not fit                                */
 size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t cap);
 
 /* ---- batch of strings: the replacement for calling get_acceptance_iter(line)++ per string ------------ *
@@ -177,6 +179,24 @@ int rrx_bitmap_to_bytes(int device, const uint32_t *d_accept_bits, size_t nlines
  * otherwise; RRX_ERR_UNSUPPORTED only when the REVERSE table does not fit 64 KiB of LDS, the forward table has more than 65534
  * rows, or its stride-2 form more than 256 MiB.  A pattern that accepts the empty string matches [0, 0) in every string.  */
 int rrx_search_corpus(const rrx_regex *re, const rrx_corpus *corpus, uint32_t *d_start, uint32_t *d_end, void *stream);
+/* WHICH strings contain a match (what grep answers; the reference has acceptance only).  Replaces rrx_search_corpus + a test of
+ * d_start[i] != 0xFFFFFFFF, which pays for match starts nobody asked for, and rrx_match_corpus on ".*(p).*", which rejects every
+ * string that holds a NUL or a byte >= 0x80.  Bit (i & 31) of d_bits[i >> 5] = 1 iff rrx_search_corpus would report a match for
+ * string i, i.e. iff some substring of it is accepted by the pattern as a whole string.  NUL and bytes >= 0x80 are ordinary text
+ * that no pattern takes; a pattern that accepts the empty string is contained in every string, the empty one included; an
+ * empty-language pattern in none.  d_bits holds rrx_corpus_bitmap_words() words, zeroed and filled on `stream`, asynchronously
+ * (an empty corpus writes nothing).  Runs the batch kernels of rrx_match_corpus on a table of its own, built at the first use:
+ * the forward search table with every accepting state folded into one absorbing state, minimised - never more states than
+ * RRX_PROGRAM_SEARCH_FWD has.  Forms and fit rules as the match path's (stride-2 table, wide / classed LDS table, table in
+ * HBM/L2; a regex compiled with RRX_ENGINE_DFA / RRX_ENGINE_DFA_GLOBAL stays on the byte-stride LDS / global table); text with
+ * bytes >= 0x80 keeps the stride-2 kernel.  RRX_ERR_UNSUPPORTED where the forward search automaton does not determinise within
+ * the state budget or the table passes 2^24 entries.                                                                        */
+int         rrx_contains_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_bits, void *stream);
+const char *rrx_contains_engine_name(const rrx_regex *re);   /* "dfa-stride2-table", ... as rrx_engine_name; NULL + rrx_last_error() if unsupported; host only */
+uint32_t    rrx_contains_states(const rrx_regex *re);        /* states of the contains table, SKIP included; 0 if unsupported; host only */
+/* *d_count (a device word, zeroed and filled on `stream`) = set bits among the first nlines bits of a result bitmap - bits of the
+ * last word beyond nlines are ignored, nlines 0 gives 0: `grep -c` on either bitmap without a host round trip.             */
+int         rrx_bitmap_count(int device, const uint32_t *d_bits, size_t nlines, uint64_t *d_count, void *stream);
 /* ALL lazy matches of every string, left to right (what the reference's CLI is documented to print, README.md:30): the
  * k-th match of a string is the search above applied to the rest of the string after the previous match (one byte
  * further after an empty match).  Two passes: _count writes d_count[i] = matches of string i; the caller turns the

@@ -23,6 +23,7 @@ PROGRAM_DFA2_ITEMS = 15
 PROGRAM_DFA2_ORDER = 11
 PROGRAM_SAMPLED_DFA = 12
 PROGRAM_SAMPLED_DFA2 = 13
+PROGRAM_CONTAINS_DFA, PROGRAM_CONTAINS_DFA2 = 16, 17   # the contains table (rrx_contains_corpus) and its stride-2 form
 OPT_BACKGROUND_ORDER = 1
 OPT_UNITS_PER_WORKGROUP = 2
 OPT_SAMPLED_TABLE = 3
@@ -40,6 +41,7 @@ ABI_SYMBOLS = (
     "rrx_match_corpus", "rrx_match_device", "rrx_search_corpus", "rrx_search_all_count", "rrx_search_all_fill", "rrx_search_all", "rrx_bitmap_to_bytes",
     "rrx_match_extents", "rrx_items_create", "rrx_items_count", "rrx_items_stripe_wise", "rrx_items_free", "rrx_match_items",
     "rrx_match_string", "rrx_match_host", "rrx_match_cstr",
+    "rrx_contains_corpus", "rrx_contains_engine_name", "rrx_contains_states", "rrx_bitmap_count",
 )
 
 
@@ -107,6 +109,10 @@ def _load():
         "rrx_search_all": (i32, [vp, vp, vp, vp, vp, sz, C.POINTER(sz), vp]),
         "rrx_match_host": (i32, [vp, i32, vp, sz, vp, sz, C.POINTER(sz)]),
         "rrx_match_cstr": (i32, [vp, i32, C.c_char_p, C.POINTER(i32), C.POINTER(sz)]),
+        "rrx_contains_corpus": (i32, [vp, vp, vp, vp]),
+        "rrx_contains_engine_name": (C.c_char_p, [vp]),
+        "rrx_contains_states": (u32, [vp]),
+        "rrx_bitmap_count": (i32, [i32, vp, sz, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -148,6 +154,18 @@ def _stream_ptr(stream):
         import torch
         stream = torch.cuda.current_stream()
     return C.c_void_p(stream.cuda_stream)
+
+
+def bitmap_count(bits, nlines, stream=None):
+    """Set bits among the first `nlines` bits of a result bitmap (a device tensor of 32-bit words, as match_corpus_bits and
+    contains_corpus_bits return it), counted on the device (rrx_bitmap_count) -> int.  Waits for the one word to come back."""
+    import torch
+    assert bits.is_cuda and bits.dtype in (torch.int32, torch.uint32) and bits.is_contiguous() and bits.numel() * 32 >= nlines
+    with _on(bits.device.index, stream):
+        count = torch.empty(1, dtype=torch.int64, device=bits.device)
+        _check(_L.rrx_bitmap_count(bits.device.index, C.c_void_p(bits.data_ptr() if nlines else 0), nlines, C.c_void_p(count.data_ptr()),
+                                   _stream_ptr(stream)))
+        return int(count.item())
 
 
 class Match:
@@ -322,6 +340,32 @@ class RRegex:
                                           C.c_void_p(out.data_ptr() if n else 0), _stream_ptr(stream)))
         return out[:n]
 
+    def contains_corpus_bits(self, corpus, out=None, stream=None):
+        """Which lines CONTAIN a match (rrx_contains_corpus): a bitmap of 32-bit words, an int32 tensor like match_corpus_bits',
+        bit (i & 31) of word i >> 5 = some substring of line i is accepted, i.e. search_corpus would report a match for it.  NUL
+        and bytes >= 0x80 are ordinary text here.  Asynchronous on `stream`."""
+        import torch
+        nw = _L.rrx_corpus_bitmap_words(corpus._h)
+        with _on(corpus.device, stream):
+            if out is None:
+                out = torch.empty(nw, dtype=torch.int32, device=corpus.data.device)
+            assert out.is_cuda and out.dtype == torch.int32 and out.numel() >= nw
+            _check(_L.rrx_contains_corpus(self._h, corpus._h, C.c_void_p(out.data_ptr() if nw else 0), _stream_ptr(stream)))
+        return out[:nw]
+
+    def contains_corpus(self, corpus, out=None, stream=None):
+        """contains[i] = 1 iff line i of the corpus contains a match (one byte per line: bitmap + expansion)."""
+        import torch
+        n = corpus.num_lines
+        with _on(corpus.device, stream):
+            bits = self.contains_corpus_bits(corpus, stream=stream)
+            if out is None:
+                out = torch.empty(n, dtype=torch.uint8, device=corpus.data.device)
+            assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
+            _check(_L.rrx_bitmap_to_bytes(corpus.device, C.c_void_p(bits.data_ptr() if n else 0), n,
+                                          C.c_void_p(out.data_ptr() if n else 0), _stream_ptr(stream)))
+        return out[:n]
+
     def search_corpus(self, corpus, stream=None):
         """Per string the accepted substring [start, end) with the smallest end, then the smallest start, as two int32
         tensors of offsets relative to the start of the string; (-1, -1) where nothing is accepted."""
@@ -448,6 +492,19 @@ class RRegex:
     @property
     def engine_name(self):
         return _L.rrx_engine_name(self._h).decode()
+
+    @property
+    def contains_engine_name(self):
+        """The table form contains_corpus runs on (host only); raises RRegexError where the pattern has no contains table."""
+        name = _L.rrx_contains_engine_name(self._h)
+        if name is None:
+            raise RRegexError(_L.rrx_last_error().decode("latin-1"))
+        return name.decode()
+
+    @property
+    def contains_states(self):
+        """States of the contains table, the SKIP row included; 0 where the pattern has none (host only)."""
+        return _L.rrx_contains_states(self._h)
 
     @property
     def useful_states(self):

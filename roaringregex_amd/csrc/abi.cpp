@@ -444,6 +444,53 @@ struct rrx_regex {
         return upload_once(search_on_device, device, false, pack, out);
     }
 
+    // "Contains a match" (rrx_contains_corpus): the forward search table with its accepting states folded into one absorbing
+    // state (lower.hpp: contains_dfa), in the forms of the match path and by its fit rules (rrx_compile_ex) - the stride-2 form,
+    // the wide / classed LDS line table, the global line table; a regex compiled with RRX_ENGINE_DFA / _DFA_GLOBAL keeps it on
+    // the byte-stride LDS / global table.  Host side (call with `mu` held).
+    mutable int contains_state = 0;      // 0 = not built, 1 = built, -1 = no table
+    mutable DfaProgram contains_dfa;
+    mutable Dfa2Program contains_dfa2;
+    mutable bool contains_has_dfa2 = false, contains_wide = false, contains_global = false;
+    mutable std::map<int, OnDevice<DeviceTables>> contains_on_device;
+    int build_contains() const {
+        if (contains_state == 0) {
+            (void)build_search();                        // (what the search entries cannot use does not matter here: the forward table does)
+            bool ok = search_fwd.nstates != 0 && rrx::contains_dfa(search_fwd, contains_dfa);
+            if (ok) {
+                const DfaProgram &d = contains_dfa;
+                contains_wide = d.nstates <= dev::kWideMaxStates && requested_engine != RRX_ENGINE_DFA_GLOBAL;
+                const size_t classed_entries = (size_t)d.nstates * (d.ncls + 2);
+                contains_global = requested_engine == RRX_ENGINE_DFA_GLOBAL || (!contains_wide && classed_entries > dev::kClassedMaxEntries);
+                if (contains_global && classed_entries >= ((size_t)1 << 24)) ok = false;
+                if (ok && !contains_global && requested_engine != RRX_ENGINE_DFA && d.nstates <= 4096)
+                    contains_has_dfa2 = lower_dfa2(d, 1024, contains_dfa2) &&
+                                        (size_t)contains_dfa2.nstates * (contains_dfa2.ncols | 1u) * 4 <= dev::kDfa2MaxTable;
+            }
+            contains_state = ok ? 1 : -1;
+        }
+        return contains_state == 1 ? RRX_OK
+                                   : fail(RRX_ERR_UNSUPPORTED, search_fwd.nstates ? "contains table too large for the device (the global form holds 2^24 entries)"
+                                                                                  : "no contains table: the forward search automaton does not determinise within the state budget");
+    }
+    const char *contains_name_locked() const {
+        return contains_has_dfa2 ? "dfa-stride2-table" : contains_global ? "dfa-global-table" : contains_wide ? "dfa-wide-table" : "dfa-classed-table";
+    }
+    // The contains tables on `device` (uploaded once); the descriptors are copied out under the lock, the launch runs without it.
+    int contains_tables(int device, bool *stride2, dev::Dfa2Device *d2, dev::LineDfaDevice *line) const {
+        std::lock_guard<std::mutex> lock(mu);
+        int rc = build_contains();
+        if (rc) return rc;
+        const DeviceTables *t = nullptr;
+        rc = upload_once(contains_on_device, device, false, [&](Image &img, DeviceTables &dt) {
+            pack_dfa_tables(contains_dfa, contains_wide, contains_global, contains_has_dfa2 ? &contains_dfa2 : nullptr, {}, {}, img, dt);
+            return true;
+        }, &t);
+        if (rc) return rc;
+        *stride2 = contains_has_dfa2; *d2 = t->dfa2; *line = t->line;
+        return RRX_OK;
+    }
+
     // Upload the program for `device` once; returns the device-side descriptors.
     int tables(int device, const DeviceTables **out) const {
         std::lock_guard<std::mutex> lock(mu);
@@ -676,6 +723,21 @@ size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t ca
         for (uint16_t c : d.pair_col) w.push_back(c);
         w.insert(w.end(), d.first.begin(), d.first.end());
         w.insert(w.end(), d.all.begin(), d.all.end());
+    } else if (kind == RRX_PROGRAM_CONTAINS_DFA || kind == RRX_PROGRAM_CONTAINS_DFA2) {
+        std::lock_guard<std::mutex> lock(re->mu);
+        if (re->build_contains()) return 0;
+        if (kind == RRX_PROGRAM_CONTAINS_DFA) {
+            const DfaProgram &d = re->contains_dfa;
+            w = {d.nstates, d.ncls, d.start, d.accepts_empty ? 1u : 0u};
+            for (int c = 0; c < 256; c++) w.push_back(d.cls[c]);
+            for (uint8_t a : d.accepting) w.push_back(a);
+            for (uint16_t n : d.next) w.push_back(n);
+        } else if (re->contains_has_dfa2) {
+            const Dfa2Program &d = re->contains_dfa2;
+            w = {d.nstates, d.ncols, d.start, d.accepts_empty ? 1u : 0u};
+            for (uint16_t c : d.pair_col) w.push_back(c);
+            w.insert(w.end(), d.next2.begin(), d.next2.end());
+        }
     } else if (kind == RRX_PROGRAM_DFA2_ORDER && re->has_dfa2) {
         std::lock_guard<std::mutex> lock(re->mu);
         if (re->t2_row_slot.size() != re->dfa2.nstates || re->t2_col_slot.size() != re->dfa2.ncols) return 0;
@@ -899,6 +961,45 @@ int rrx_match_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_accep
                                                  re->opt_flush_slots.load() ? (uint32_t)re->opt_flush_slots.load() - 1u : dev::flush_mask_for(c->nbytes, c->nlines)))
                 : dev::match_stripes_dfa(t->line, c->has_high, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, stream);
     if (e) return hip_fail((hipError_t)e, "match_stripes launch");
+    return RRX_OK;
+}
+
+// "Which lines contain a match": the batch kernels of rrx_match_corpus on the contains table (build_contains).  On a corpus with
+// bytes >= 0x80 the stride-2 table keeps its kernel - the instantiation that steps such bytes as 0x00, which is their class.
+int rrx_contains_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_bits, void *stream) {
+    if (!re || !c || (c->nlines && !d_bits)) return fail(RRX_ERR_ARG, "null argument");
+    bool stride2 = false;
+    dev::Dfa2Device d2;
+    dev::LineDfaDevice line;
+    int rc = re->contains_tables(c->device, &stride2, &d2, &line);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->nlines) return RRX_OK;
+    // the kernels merge words with atomic OR: start from an all-zero bitmap
+    HIP_TRY(hipMemsetAsync(d_bits, 0, rrx_corpus_bitmap_words(c) * sizeof(uint32_t), (hipStream_t)stream));
+    const uint32_t flush_mask = re->opt_flush_slots.load() ? (uint32_t)re->opt_flush_slots.load() - 1u : dev::flush_mask_for(c->nbytes, c->nlines);
+    const int e = !stride2     ? dev::match_stripes_dfa(line, c->has_high, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_bits, stream)
+                  : c->has_high ? dev::match_stripes_dfa2_clean(d2, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_bits, stream, flush_mask)
+                                : dev::match_stripes_dfa2(d2, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_bits, stream, flush_mask);
+    if (e) return hip_fail((hipError_t)e, "contains launch");
+    return RRX_OK;
+}
+const char *rrx_contains_engine_name(const rrx_regex *re) {
+    if (!re) { (void)fail(RRX_ERR_ARG, "null argument"); return nullptr; }
+    std::lock_guard<std::mutex> lock(re->mu);
+    return re->build_contains() ? nullptr : re->contains_name_locked();
+}
+uint32_t rrx_contains_states(const rrx_regex *re) {
+    if (!re) { (void)fail(RRX_ERR_ARG, "null argument"); return 0; }
+    std::lock_guard<std::mutex> lock(re->mu);
+    return re->build_contains() ? 0 : re->contains_dfa.nstates;
+}
+int rrx_bitmap_count(int device, const uint32_t *d_bits, size_t nlines, uint64_t *d_count, void *stream) {
+    if (!d_count || (nlines && !d_bits)) return fail(RRX_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(device));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit atomics");
+    int e = dev::bitmap_count(d_bits, nlines, reinterpret_cast<unsigned long long *>(d_count), stream);
+    if (e) return hip_fail((hipError_t)e, "bitmap_count launch");
     return RRX_OK;
 }
 

@@ -164,6 +164,11 @@ int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_
 uint32_t flush_mask_for(size_t nbytes, size_t nlines);      // the stride-2 kernel's common flush period from the mean line length
 int match_stripes_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
                        size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask = 31u);
+// the same over text that may hold bytes >= 0x80: they are stepped as 0x00 (rrx_contains_corpus, where both are ordinary text of one class)
+int match_stripes_dfa2_clean(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                             size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask = 31u);
+// *count (zeroed here, on `stream`) = set bits among the first `nlines` bits of a result bitmap
+int bitmap_count(const uint32_t *bits, size_t nlines, unsigned long long *count, void *stream);
 // The sampled-table engine: the stride-2 kernel on a table with an ESCAPE state writes two bits per line into
 // `wide_bits` (2 x the accept bitmap, zeroed by the caller); split_two_bit takes them apart (every word of both outputs is
 // written) and counts the escaped lines; recheck_escaped_nfa lets the exact NFA lane engine decide those and ORs its accepts in.

@@ -305,7 +305,9 @@ __device__ __forceinline__ void feed_load(uint4 (&buf)[kRound / 16], const uint4
 // One stripe of one lane: lane-local state only (what the caller keeps across stripes is the engine, the window and `g`).
 // KB: result bits per line - 1 (accepted), or 2 (accepted, ESCAPED: the sampled-table engine, whose table does not know every
 // transition; the table's line ends then shift two bits in, and everything that counts results counts bits).
-template <bool ONEPASS, class PhaseHook, bool FEED_ASM = false, int KB = 1>
+// CLEAN: the text may hold bytes >= 0x80 (the one-pass entry, which has no index that could tell; rrx_contains_corpus on a corpus
+// that holds some).  They are stepped as 0x00 - the same byte class on every table - under the wave-uniform test below.
+template <bool ONEPASS, class PhaseHook, bool FEED_ASM = false, int KB = 1, bool CLEAN = ONEPASS>
 __device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, const uint64_t window_word, uint32_t *const stage, const uint32_t stage_words,
                                             const uint8_t *__restrict__ bytes, const size_t nbytes, const uint32_t stripe,
                                             const uint64_t *__restrict__ stripe_base, uint32_t *__restrict__ accept_bits,
@@ -327,8 +329,8 @@ __device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, con
         res.drop_mask = (1u << KB) - 1u;
     }
     Dfa2::State st = fresh ? eng.fresh() : eng.skipping();
-    auto clean = [](uint32_t w) -> uint32_t {                       // ONEPASS: bytes >= 0x80 -> 0x00
-        if (ONEPASS && __builtin_amdgcn_ballot_w64((w & 0x80808080u) != 0)) {
+    auto clean = [](uint32_t w) -> uint32_t {                       // CLEAN: bytes >= 0x80 -> 0x00
+        if (CLEAN && __builtin_amdgcn_ballot_w64((w & 0x80808080u) != 0)) {
             const uint32_t hi = (w & 0x80808080u) >> 7;             // 1 in every byte to clear
             w &= ~(hi * 0xffu);
         }
@@ -352,7 +354,7 @@ __device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, con
         phase.round(r);
 #pragma unroll
         for (int i = 0; i < kSlots; i++) {
-            if (ONEPASS && __builtin_expect(__builtin_amdgcn_ballot_w64(((buf[i].x | buf[i].y | buf[i].z | buf[i].w) & 0x80808080u) != 0) != 0, 0)) {
+            if (CLEAN && __builtin_expect(__builtin_amdgcn_ballot_w64(((buf[i].x | buf[i].y | buf[i].z | buf[i].w) & 0x80808080u) != 0) != 0, 0)) {
                 // some lane of the wave holds a byte >= 0x80 in this slot (one test per 16 bytes; rare on text)
                 eng.consume_dword(st, clean(buf[i].x), res.bits);
                 eng.consume_dword(st, clean(buf[i].y), res.bits);
@@ -384,7 +386,7 @@ __device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, con
     }
     pos += (size_t)rounds * kRound;
     phase(kPhaseMainDone);
-    auto byte_at = [&](size_t q) -> uint32_t { const uint32_t b = bytes[q]; return (ONEPASS && b >= 0x80u) ? 0u : b; };
+    auto byte_at = [&](size_t q) -> uint32_t { const uint32_t b = bytes[q]; return (CLEAN && b >= 0x80u) ? 0u : b; };
 
     // ---- tail of the corpus inside my stripe (only the last stripe has one): whole pairs, then an odd last byte.
     // The odd byte is paired with a virtual '\n': if it is a '\n' itself the pair reports two line ends, of which
@@ -448,7 +450,7 @@ __device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, con
     }
 }
 
-template <bool ONEPASS, class PhaseHook = NoPhaseHook, int KB = 1>
+template <bool ONEPASS, class PhaseHook = NoPhaseHook, int KB = 1, bool CLEAN = ONEPASS>
 __device__ __forceinline__ void dfa2_body(const Dfa2Device &prog, const uint8_t *__restrict__ bytes, size_t nbytes, uint32_t stripe,
                                           const uint64_t *__restrict__ stripe_base, uint32_t *__restrict__ accept_bits,
                                           uint32_t *__restrict__ counts, uint32_t *__restrict__ slabs, PhaseHook phase = PhaseHook(),
@@ -473,7 +475,7 @@ __device__ __forceinline__ void dfa2_body(const Dfa2Device &prog, const uint8_t 
     const size_t g0 = (size_t)blockIdx.x * kThreads;
     uint64_t window_word = 0;
     if (!ONEPASS) window_word = (line_of(stripe_base[g0]) * KB) >> 5;       // the workgroup's first stripe exists: uniform load
-    dfa2_stripe<ONEPASS, PhaseHook, false, KB>(eng, g0 + threadIdx.x, window_word, stage, stage_words, bytes, nbytes, stripe, stripe_base, accept_bits, counts, slabs,
+    dfa2_stripe<ONEPASS, PhaseHook, false, KB, CLEAN>(eng, g0 + threadIdx.x, window_word, stage, stage_words, bytes, nbytes, stripe, stripe_base, accept_bits, counts, slabs,
                          gridDim.x * kThreads, phase, flush_mask);
     if (!ONEPASS) {
         // ---- write the window out: consecutive lanes, consecutive words (the atomics merge into whole lines in L2;
@@ -549,6 +551,13 @@ __global__ __launch_bounds__(kThreads) void match_stripes2_kernel(Dfa2Device pro
                                                                    uint32_t stripe, const uint64_t *__restrict__ stripe_base,
                                                                    uint32_t *__restrict__ accept_bits, uint32_t flush_mask) {
     dfa2_body<false>(prog, bytes, nbytes, stripe, stripe_base, accept_bits, nullptr, nullptr, NoPhaseHook(), flush_mask);
+}
+// the same over text that may hold bytes >= 0x80, stepped as 0x00 (rrx_contains_corpus: such bytes are ordinary text there, of the
+// class of NUL, and UTF-8 text stays on the two-bytes-per-lookup kernel)
+__global__ __launch_bounds__(kThreads) void match_stripes2_clean_kernel(
+    Dfa2Device prog, const uint8_t *__restrict__ bytes, size_t nbytes, uint32_t stripe, const uint64_t *__restrict__ stripe_base,
+    uint32_t *__restrict__ accept_bits, uint32_t flush_mask) {
+    dfa2_body<false, NoPhaseHook, 1, true>(prog, bytes, nbytes, stripe, stripe_base, accept_bits, nullptr, nullptr, NoPhaseHook(), flush_mask);
 }
 // two result bits per line (accepted, escaped) into a bitmap of twice the size: the sampled-table engine's first pass
 __global__ __launch_bounds__(kThreads) void match_stripes2_two_bit_kernel(Dfa2Device prog, const uint8_t *__restrict__ bytes, size_t nbytes,
@@ -1436,6 +1445,36 @@ int match_stripes_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes,
     if (Dfa2::lds_bytes(p) > kDfa2MaxTable) return (int)hipErrorInvalidValue;
     size_t blocks = (nstripes + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(match_stripes2_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, p, bytes, nbytes, stripe, stripe_base, accept, flush_mask);
+    return (int)hipGetLastError();
+}
+int match_stripes_dfa2_clean(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                             size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask) {
+    if (!nstripes) return 0;
+    if (Dfa2::lds_bytes(p) > kDfa2MaxTable) return (int)hipErrorInvalidValue;
+    size_t blocks = (nstripes + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(match_stripes2_clean_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, p, bytes, nbytes, stripe, stripe_base, accept, flush_mask);
+    return (int)hipGetLastError();
+}
+// popcount of the first `nlines` bits of a result bitmap (bits of the last word beyond them ignored), added to *count, which the
+// caller has zeroed on the same stream: a sum per lane, per wave (DPP/shuffle reduction), one atomic per wave
+__global__ __launch_bounds__(256) void bitmap_count_kernel(const uint32_t *__restrict__ bits, size_t nlines, unsigned long long *__restrict__ count) {
+    const size_t words = (nlines + 31) / 32;
+    const uint32_t tail = (uint32_t)(nlines & 31u);
+    unsigned long long n = 0;
+    for (size_t w = (size_t)blockIdx.x * 256 + threadIdx.x; w < words; w += (size_t)gridDim.x * 256) {
+        uint32_t v = bits[w];
+        if (w + 1 == words && tail) v &= (1u << tail) - 1u;
+        n += (uint32_t)__popc(v);
+    }
+    for (int d = 32; d > 0; d >>= 1) n += __shfl_down(n, d, 64);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(count, n);
+}
+int bitmap_count(const uint32_t *bits, size_t nlines, unsigned long long *count, void *stream) {
+    hipError_t e = hipMemsetAsync(count, 0, sizeof *count, (hipStream_t)stream);
+    if (e != hipSuccess || !nlines) return (int)e;
+    size_t blocks = ((nlines + 31) / 32 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(bitmap_count_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bits, nlines, count);
     return (int)hipGetLastError();
 }
 // ---- the sampled-table engine's second step: the two-bit bitmap (bit 2i = line i accepted, bit 2i + 1 = line i ended in the

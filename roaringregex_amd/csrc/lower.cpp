@@ -1124,6 +1124,30 @@ bool search_dfas(const Reduced &r, uint32_t max_states, DfaProgram &fwd, DfaProg
     return subset_construct(r, max_states, true, fwd) && subset_construct(reversed(r), max_states, false, rev);
 }
 
+// "Does the line contain a match": the forward search table with every accepting state folded into one absorbing accepting
+// state FOUND (the line's verdict is in, it waits for the '\n'), minimised again.  Row 0 of the forward table - the empty set,
+// which the sticky construction never reaches - is already absorbing and rejecting: it stays row 0 as the SKIP row of the batch
+// kernels (a lane whose stripe begins inside somebody else's line waits in it).  Class 0 is an ordinary column here.
+bool contains_dfa(const DfaProgram &fwd, DfaProgram &out) {
+    out = DfaProgram();
+    std::memcpy(out.cls, fwd.cls, sizeof out.cls);
+    out.ncls = fwd.ncls;
+    const uint32_t K = fwd.ncls, D = fwd.nstates;
+    if (D < 2) {                                        // the empty language: SKIP is all there is, and the start
+        out.nstates = 1; out.start = 0; out.accepting = {0}; out.next.assign(K, 0);
+        return true;
+    }
+    // minimise_into wants the dead state as 0 and the start as 1: the forward table has them there
+    if (fwd.start != 1 || fwd.accepting[0]) return false;
+    std::vector<uint32_t> nxt((size_t)D * K);
+    std::vector<uint8_t> kind(D);
+    for (uint32_t s = 0; s < D; s++) {
+        kind[s] = fwd.accepting[s] ? 1 : 0;
+        for (uint32_t k = 0; k < K; k++) nxt[(size_t)s * K + k] = fwd.accepting[s] ? s : fwd.next[(size_t)s * K + k];
+    }
+    return minimise_into(nxt, kind, K, out);
+}
+
 // Line-mode search table: the product of the sticky forward table (where does the first match END) and the anchored table
 // of the pattern itself (is the line's prefix up to here accepted: then the match STARTS at the line start and no walk back
 // is needed).  Rows = reachable pairs + SKIP (last), columns = byte classes + '\n' (last).

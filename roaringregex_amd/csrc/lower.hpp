@@ -166,6 +166,11 @@ bool lower_dfa_sampled(const Reduced &r, const uint8_t *sample, uint32_t pieces,
 // byte kills it, it is accepting exactly at the positions where some match ends.  rev: the DFA of the pattern read
 // right to left - walked backwards from a match end it is accepting exactly at the positions where a match starts.
 bool search_dfas(const Reduced &r, uint32_t max_states, DfaProgram &fwd, DfaProgram &rev);
+// "Contains a match" (rrx_contains_corpus): `fwd` with its accepting states folded into one absorbing accepting state, minimised;
+// state 0 = the SKIP row (absorbing, rejecting, reached from nowhere), never more states than `fwd` has.  Class 0 (NUL, bytes
+// >= 0x80, bytes the pattern does not mention) is a live column: it leads where `fwd` says.  Steps like any DfaProgram in line
+// mode: start state at a line start, verdict of the state at the line end.
+bool contains_dfa(const DfaProgram &fwd, DfaProgram &out);
 
 // Line-mode search table (stripe-wise search kernel): rows = reachable pairs (anchored state, sticky forward state) + the
 // SKIP row, columns = byte classes + '\n'.  Entry = next row | flags: kSearchNewline (the byte was '\n': next row = start),

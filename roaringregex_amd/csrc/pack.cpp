@@ -43,7 +43,8 @@ void pack_dfa_tables(const DfaProgram &dfa, bool wide, bool global, const Dfa2Pr
         if (wide) {
             for (uint32_t c = 0; c < 128; c++) row[c] = (uint32_t)dfa.next[(size_t)d * K + dfa.cls[c]] * row_bytes;
             row['\n'] = nl_entry;
-            row[128] = 0;
+            row[128] = (uint32_t)dfa.next[(size_t)d * K + dfa.cls[128]] * row_bytes;    // any byte >= 0x80: class 0 - the dead row 0 on
+                                                                                         //   a match table, a live row on a contains table
         } else {
             for (uint32_t k = 0; k < K; k++) row[k] = (uint32_t)dfa.next[(size_t)d * K + k] * row_bytes;
             row[K] = nl_entry;
