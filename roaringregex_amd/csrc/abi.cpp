@@ -1,4 +1,5 @@
-// abi.cpp — the C ABI of librrx.so (include/rrx.h): host compile pipeline + device program upload + launches.
+// abi.cpp — the C ABI of librrx.so (include/rrx.h): handles and locks, device program upload, launches.  What a pattern compiles
+// to and which table forms it gets is decided in plan.cpp.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -16,6 +17,7 @@
 #include "frontend.hpp"
 #include "lower.hpp"
 #include "pack.hpp"
+#include "plan.hpp"
 
 using namespace rrx;
 
@@ -27,9 +29,8 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
 int hip_fail(hipError_t e, const char *what) {
     return fail(RRX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+int launched(int e, const char *what) { return e ? hip_fail((hipError_t)e, what) : RRX_OK; }     // (what a dev:: launcher returned)
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(e_, #expr); } while (0)
-
-constexpr uint32_t kMaxSubsetStates = 16384;   // subset construction is abandoned beyond this
 
 // One device allocation, freed on its own device.
 struct DeviceAlloc {
@@ -112,19 +113,8 @@ struct MailboxGuard {
 
 }  // namespace
 
-struct rrx_regex {
+struct rrx_regex : Programs {                            // (plan.hpp: the programs, the match tables' forms, the engine)
     std::string pattern;
-    RefAutomaton ref;
-    Trimmed trimmed;
-    bool has_nfa = false, has_dfa = false;
-    NfaProgram nfa;
-    NfaProgram nfa_wave;         // up to 4096 positions, no carry groups (wave-cooperative engine)
-    bool has_wave = false;
-    NfaProgram nfa_block;        // up to 65536 positions, exception edges in CSR form (wave-resident engine)
-    bool has_block = false;
-    DfaProgram dfa;
-    Dfa2Program dfa2;
-    bool has_dfa2 = false;
     // Order of the stride-2 table's rows and columns in LDS (empty: as numbered).  The order costs no memory and decides which
     // entries share an LDS bank: bank = (row slot * row words + column slot) mod 32.  State 0 (dead) keeps slot 0.
     std::vector<uint32_t> t2_row_slot, t2_col_slot;
@@ -170,7 +160,7 @@ struct rrx_regex {
         bool ok = false;
         for (uint32_t budget = 2048; budget >= 64 && !ok; budget /= 2) {       // the largest table whose stride-2 form fits the LDS
             if (!lower_dfa_sampled(red, text, pieces, piece_bytes, budget, d, &st)) return false;
-            ok = d.nstates <= 4096 && lower_dfa2(d, 1024, d2) && (size_t)d2.nstates * (d2.ncols | 1u) * 4 <= dev::kDfa2MaxTable;
+            ok = lower_dfa2_that_fits(d, d2);
         }
         if (!ok || d.escaped.empty()) return false;      // (no escape state: the closure closed the table - lower_dfa would have too)
         // A table its own sample escapes from is the wrong tool: every escaped line is read a second time by the NFA engine, so
@@ -220,7 +210,7 @@ struct rrx_regex {
     // stride-2 tables uploaded again in the profiled order (under `mu`)
     mutable std::vector<DeviceAlloc> kept;
     bool t2_order_applies() const {                      // single-copy tables only: interleaved copies already keep lanes apart
-        return has_dfa2 && (size_t)dfa2.nstates * (dfa2.ncols | 1u) * 4 * 2 > dev::kDfa2TableBudget;
+        return match.has_dfa2 && dfa2_table_bytes(match.dfa2) * 2 > dev::kDfa2TableBudget;
     }
     // What happens to a found order (runs in the searching thread).  For devices whose tables are already up the stride-2 arrays
     // are built and uploaded again WITHOUT `mu` - launches go on meanwhile on the table as numbered; `mu` is taken twice, briefly:
@@ -233,7 +223,7 @@ struct rrx_regex {
         for (int device : up) {
             Image img;
             OnDevice<dev::Dfa2Device> t;
-            (void)pack_dfa2(dfa2, rows, cols, img, t.d);
+            (void)pack_dfa2(match.dfa2, rows, cols, img, t.d);
             hipStream_t st2 = nullptr;
             bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&st2, hipStreamNonBlocking) == hipSuccess &&
                       upload(device, img, t.mem, st2) == hipSuccess;
@@ -260,22 +250,15 @@ struct rrx_regex {
         if (!t2_order_applies() || !sample || lanes < 32) return t2_order.skip();
         if (!now && !opt_background_order.load()) return true;                   // (left undecided: rrx_order_table may still come)
         std::vector<uint8_t> copy(sample, sample + (size_t)lanes * bytes_per_lane);
-        return t2_order.start(dfa2, std::move(copy), lanes, bytes_per_lane, /*background=*/!now,
+        return t2_order.start(match.dfa2, std::move(copy), lanes, bytes_per_lane, /*background=*/!now,
                               [this](std::vector<uint32_t> &&r, std::vector<uint32_t> &&c, const Dfa2OrderStats &st) { apply_t2_order(std::move(r), std::move(c), st); });
     }
     dev::Dfa2Device dfa2_device(const DeviceTables *t) const { std::lock_guard<std::mutex> lock(mu); return t->dfa2; }
-    int engine = 0;
-    bool line_wide = false;      // DFA engine: byte-indexed rows (<= kWideMaxStates states) or class-indexed rows
-    bool line_global = false;    // DFA engine: class-indexed table too large for LDS, kept in global memory
     mutable std::mutex mu;
     mutable std::map<int, OnDevice<DeviceTables>> on_device;
-    // search (built on first use): the forward "anything, then the pattern" DFA and the reverse DFA
+    // search (built on first use; plan.hpp: plan_search)
     mutable int search_state = 0;        // 0 = not built, 1 = built, -1 = does not fit
-    mutable DfaProgram search_fwd, search_rev;
-    mutable SearchLineProgram search_line;  // stripe-wise form (nrows = 0: not built)
-    mutable SearchLine2Program search_line2;    // its stride-2 form, what the stripe-wise kernel runs (nrows = 0: not built)
-    mutable dev::SearchChunkDevice chunk_proto; // its layout on the device, without the pointers (nrows = 0: the line-per-lane kernels)
-    mutable bool search_nullable = false;       // the pattern accepts the empty string: every offset is a match, no table (empty_matches)
+    mutable SearchPlan search;
     mutable std::map<int, OnDevice<dev::SearchChunkDevice>> search_on_device;
     // The plain table in the wide line-table format with one more column: 0..127 byte values ('\n' an ordinary byte), 128 = any
     // byte >= 0x80, 129 = END OF ITEM (verdict of the row, back to the start row).  For explicit items stepped stripe-wise.
@@ -354,10 +337,7 @@ struct rrx_regex {
     // The stride-2 table of explicit items with a separator byte each (trim 1; lower_dfa2's items form): nullptr where the regex
     // has no stride-2 table or the items form - one symbol more - does not fit the same LDS region.
     bool items2_program_locked() const {                 // host side (call with `mu` held)
-        if (has_dfa2 && items2_state == 0) {
-            items2_state = lower_dfa2(dfa, 1024, items2_prog, /*items=*/true) &&
-                           (size_t)items2_prog.nstates * (items2_prog.ncols | 1u) * 4 <= dev::kDfa2MaxTable ? 1 : 2;
-        }
+        if (match.has_dfa2 && items2_state == 0) items2_state = lower_dfa2_that_fits(match.dfa, items2_prog, /*items=*/true) ? 1 : 2;
         return items2_state == 1;
     }
     bool items2_program() const { std::lock_guard<std::mutex> lock(mu); return items2_program_locked(); }
@@ -388,47 +368,15 @@ struct rrx_regex {
     const dev::LineDfaDevice *items_table(int device) const {       // (none: more states than 16-bit row offsets allow)
         std::lock_guard<std::mutex> lock(mu);
         const dev::LineDfaDevice *d = nullptr;
-        (void)upload_once(items_on_device, device, true, [&](Image &img, dev::LineDfaDevice &t) { return pack_items(dfa, img, t); }, &d);
+        (void)upload_once(items_on_device, device, true, [&](Image &img, dev::LineDfaDevice &t) { return pack_items(match.dfa, img, t); }, &d);
         return d;
     }
 
     // Host side of the search tables (call with `mu` held).  RRX_OK also for a pattern that accepts the empty string: it needs
-    // no table (search_nullable), search_fwd / search_rev are built all the same (rrx_program_words).
+    // no table (search.nullable), search.fwd / search.rev are built all the same (rrx_program_words).
     int build_search() const {
-        if (search_state == 0) {
-            const Reduced red = reduce(trimmed);
-            const bool ok = search_dfas(red, kMaxSubsetStates, search_fwd, search_rev);
-            search_nullable = rrx_accepts_empty(this) != 0;
-            search_line = SearchLineProgram();
-            search_line2 = SearchLine2Program();
-            chunk_proto = dev::SearchChunkDevice();
-            if (ok && !search_nullable) {
-                // the product with the anchored table tells the hits whose match starts at the line start (no walk back); a
-                // product beyond the row budget: the forward table alone (every hit walks)
-                DfaProgram anchored;
-                if (!(opt_search_anchored.load() && lower_dfa(red, kMaxSubsetStates, anchored) && lower_search_line(search_fwd, &anchored, 65534, search_line)) &&
-                    !lower_search_line(search_fwd, nullptr, 65534, search_line))
-                    search_line = SearchLineProgram();
-            }
-            if (search_line.nrows) {
-                uint32_t column[256];
-                for (int c = 0; c < 256; c++) column[c] = c == '\n' ? search_line.ncols - 1 : search_fwd.cls[c];
-                if (!lower_search_line2(search_line, column, 16383, search_line2)) search_line2 = SearchLine2Program();
-            }
-            // the stripe-wise kernel's layout of that table: LDS if it fits beside the reverse table, the job pools and a result
-            // window, else HBM/L2 (device.hpp: SearchChunkDevice)
-            const SearchLine2Program &s2 = search_line2;
-            if (s2.nrows && search_fwd.ncls < 128) {
-                dev::SearchChunkDevice c = search_chunk_layout(s2, search_fwd, search_rev, /*in_global=*/false);
-                bool fits = s2.ncols <= 127 && c.base_row + s2.nrows <= 4096 && dev::search_chunks_lds_bytes(c) <= dev::kSearchChunkLdsBudget;
-                if (!fits) {
-                    c = search_chunk_layout(s2, search_fwd, search_rev, /*in_global=*/true);
-                    fits = dev::search_chunks_lds_bytes(c) <= dev::kSearchChunkLdsBudget;      // (the reverse table has no global form)
-                }
-                if (fits) chunk_proto = c;
-            }
-            search_state = ok && (search_nullable || chunk_proto.nrows) ? 1 : -1;
-        }
+        if (search_state == 0)
+            search_state = plan_search(reduce(trimmed), opt_search_anchored.load() != 0, accepts_empty(), dev::search_chunks_lds_bytes, search) ? 1 : -1;
         return search_state == 1 ? RRX_OK
                                  : fail(RRX_ERR_UNSUPPORTED, "search tables too large for the device (the reverse DFA must fit 64 KiB of LDS, the forward "
                                                               "product table 65534 rows and 256 MiB)");
@@ -439,56 +387,32 @@ struct rrx_regex {
         int rc = build_search();
         if (rc) return rc;
         *out = nullptr;
-        if (search_nullable) return RRX_OK;
-        auto pack = [&](Image &img, dev::SearchChunkDevice &t) { pack_search(search_line2, search_fwd, search_rev, chunk_proto, img, t); return true; };
+        if (search.nullable) return RRX_OK;
+        auto pack = [&](Image &img, dev::SearchChunkDevice &t) { pack_search(search.line2, search.fwd, search.rev, search.layout, img, t); return true; };
         return upload_once(search_on_device, device, false, pack, out);
     }
 
     // "Contains a match" (rrx_contains_corpus): the forward search table with its accepting states folded into one absorbing
-    // state (lower.hpp: contains_dfa), in the forms of the match path and by its fit rules (rrx_compile_ex) - the stride-2 form,
-    // the wide / classed LDS line table, the global line table; a regex compiled with RRX_ENGINE_DFA / _DFA_GLOBAL keeps it on
-    // the byte-stride LDS / global table.  Host side (call with `mu` held).
+    // state (lower.hpp: contains_dfa), in the forms of the match path and by its fit rules (plan.hpp: LineTables) - the stride-2
+    // form, the wide / classed LDS line table, the global line table; a regex compiled with RRX_ENGINE_DFA / _DFA_GLOBAL keeps it
+    // on the byte-stride LDS / global table.  Host side (call with `mu` held).
     mutable int contains_state = 0;      // 0 = not built, 1 = built, -1 = no table
-    mutable DfaProgram contains_dfa;
-    mutable Dfa2Program contains_dfa2;
-    mutable bool contains_has_dfa2 = false, contains_wide = false, contains_global = false;
+    mutable LineTables contains;
     mutable std::map<int, OnDevice<DeviceTables>> contains_on_device;
     int build_contains() const {
         if (contains_state == 0) {
             (void)build_search();                        // (what the search entries cannot use does not matter here: the forward table does)
-            bool ok = search_fwd.nstates != 0 && rrx::contains_dfa(search_fwd, contains_dfa);
-            if (ok) {
-                const DfaProgram &d = contains_dfa;
-                contains_wide = d.nstates <= dev::kWideMaxStates && requested_engine != RRX_ENGINE_DFA_GLOBAL;
-                const size_t classed_entries = (size_t)d.nstates * (d.ncls + 2);
-                contains_global = requested_engine == RRX_ENGINE_DFA_GLOBAL || (!contains_wide && classed_entries > dev::kClassedMaxEntries);
-                if (contains_global && classed_entries >= ((size_t)1 << 24)) ok = false;
-                if (ok && !contains_global && requested_engine != RRX_ENGINE_DFA && d.nstates <= 4096)
-                    contains_has_dfa2 = lower_dfa2(d, 1024, contains_dfa2) &&
-                                        (size_t)contains_dfa2.nstates * (contains_dfa2.ncols | 1u) * 4 <= dev::kDfa2MaxTable;
-            }
-            contains_state = ok ? 1 : -1;
+            contains_state = search.fwd.nstates != 0 && contains_dfa(search.fwd, contains.dfa) && contains.decide(requested_engine) ? 1 : -1;
         }
         return contains_state == 1 ? RRX_OK
-                                   : fail(RRX_ERR_UNSUPPORTED, search_fwd.nstates ? "contains table too large for the device (the global form holds 2^24 entries)"
+                                   : fail(RRX_ERR_UNSUPPORTED, search.fwd.nstates ? "contains table too large for the device (the global form holds 2^24 entries)"
                                                                                   : "no contains table: the forward search automaton does not determinise within the state budget");
     }
-    const char *contains_name_locked() const {
-        return contains_has_dfa2 ? "dfa-stride2-table" : contains_global ? "dfa-global-table" : contains_wide ? "dfa-wide-table" : "dfa-classed-table";
-    }
-    // The contains tables on `device` (uploaded once); the descriptors are copied out under the lock, the launch runs without it.
-    int contains_tables(int device, bool *stride2, dev::Dfa2Device *d2, dev::LineDfaDevice *line) const {
+    // The contains tables on `device` (uploaded once)
+    int contains_tables(int device, const DeviceTables **out) const {
         std::lock_guard<std::mutex> lock(mu);
-        int rc = build_contains();
-        if (rc) return rc;
-        const DeviceTables *t = nullptr;
-        rc = upload_once(contains_on_device, device, false, [&](Image &img, DeviceTables &dt) {
-            pack_dfa_tables(contains_dfa, contains_wide, contains_global, contains_has_dfa2 ? &contains_dfa2 : nullptr, {}, {}, img, dt);
-            return true;
-        }, &t);
-        if (rc) return rc;
-        *stride2 = contains_has_dfa2; *d2 = t->dfa2; *line = t->line;
-        return RRX_OK;
+        const int rc = build_contains();
+        return rc ? rc : upload_once(contains_on_device, device, false, [&](Image &img, DeviceTables &t) { contains.pack({}, {}, img, t); return true; }, out);
     }
 
     // Upload the program for `device` once; returns the device-side descriptors.
@@ -503,7 +427,7 @@ struct rrx_regex {
             } else if (engine == RRX_ENGINE_NFA) {
                 pack_lane_nfa(nfa, img, t.nfa);
             } else {
-                pack_dfa_tables(dfa, line_wide, line_global, has_dfa2 ? &dfa2 : nullptr, t2_row_slot, t2_col_slot, img, t);
+                match.pack(t2_row_slot, t2_col_slot, img, t);
             }
             return true;
         }, out);
@@ -553,30 +477,7 @@ int rrx_compile_ex(const char *pattern, int engine, rrx_regex **out) {
     try {
         re->pattern = pattern;
         re->requested_engine = engine;
-        re->ref = build_reference_automaton(re->pattern);
-        re->trimmed = trim(re->ref);
-        const Reduced red = reduce(re->trimmed);
-        if (engine == RRX_ENGINE_AUTO || engine == RRX_ENGINE_NFA) re->has_nfa = lower_nfa(red, dev::kMaxNfaWords * 32, re->nfa, /*allow_carry=*/true, /*gaps=*/true);
-        if (engine != RRX_ENGINE_NFA && engine != RRX_ENGINE_NFA_WAVE && engine != RRX_ENGINE_NFA_BLOCK && engine != RRX_ENGINE_NFA_SPARSE) {     // (DFA, DFA_GLOBAL, DFA2, AUTO)
-            re->has_dfa = lower_dfa(red, kMaxSubsetStates, re->dfa);
-            if (re->has_dfa) {
-                re->line_wide = re->dfa.nstates <= dev::kWideMaxStates && engine != RRX_ENGINE_DFA_GLOBAL;
-                const size_t classed_entries = (size_t)re->dfa.nstates * (re->dfa.ncls + 2);
-                re->line_global = engine == RRX_ENGINE_DFA_GLOBAL || (!re->line_wide && classed_entries > dev::kClassedMaxEntries);
-                if (re->line_global && classed_entries >= ((size_t)1 << 24)) re->has_dfa = false;
-                // stride-2 form: when the table (rows of distinct pair columns) fits next to the 32 KiB pair table
-                if (re->has_dfa && !re->line_global && engine != RRX_ENGINE_DFA && re->dfa.nstates <= 4096) {
-                    re->has_dfa2 = lower_dfa2(re->dfa, 1024, re->dfa2) &&
-                                   (size_t)re->dfa2.nstates * (re->dfa2.ncols | 1u) * 4 <= dev::kDfa2MaxTable;
-                }
-            }
-        }
-        // the wave-cooperative form: when asked for, or as the last resort of AUTO
-        if (engine == RRX_ENGINE_NFA_WAVE || (engine == RRX_ENGINE_AUTO && !re->has_nfa && !re->has_dfa))
-            re->has_wave = lower_nfa(red, dev::kGroupMaxBits, re->nfa_wave, /*allow_carry=*/false, /*gaps=*/true);
-        // the wave-resident form (any automaton up to 65536 positions): when asked for, or when nothing else took it
-        if (engine == RRX_ENGINE_NFA_BLOCK || engine == RRX_ENGINE_NFA_SPARSE || (engine == RRX_ENGINE_AUTO && !re->has_nfa && !re->has_dfa && !re->has_wave))
-            re->has_block = lower_nfa(red, dev::kBlockMaxBits, re->nfa_block, /*allow_carry=*/false, /*gaps=*/true);
+        plan_engines(re->pattern, engine, *re);
     } catch (const PatternError &e) {
         delete re;
         return fail(RRX_ERR_PATTERN, e.what());
@@ -587,14 +488,6 @@ int rrx_compile_ex(const char *pattern, int engine, rrx_regex **out) {
         delete re;
         return fail(RRX_ERR_PATTERN, std::string("internal: ") + e.what());
     }
-    // AUTO: the LDS-resident table when it fits, else the register-resident NFA, else the table in global memory
-    if (engine == RRX_ENGINE_NFA) re->engine = re->has_nfa ? RRX_ENGINE_NFA : 0;
-    else if (engine == RRX_ENGINE_DFA || engine == RRX_ENGINE_DFA_GLOBAL) re->engine = re->has_dfa ? RRX_ENGINE_DFA : 0;
-    else if (engine == RRX_ENGINE_NFA_WAVE) re->engine = re->has_wave ? RRX_ENGINE_NFA_WAVE : 0;
-    else if (engine == RRX_ENGINE_NFA_BLOCK || engine == RRX_ENGINE_NFA_SPARSE) re->engine = re->has_block ? engine : 0;
-    else if (engine == RRX_ENGINE_DFA2) re->engine = re->has_dfa2 ? RRX_ENGINE_DFA : 0;
-    else re->engine = (re->has_dfa && !re->line_global) ? RRX_ENGINE_DFA : re->has_nfa ? RRX_ENGINE_NFA : re->has_dfa ? RRX_ENGINE_DFA
-                      : re->has_wave ? RRX_ENGINE_NFA_WAVE : re->has_block ? RRX_ENGINE_NFA_BLOCK : 0;
     if (!re->engine) {
         char msg[200];
         std::snprintf(msg, sizeof msg, "automaton too large for the requested engine (%u useful states)", re->trimmed.n);
@@ -617,14 +510,7 @@ uint32_t rrx_ref_row(const rrx_regex *re, uint32_t state, unsigned c, uint32_t *
     return (uint32_t)r.size();
 }
 int rrx_engine(const rrx_regex *re) { return re->engine; }
-const char *rrx_engine_name(const rrx_regex *re) {
-    if (re->engine == RRX_ENGINE_NFA_WAVE) return "nfa-group-cooperative";
-    if (re->engine == RRX_ENGINE_NFA_BLOCK) return "nfa-wave-resident";
-    if (re->engine == RRX_ENGINE_NFA_SPARSE) return "nfa-wave-sparse";
-    if (re->engine != RRX_ENGINE_DFA) return "nfa-shift-and";
-    if (re->has_dfa2) return "dfa-stride2-table";      // (the byte-stride table still serves corpora with bytes >= 0x80)
-    return re->line_global ? "dfa-global-table" : re->line_wide ? "dfa-wide-table" : "dfa-classed-table";
-}
+const char *rrx_engine_name(const rrx_regex *re) { return re->engine_name(); }
 uint32_t rrx_useful_states(const rrx_regex *re) { return re->trimmed.n; }
 int rrx_order_table(rrx_regex *re, const void *sample, uint32_t lanes, uint32_t bytes_per_lane) {
     if (!re || !sample || lanes < 32 || bytes_per_lane < 2) return fail(RRX_ERR_ARG, "sample: at least 32 lanes of 2 bytes");
@@ -635,7 +521,7 @@ int rrx_order_table(rrx_regex *re, const void *sample, uint32_t lanes, uint32_t 
 int rrx_table_order(const rrx_regex *re, double *conflict_before, double *conflict_after) {
     const TableOrderSearch::State st = re->t2_order.state();          // (one atomic read; the thread object is its owner's)
     std::lock_guard<std::mutex> lock(re->mu);
-    const bool profiled = st == TableOrderSearch::kDone && re->t2_row_slot.size() == re->dfa2.nstates && re->has_dfa2 && re->t2_order_stats.half_waves;
+    const bool profiled = st == TableOrderSearch::kDone && re->t2_row_slot.size() == re->match.dfa2.nstates && re->match.has_dfa2 && re->t2_order_stats.half_waves;
     if (conflict_before) *conflict_before = profiled ? re->t2_order_stats.before : 0.0;
     if (conflict_after) *conflict_after = profiled ? re->t2_order_stats.after : 0.0;
     return profiled ? 1 : st == TableOrderSearch::kRunning ? 2 : 0;   // 2: the search is running
@@ -694,94 +580,46 @@ int rrx_set_option(rrx_regex *re, int option, int64_t value) {
 }
 uint32_t rrx_byte_classes(const rrx_regex *re) { return re->trimmed.ncls; }
 uint32_t rrx_words_per_set(const rrx_regex *re) { return re->has_nfa ? re->nfa.W : re->has_wave ? re->nfa_wave.W : re->has_block ? re->nfa_block.W : 0; }
-int rrx_accepts_empty(const rrx_regex *re) {
-    return re->has_nfa ? re->nfa.accepts_empty : re->has_wave ? re->nfa_wave.accepts_empty : re->has_block ? re->nfa_block.accepts_empty : re->dfa.accepts_empty;
-}
+int rrx_accepts_empty(const rrx_regex *re) { return re->accepts_empty(); }
 
 size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t cap) {
     std::vector<uint32_t> w;
-    if ((kind == RRX_ENGINE_NFA && re->has_nfa) || (kind == RRX_ENGINE_NFA_WAVE && re->has_wave)) {
-        const NfaProgram &p = kind == RRX_ENGINE_NFA ? re->nfa : re->nfa_wave;
-        w = {p.W, p.nbits, p.n_exc, p.accepts_empty ? 1u : 0u};
-        for (auto *v : {&p.init, &p.fin, &p.chain, &p.self, &p.excm, &p.cgrp, &p.ctgt, &p.B, &p.X}) w.insert(w.end(), v->begin(), v->end());
+    if (kind == RRX_ENGINE_NFA && re->has_nfa) {
+        append_words(w, re->nfa, /*csr=*/false);
+    } else if (kind == RRX_ENGINE_NFA_WAVE && re->has_wave) {
+        append_words(w, re->nfa_wave, /*csr=*/false);
     } else if ((kind == RRX_ENGINE_NFA_BLOCK || kind == RRX_ENGINE_NFA_SPARSE) && re->has_block) {
-        const NfaProgram &p = re->nfa_block;
-        w = {p.W, p.nbits, p.n_exc, p.accepts_empty ? 1u : 0u};
-        for (auto *v : {&p.init, &p.fin, &p.chain, &p.self, &p.excm, &p.cgrp, &p.ctgt, &p.B, &p.xoff, &p.xtgt}) w.insert(w.end(), v->begin(), v->end());
-    } else if (kind == RRX_PROGRAM_SEARCH_LINE) {
+        append_words(w, re->nfa_block, /*csr=*/true);
+    } else if (kind == RRX_PROGRAM_SEARCH_LINE || kind == RRX_PROGRAM_SEARCH_LINE2 || kind == RRX_PROGRAM_SEARCH_FWD || kind == RRX_PROGRAM_SEARCH_REV) {
         std::lock_guard<std::mutex> lock(re->mu);
-        if (re->build_search() || !re->search_line.nrows) return 0;
-        const SearchLineProgram &d = re->search_line;
-        w = {d.nrows, d.ncols, d.start, d.skip};
-        for (int c = 0; c < 256; c++) w.push_back(c == '\n' ? d.ncols - 1 : re->search_fwd.cls[c]);
-        w.insert(w.end(), d.table.begin(), d.table.end());
-    } else if (kind == RRX_PROGRAM_SEARCH_LINE2) {
-        std::lock_guard<std::mutex> lock(re->mu);
-        if (re->build_search() || !re->search_line2.nrows) return 0;
-        const SearchLine2Program &d = re->search_line2;
-        w = {d.nrows, d.ncols, d.start, d.skip, re->chunk_proto.nrows ? (re->chunk_proto.in_global ? 2u : 1u) : 0u};
-        for (uint16_t c : d.pair_col) w.push_back(c);
-        w.insert(w.end(), d.first.begin(), d.first.end());
-        w.insert(w.end(), d.all.begin(), d.all.end());
+        if (re->build_search()) return 0;
+        const SearchPlan &s = re->search;
+        if (kind == RRX_PROGRAM_SEARCH_FWD) append_words(w, s.fwd);
+        else if (kind == RRX_PROGRAM_SEARCH_REV) append_words(w, s.rev);
+        else if (kind == RRX_PROGRAM_SEARCH_LINE && s.line.nrows) append_words(w, s.line, s.fwd);
+        else if (kind == RRX_PROGRAM_SEARCH_LINE2 && s.line2.nrows) append_words(w, s.line2, s.layout);
     } else if (kind == RRX_PROGRAM_CONTAINS_DFA || kind == RRX_PROGRAM_CONTAINS_DFA2) {
         std::lock_guard<std::mutex> lock(re->mu);
         if (re->build_contains()) return 0;
-        if (kind == RRX_PROGRAM_CONTAINS_DFA) {
-            const DfaProgram &d = re->contains_dfa;
-            w = {d.nstates, d.ncls, d.start, d.accepts_empty ? 1u : 0u};
-            for (int c = 0; c < 256; c++) w.push_back(d.cls[c]);
-            for (uint8_t a : d.accepting) w.push_back(a);
-            for (uint16_t n : d.next) w.push_back(n);
-        } else if (re->contains_has_dfa2) {
-            const Dfa2Program &d = re->contains_dfa2;
-            w = {d.nstates, d.ncols, d.start, d.accepts_empty ? 1u : 0u};
-            for (uint16_t c : d.pair_col) w.push_back(c);
-            w.insert(w.end(), d.next2.begin(), d.next2.end());
-        }
-    } else if (kind == RRX_PROGRAM_DFA2_ORDER && re->has_dfa2) {
+        if (kind == RRX_PROGRAM_CONTAINS_DFA) append_words(w, re->contains.dfa);
+        else if (re->contains.has_dfa2) append_words(w, re->contains.dfa2);
+    } else if (kind == RRX_PROGRAM_DFA2_ORDER && re->match.has_dfa2) {
         std::lock_guard<std::mutex> lock(re->mu);
-        if (re->t2_row_slot.size() != re->dfa2.nstates || re->t2_col_slot.size() != re->dfa2.ncols) return 0;
-        w = {re->dfa2.nstates, re->dfa2.ncols};
+        if (re->t2_row_slot.size() != re->match.dfa2.nstates || re->t2_col_slot.size() != re->match.dfa2.ncols) return 0;
+        w = {re->match.dfa2.nstates, re->match.dfa2.ncols};
         w.insert(w.end(), re->t2_row_slot.begin(), re->t2_row_slot.end());
         w.insert(w.end(), re->t2_col_slot.begin(), re->t2_col_slot.end());
     } else if (kind == RRX_PROGRAM_SAMPLED_DFA || kind == RRX_PROGRAM_SAMPLED_DFA2) {
         if (!re->sampled_ready.load(std::memory_order_acquire)) return 0;
         std::lock_guard<std::mutex> lock(re->mu);
-        if (kind == RRX_PROGRAM_SAMPLED_DFA) {              // the DFA layout, then the escaped flag per state
-            const DfaProgram &d = re->sampled_dfa;
-            w = {d.nstates, d.ncls, d.start, d.accepts_empty ? 1u : 0u};
-            for (int c = 0; c < 256; c++) w.push_back(d.cls[c]);
-            for (uint8_t a : d.accepting) w.push_back(a);
-            for (uint16_t n : d.next) w.push_back(n);
-            for (uint8_t e : d.escaped) w.push_back(e);
-        } else {                                            // the stride-2 layout (entries: next | result bits << 16 | verdict pairs << 24)
-            const Dfa2Program &d = re->sampled_dfa2;
-            w = {d.nstates, d.ncols, d.start, d.accepts_empty ? 1u : 0u};
-            for (uint16_t c : d.pair_col) w.push_back(c);
-            w.insert(w.end(), d.next2.begin(), d.next2.end());
-        }
-    } else if (kind == RRX_PROGRAM_DFA2_ITEMS && re->has_dfa2) {
-        if (re->items2_program()) {
-            const Dfa2Program &d = re->items2_prog;
-            w = {d.nstates, d.ncols, d.start, d.accepts_empty ? 1u : 0u, d.pair_dim};
-            for (uint16_t c : d.pair_col) w.push_back(c);
-            w.insert(w.end(), d.next2.begin(), d.next2.end());
-        }
-    } else if (kind == RRX_ENGINE_DFA2 && re->has_dfa2) {
-        const Dfa2Program &d = re->dfa2;
-        w = {d.nstates, d.ncols, d.start, d.accepts_empty ? 1u : 0u};
-        for (uint16_t c : d.pair_col) w.push_back(c);
-        w.insert(w.end(), d.next2.begin(), d.next2.end());
-    } else if ((kind == RRX_ENGINE_DFA && re->has_dfa) || kind == RRX_PROGRAM_SEARCH_FWD || kind == RRX_PROGRAM_SEARCH_REV) {
-        if (kind != RRX_ENGINE_DFA) {
-            std::lock_guard<std::mutex> lock(re->mu);
-            if (re->build_search()) return 0;
-        }
-        const DfaProgram &d = kind == RRX_ENGINE_DFA ? re->dfa : kind == RRX_PROGRAM_SEARCH_FWD ? re->search_fwd : re->search_rev;
-        w = {d.nstates, d.ncls, d.start, d.accepts_empty ? 1u : 0u};
-        for (int c = 0; c < 256; c++) w.push_back(d.cls[c]);
-        for (uint8_t a : d.accepting) w.push_back(a);
-        for (uint16_t n : d.next) w.push_back(n);
+        if (kind == RRX_PROGRAM_SAMPLED_DFA) append_words(w, re->sampled_dfa, /*escaped=*/true);
+        else append_words(w, re->sampled_dfa2);
+    } else if (kind == RRX_PROGRAM_DFA2_ITEMS && re->match.has_dfa2) {
+        if (re->items2_program()) append_words(w, re->items2_prog, /*pair_dim=*/true);
+    } else if (kind == RRX_ENGINE_DFA2 && re->match.has_dfa2) {
+        append_words(w, re->match.dfa2);
+    } else if (kind == RRX_ENGINE_DFA && re->has_dfa) {
+        append_words(w, re->match.dfa);
     }
     for (size_t i = 0; i < w.size() && i < cap; i++) out[i] = w[i];
     return w.size();
@@ -923,6 +761,16 @@ static int match_corpus_sampled(const rrx_regex *re, const rrx_corpus *c, const 
     return rc2;
 }
 
+// The table engine of a LineTables on a corpus (`bits` zeroed): the stride-2 table where there is one - on a corpus with bytes
+// >= 0x80 only if the caller allows the instantiation that steps them as 0x00 (stride2_over_high) -, else the line table.
+static int launch_line_tables(const rrx_regex *re, const rrx_corpus *c, const LineTables &lt, const DeviceTables *t, bool stride2_over_high, uint32_t *bits,
+                              void *stream) {
+    if (!lt.has_dfa2 || (c->has_high && !stride2_over_high)) return dev::match_stripes_dfa(t->line, c->has_high, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, bits, stream);
+    const dev::Dfa2Device d2 = re->dfa2_device(t);
+    const uint32_t flush_mask = re->opt_flush_slots.load() ? (uint32_t)re->opt_flush_slots.load() - 1u : dev::flush_mask_for(c->nbytes, c->nlines);
+    return (c->has_high ? dev::match_stripes_dfa2_clean : dev::match_stripes_dfa2)(d2, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, bits, stream, flush_mask);
+}
+
 int rrx_match_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_accept_bits, void *stream) {
     if (!re || !c || (c->nlines && !d_accept_bits)) return fail(RRX_ERR_ARG, "null argument");
     if (!re->t2_order.decided() && c->h_sample && !c->has_high) (void)re->decide_t2_order(c->h_sample, c->sample_lanes, kSampleBytes, /*now=*/false);
@@ -954,53 +802,41 @@ int rrx_match_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_accep
                 ? dev::match_stripes_group_nfa(t->group, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, stream)
             : re->engine == RRX_ENGINE_NFA
                 ? dev::match_stripes_nfa(t->nfa, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, stream)
-            : (re->has_dfa2 && !c->has_high)
-                ? (re->opt_units_per_wg.load()
-                       ? dev::match_units_dfa2(re->dfa2_device(t), c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, (uint32_t)re->opt_units_per_wg.load(), stream)
-                       : dev::match_stripes_dfa2(re->dfa2_device(t), c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, stream,
-                                                 re->opt_flush_slots.load() ? (uint32_t)re->opt_flush_slots.load() - 1u : dev::flush_mask_for(c->nbytes, c->nlines)))
-                : dev::match_stripes_dfa(t->line, c->has_high, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, stream);
-    if (e) return hip_fail((hipError_t)e, "match_stripes launch");
-    return RRX_OK;
+            : (re->match.has_dfa2 && !c->has_high && re->opt_units_per_wg.load())
+                ? dev::match_units_dfa2(re->dfa2_device(t), c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, (uint32_t)re->opt_units_per_wg.load(), stream)
+                // (a corpus with bytes >= 0x80 leaves the stride-2 table for the byte-stride one)
+                : launch_line_tables(re, c, re->match, t, /*stride2_over_high=*/false, d_accept_bits, stream);
+    return launched(e, "match_stripes launch");
 }
 
 // "Which lines contain a match": the batch kernels of rrx_match_corpus on the contains table (build_contains).  On a corpus with
 // bytes >= 0x80 the stride-2 table keeps its kernel - the instantiation that steps such bytes as 0x00, which is their class.
 int rrx_contains_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_bits, void *stream) {
     if (!re || !c || (c->nlines && !d_bits)) return fail(RRX_ERR_ARG, "null argument");
-    bool stride2 = false;
-    dev::Dfa2Device d2;
-    dev::LineDfaDevice line;
-    int rc = re->contains_tables(c->device, &stride2, &d2, &line);
+    const DeviceTables *t;
+    int rc = re->contains_tables(c->device, &t);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (!c->nlines) return RRX_OK;
     // the kernels merge words with atomic OR: start from an all-zero bitmap
     HIP_TRY(hipMemsetAsync(d_bits, 0, rrx_corpus_bitmap_words(c) * sizeof(uint32_t), (hipStream_t)stream));
-    const uint32_t flush_mask = re->opt_flush_slots.load() ? (uint32_t)re->opt_flush_slots.load() - 1u : dev::flush_mask_for(c->nbytes, c->nlines);
-    const int e = !stride2     ? dev::match_stripes_dfa(line, c->has_high, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_bits, stream)
-                  : c->has_high ? dev::match_stripes_dfa2_clean(d2, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_bits, stream, flush_mask)
-                                : dev::match_stripes_dfa2(d2, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_bits, stream, flush_mask);
-    if (e) return hip_fail((hipError_t)e, "contains launch");
-    return RRX_OK;
+    return launched(launch_line_tables(re, c, re->contains, t, /*stride2_over_high=*/true, d_bits, stream), "contains launch");
 }
 const char *rrx_contains_engine_name(const rrx_regex *re) {
     if (!re) { (void)fail(RRX_ERR_ARG, "null argument"); return nullptr; }
     std::lock_guard<std::mutex> lock(re->mu);
-    return re->build_contains() ? nullptr : re->contains_name_locked();
+    return re->build_contains() ? nullptr : re->contains.name();
 }
 uint32_t rrx_contains_states(const rrx_regex *re) {
     if (!re) { (void)fail(RRX_ERR_ARG, "null argument"); return 0; }
     std::lock_guard<std::mutex> lock(re->mu);
-    return re->build_contains() ? 0 : re->contains_dfa.nstates;
+    return re->build_contains() ? 0 : re->contains.dfa.nstates;
 }
 int rrx_bitmap_count(int device, const uint32_t *d_bits, size_t nlines, uint64_t *d_count, void *stream) {
     if (!d_count || (nlines && !d_bits)) return fail(RRX_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(device));
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit atomics");
-    int e = dev::bitmap_count(d_bits, nlines, reinterpret_cast<unsigned long long *>(d_count), stream);
-    if (e) return hip_fail((hipError_t)e, "bitmap_count launch");
-    return RRX_OK;
+    return launched(dev::bitmap_count(d_bits, nlines, reinterpret_cast<unsigned long long *>(d_count), stream), "bitmap_count launch");
 }
 
 // One-shot entry: a device-resident buffer that nobody has indexed.  With the lane engines (tables and NFA) the text is
@@ -1052,7 +888,7 @@ int rrx_match_device(const rrx_regex *re, int device, const void *d_bytes, size_
     if (rc) return rc;
     if (cap_words) HIP_TRY(hipMemsetAsync(d_accept_bits, 0, cap_words * sizeof(uint32_t), st));
     int e = re->engine == RRX_ENGINE_NFA ? dev::match_onepass_nfa(t->nfa, bytes, nbytes, stripe, nstripes, d_counts, d_slabs, stream)
-            : re->has_dfa2               ? dev::match_onepass_dfa2(re->dfa2_device(t), bytes, nbytes, stripe, nstripes, d_counts, d_slabs, stream)
+            : re->match.has_dfa2         ? dev::match_onepass_dfa2(re->dfa2_device(t), bytes, nbytes, stripe, nstripes, d_counts, d_slabs, stream)
                                          : dev::match_onepass_dfa(t->line, bytes, nbytes, stripe, nstripes, d_counts, d_slabs, stream);
     if (!e) e = dev::scan_counts(d_counts, d_base, d_base + nstripes + 1, nstripes, stream);
     // (words beyond the caller's bitmap are dropped by the compaction; whether there were any follows from the line count)
@@ -1111,13 +947,20 @@ static int chunk_index(const rrx_corpus *c, void *stream) {
     return RRX_OK;
 }
 
+// What every search entry begins with, behind its null checks: the tables (*ct = nullptr: the pattern accepts the empty string),
+// the device and - for a corpus with lines and a pattern with tables - the chunk index.
+static int search_begin(const rrx_regex *re, const rrx_corpus *c, void *stream, const dev::SearchChunkDevice **ct) {
+    const int rc = re->search_tables(c->device, ct);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return c->nlines && *ct ? chunk_index(c, stream) : RRX_OK;
+}
+
 int rrx_search_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_start, uint32_t *d_end, void *stream) {
     if (!re || !c || (c->nlines && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
     const dev::SearchChunkDevice *ct;
-    int rc = re->search_tables(c->device, &ct);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->nlines) return RRX_OK;
+    int rc = search_begin(re, c, stream, &ct);
+    if (rc || !c->nlines) return rc;
     if (!ct) {
         // the pattern accepts the empty string: the accepted substring with the smallest end is [0, 0) in every string - no
         // table, no line offsets, two fills
@@ -1125,53 +968,33 @@ int rrx_search_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_star
         HIP_TRY(hipMemsetAsync(d_end, 0, c->nlines * sizeof(uint32_t), (hipStream_t)stream));
         return RRX_OK;
     }
-    rc = chunk_index(c, stream);
-    if (rc) return rc;
-    int e = dev::search_chunks(*ct, c->has_high, c->d_bytes, c->nbytes, c->d_chunk_base, c->nchunks, c->nlines, d_start, d_end, stream);
-    if (e) return hip_fail((hipError_t)e, "search_chunks launch");
-    return RRX_OK;
+    return launched(dev::search_chunks(*ct, c->has_high, c->d_bytes, c->nbytes, c->d_chunk_base, c->nchunks, c->nlines, d_start, d_end, stream), "search_chunks launch");
 }
 
 int rrx_search_all_count(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_count, void *stream) {
     if (!re || !c || (c->nlines && !d_count)) return fail(RRX_ERR_ARG, "null argument");
     const dev::SearchChunkDevice *ct;
-    int rc = re->search_tables(c->device, &ct);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->nlines) return RRX_OK;
+    int rc = search_begin(re, c, stream, &ct);
+    if (rc || !c->nlines) return rc;
     if (!ct) {                                                       // accepts "": a match at every offset of the line, its end included
         rc = line_offsets(c, stream);
         if (rc) return rc;
-        int e = dev::empty_matches(c->d_line_off, c->nlines, d_count, nullptr, nullptr, nullptr, stream);
-        if (e) return hip_fail((hipError_t)e, "empty_matches launch");
-        return RRX_OK;
+        return launched(dev::empty_matches(c->d_line_off, c->nlines, d_count, nullptr, nullptr, nullptr, stream), "empty_matches launch");
     }
-    rc = chunk_index(c, stream);
-    if (rc) return rc;
-    int e = dev::search_chunks_count(*ct, c->has_high, c->d_bytes, c->nbytes, c->d_chunk_base, c->nchunks, d_count, stream);
-    if (e) return hip_fail((hipError_t)e, "search_chunks_count launch");
-    return RRX_OK;
+    return launched(dev::search_chunks_count(*ct, c->has_high, c->d_bytes, c->nbytes, c->d_chunk_base, c->nchunks, d_count, stream), "search_chunks_count launch");
 }
 
 int rrx_search_all_fill(const rrx_regex *re, const rrx_corpus *c, const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, void *stream) {
     if (!re || !c || (c->nlines && (!d_first || !d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
     const dev::SearchChunkDevice *ct;
-    int rc = re->search_tables(c->device, &ct);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->nlines) return RRX_OK;
+    int rc = search_begin(re, c, stream, &ct);
+    if (rc || !c->nlines) return rc;
     if (!ct) {
         rc = line_offsets(c, stream);
         if (rc) return rc;
-        int e = dev::empty_matches(c->d_line_off, c->nlines, nullptr, d_first, d_start, d_end, stream);
-        if (e) return hip_fail((hipError_t)e, "empty_matches launch");
-        return RRX_OK;
+        return launched(dev::empty_matches(c->d_line_off, c->nlines, nullptr, d_first, d_start, d_end, stream), "empty_matches launch");
     }
-    rc = chunk_index(c, stream);
-    if (rc) return rc;
-    int e = dev::search_chunks_fill(*ct, c->has_high, c->d_bytes, c->nbytes, c->d_chunk_base, c->nchunks, d_first, d_start, d_end, stream);
-    if (e) return hip_fail((hipError_t)e, "search_chunks_fill launch");
-    return RRX_OK;
+    return launched(dev::search_chunks_fill(*ct, c->has_high, c->d_bytes, c->nbytes, c->d_chunk_base, c->nchunks, d_first, d_start, d_end, stream), "search_chunks_fill launch");
 }
 
 // count + fill in one call: one launch (decoupled look-back over the chunks' match counts).  A pattern that accepts the empty
@@ -1181,14 +1004,11 @@ int rrx_search_all(const rrx_regex *re, const rrx_corpus *c, uint64_t *d_first, 
     if (!re || !c || !total || !d_first || (cap && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
     *total = 0;
     const dev::SearchChunkDevice *ct;
-    int rc = re->search_tables(c->device, &ct);
+    int rc = search_begin(re, c, stream, &ct);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     if (!c->nlines) { HIP_TRY(hipMemsetAsync(d_first, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
     if (ct) {
-        rc = chunk_index(c, stream);
-        if (rc) return rc;
         const size_t sb = dev::search_all_scratch_bytes(c->nchunks);
         {
             std::lock_guard<std::mutex> lock(c->mu);
@@ -1235,9 +1055,7 @@ int rrx_bitmap_to_bytes(int device, const uint32_t *d_bits, size_t nlines, uint8
     if (nlines && (!d_bits || !d_accept)) return fail(RRX_ERR_ARG, "null argument");
     if (reinterpret_cast<uintptr_t>(d_accept) & 15) return fail(RRX_ERR_ARG, "byte buffer must be 16-byte aligned");
     HIP_TRY(hipSetDevice(device));
-    int e = dev::expand_bits(d_bits, nlines, d_accept, stream);
-    if (e) return hip_fail((hipError_t)e, "expand_bits launch");
-    return RRX_OK;
+    return launched(dev::expand_bits(d_bits, nlines, d_accept, stream), "expand_bits launch");
 }
 
 // below these a batch stays on the lane-per-item kernel (the index costs more than it saves)
@@ -1251,8 +1069,16 @@ static int match_extents_lanes(const rrx_regex *re, const DeviceTables *t, const
             : re->engine == RRX_ENGINE_NFA_WAVE ? dev::match_extents_group_nfa(t->group, b, d_off, nitems, trim, d_accept, stream)
             : re->engine == RRX_ENGINE_NFA ? dev::match_extents_nfa(t->nfa, b, d_off, nitems, trim, d_accept, stream)
                                          : dev::match_extents_dfa(t->dfa, b, d_off, nitems, trim, d_accept, stream, only_if);
-    if (e) return hip_fail((hipError_t)e, "match_extents launch");
-    return RRX_OK;
+    return launched(e, "match_extents launch");
+}
+// The table of the stripe-wise items kernels on `device`: the stride-2 items table for trim 1 (unless RRX_OPT_ITEMS_STRIDE2 is 0),
+// else - or where that one does not fit - the byte-stride items table; both nullptr: the regex has none (the lane-per-item kernel).
+struct ItemsTable { const dev::LineDfaDevice *items1 = nullptr; const dev::Dfa2Device *items2 = nullptr; };
+static ItemsTable pick_items_table(const rrx_regex *re, int device, uint32_t trim) {
+    ItemsTable t;
+    if (trim == 1 && re->items_stride2.load()) t.items2 = re->items2_table(device);
+    if (!t.items2) t.items1 = re->items_table(device);
+    return t;
 }
 int rrx_match_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                       uint8_t *d_accept, void *stream) {
@@ -1271,13 +1097,9 @@ int rrx_match_extents(const rrx_regex *re, int device, const void *d_bytes, cons
     // stripe-wise kernel does nothing on an unfit batch and the lane-per-item kernel queued behind it does nothing on a fit one.
     // (r4) trim 1 on a regex with a stride-2 table: the stride-2 items table (it also serves automata whose byte-stride items table
     // is beyond the LDS - a{1,300}: 302 rows of 130 columns)
-    const dev::LineDfaDevice *items1 = nullptr;
-    const dev::Dfa2Device *items2 = nullptr;
-    if (re->engine == RRX_ENGINE_DFA && trim <= 1 && nitems >= kItemsStripesMin && !(reinterpret_cast<uintptr_t>(d_accept) & 15)) {
-        if (trim == 1 && re->items_stride2.load()) items2 = re->items2_table(device);
-        if (!items2) items1 = re->items_table(device);
-    }
-    const bool items = items1 || items2;
+    ItemsTable it;
+    if (re->engine == RRX_ENGINE_DFA && trim <= 1 && nitems >= kItemsStripesMin && !(reinterpret_cast<uintptr_t>(d_accept) & 15)) it = pick_items_table(re, device, trim);
+    const bool items = it.items1 || it.items2;
     size_t bound = 0;
     if (items) {
         hipDeviceptr_t abase = nullptr;
@@ -1312,8 +1134,8 @@ int rrx_match_extents(const rrx_regex *re, int device, const void *d_bytes, cons
         if (rc) return rc;
         uint32_t *d_flag = nullptr;
         int le = dev::items_index_build(bound, d_off, nitems, trim, buf, &d_flag, stream, b, kItemsStripesMinBytes);
-        if (!le) le = items2 ? dev::items_match2(*items2, b, bound, nitems, buf, static_cast<uint8_t *>(buf) + ib, d_accept, stream, d_off, d_flag)
-                             : dev::items_match(*items1, b, bound, nitems, trim, buf, static_cast<uint8_t *>(buf) + ib, d_accept, stream, d_off, d_flag);
+        if (!le) le = it.items2 ? dev::items_match2(*it.items2, b, bound, nitems, buf, static_cast<uint8_t *>(buf) + ib, d_accept, stream, d_off, d_flag)
+                                : dev::items_match(*it.items1, b, bound, nitems, trim, buf, static_cast<uint8_t *>(buf) + ib, d_accept, stream, d_off, d_flag);
         if (!le) rc = match_extents_lanes(re, t, b, d_off, nitems, trim, d_accept, stream, d_flag);
         const int rc2 = re->onepass_done(device, st);            // (whatever was queued: the next user waits for it)
         if (le) return hip_fail((hipError_t)le, "match_items_stripes launch");
@@ -1384,14 +1206,12 @@ int rrx_match_items(const rrx_regex *re, const rrx_items *it, uint8_t *d_accept,
     if (rc) return rc;
     HIP_TRY(hipSetDevice(it->device));
     if (it->stripes && re->engine == RRX_ENGINE_DFA && !(reinterpret_cast<uintptr_t>(d_accept) & 15)) {
-        const dev::Dfa2Device *items2 = (it->trim == 1 && re->items_stride2.load()) ? re->items2_table(it->device) : nullptr;
-        const dev::LineDfaDevice *items1 = items2 ? nullptr : re->items_table(it->device);
-        if (items1 || items2) {
+        const ItemsTable tab = pick_items_table(re, it->device, it->trim);
+        if (tab.items1 || tab.items2) {
             std::lock_guard<std::mutex> lock(it->mu);
-            int le = items2 ? dev::items_match2(*items2, it->d_bytes + it->first, it->nbytes, it->nitems, it->d_index, it->d_result, d_accept, stream)
-                            : dev::items_match(*items1, it->d_bytes + it->first, it->nbytes, it->nitems, it->trim, it->d_index, it->d_result, d_accept, stream);
-            if (le) return hip_fail((hipError_t)le, "match_items launch");
-            return RRX_OK;
+            int le = tab.items2 ? dev::items_match2(*tab.items2, it->d_bytes + it->first, it->nbytes, it->nitems, it->d_index, it->d_result, d_accept, stream)
+                                : dev::items_match(*tab.items1, it->d_bytes + it->first, it->nbytes, it->nitems, it->trim, it->d_index, it->d_result, d_accept, stream);
+            return launched(le, "match_items launch");
         }
     }
     // the batch or the pattern does not admit the stripe-wise kernel (the index said so once: no second attempt)
@@ -1400,23 +1220,31 @@ int rrx_match_items(const rrx_regex *re, const rrx_items *it, uint8_t *d_accept,
 
 // One device-resident string of any length.  Long strings take the chunk-map path when the automaton has a small
 // table (every chunk stepped from every state, maps composed); the rest is one item of the extents kernel.
-// `scratch`/`scratch_bytes`: caller-provided device memory (rrx_match_cstr passes the tail of its own buffer).
-static int match_string_with(const rrx_regex *re, int device, const DeviceTables *t, const uint8_t *d_bytes, size_t nbytes, uint8_t *d_accept,
-                             uint8_t *scratch, hipStream_t st) {
-    const bool table_engine = re->engine == RRX_ENGINE_DFA;
-    if (table_engine && nbytes >= kLongStringBytesTable && t->dfa.nstates && t->dfa.nstates <= dev::kLongMaxStates) {
-        uint32_t chunk = 0;
-        (void)dev::long_scratch_bytes(t->dfa.nstates, nbytes, &chunk);
-        int le = dev::match_long_dfa(t->dfa, d_bytes, nbytes, chunk, scratch, d_accept, st);
-        if (le) return hip_fail((hipError_t)le, "match_long launch");
-        return RRX_OK;
+// long_string_plan decides which, once per call: the scratch is sized and the string matched by the same plan.
+// `scratch`: caller-provided device memory of plan.scratch_bytes (rrx_match_cstr passes the tail of its own buffer).
+struct LongStringPlan {
+    enum Kind { kOneItem, kLongDfa, kLongNfa } kind = kOneItem;       // one item of the extents kernel, or the chunk maps of a table / NFA engine
+    uint32_t chunk = 0, nchunks = 0;
+    size_t scratch_bytes = 2 * sizeof(uint64_t);                      // (one item: its two offsets)
+};
+static LongStringPlan long_string_plan(const rrx_regex *re, const DeviceTables *t, size_t nbytes) {
+    LongStringPlan p;
+    if (re->engine == RRX_ENGINE_DFA && nbytes >= kLongStringBytesTable && t->dfa.nstates && t->dfa.nstates <= dev::kLongMaxStates) {
+        p.kind = LongStringPlan::kLongDfa;
+        p.scratch_bytes = dev::long_scratch_bytes(t->dfa.nstates, nbytes, &p.chunk);
+    } else if (re->engine == RRX_ENGINE_NFA && nbytes >= kLongStringBytes && t->nfa.nbits <= kLongNfaMaxBits) {
+        p.kind = LongStringPlan::kLongNfa;
+        p.scratch_bytes = dev::long_nfa_scratch_bytes(t->nfa, nbytes, &p.chunk, &p.nchunks);
     }
-    if (re->engine == RRX_ENGINE_NFA && nbytes >= kLongStringBytes && t->nfa.nbits <= kLongNfaMaxBits) {
-        uint32_t chunk = 0, nchunks = 0;
-        (void)dev::long_nfa_scratch_bytes(t->nfa, nbytes, &chunk, &nchunks);
-        int le = dev::match_long_nfa(t->nfa, d_bytes, nbytes, chunk, nchunks, scratch, d_accept, st);
-        if (le) return hip_fail((hipError_t)le, "match_long_nfa launch");
-        return RRX_OK;
+    return p;
+}
+static int match_string_with(const rrx_regex *re, int device, const DeviceTables *t, const LongStringPlan &plan, const uint8_t *d_bytes, size_t nbytes,
+                             uint8_t *d_accept, uint8_t *scratch, hipStream_t st) {
+    if (plan.kind == LongStringPlan::kLongDfa) {
+        return launched(dev::match_long_dfa(t->dfa, d_bytes, nbytes, plan.chunk, scratch, d_accept, st), "match_long launch");
+    }
+    if (plan.kind == LongStringPlan::kLongNfa) {
+        return launched(dev::match_long_nfa(t->nfa, d_bytes, nbytes, plan.chunk, plan.nchunks, scratch, d_accept, st), "match_long_nfa launch");
     }
     const uint64_t off[2] = {0, nbytes};
     uint64_t *d_off = reinterpret_cast<uint64_t *>(scratch);
@@ -1424,18 +1252,6 @@ static int match_string_with(const rrx_regex *re, int device, const DeviceTables
     if (e == hipSuccess) e = hipStreamSynchronize(st);                    // `off` leaves scope
     if (e != hipSuccess) return hip_fail(e, "extent upload");
     return rrx_match_extents(re, device, d_bytes, d_off, 1, 0, d_accept, st);
-}
-static size_t match_string_scratch_bytes(const rrx_regex *re, const DeviceTables *t, size_t nbytes) {
-    const bool table_engine = re->engine == RRX_ENGINE_DFA;
-    if (table_engine && nbytes >= kLongStringBytesTable && t->dfa.nstates && t->dfa.nstates <= dev::kLongMaxStates) {
-        uint32_t chunk = 0;
-        return dev::long_scratch_bytes(t->dfa.nstates, nbytes, &chunk);
-    }
-    if (re->engine == RRX_ENGINE_NFA && nbytes >= kLongStringBytes && t->nfa.nbits <= kLongNfaMaxBits) {
-        uint32_t chunk = 0, nchunks = 0;
-        return dev::long_nfa_scratch_bytes(t->nfa, nbytes, &chunk, &nchunks);
-    }
-    return 2 * sizeof(uint64_t);
 }
 
 int rrx_match_string(const rrx_regex *re, int device, const void *d_bytes, size_t nbytes, uint8_t *d_accept, void *stream) {
@@ -1446,9 +1262,10 @@ int rrx_match_string(const rrx_regex *re, int device, const void *d_bytes, size_
     HIP_TRY(hipSetDevice(device));
     std::lock_guard<std::mutex> lock(re->scratch_mu);
     void *scratch = nullptr;
-    rc = re->scratch_for(device, match_string_scratch_bytes(re, t, nbytes), &scratch);
+    const LongStringPlan plan = long_string_plan(re, t, nbytes);
+    rc = re->scratch_for(device, plan.scratch_bytes, &scratch);
     if (rc) return rc;
-    rc = match_string_with(re, device, t, static_cast<const uint8_t *>(d_bytes), nbytes, d_accept, static_cast<uint8_t *>(scratch),
+    rc = match_string_with(re, device, t, plan, static_cast<const uint8_t *>(d_bytes), nbytes, d_accept, static_cast<uint8_t *>(scratch),
                            static_cast<hipStream_t>(stream));
     const hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(stream));      // the scratch is reused by the next call
     if (!rc && e != hipSuccess) rc = hip_fail(e, "match_string");
@@ -1556,12 +1373,13 @@ int rrx_match_cstr(const rrx_regex *re, int device, const char *text, int *accep
     std::lock_guard<std::mutex> lock(re->scratch_mu);
     const size_t acc_at = (n + 15) & ~(size_t)15, scratch_at = acc_at + 16;
     void *buf = nullptr;
-    rc = re->scratch_for(device, scratch_at + match_string_scratch_bytes(re, t, n), &buf);
+    const LongStringPlan plan = long_string_plan(re, t, n);
+    rc = re->scratch_for(device, scratch_at + plan.scratch_bytes, &buf);
     if (rc) return rc;
     uint8_t *d = static_cast<uint8_t *>(buf);
     hipError_t e = n ? hipMemcpy(d, text, n, hipMemcpyHostToDevice) : hipSuccess;
     if (e != hipSuccess) return hip_fail(e, "text upload");
-    rc = match_string_with(re, device, t, d, n, d + acc_at, d + scratch_at, nullptr);
+    rc = match_string_with(re, device, t, plan, d, n, d + acc_at, d + scratch_at, nullptr);
     uint8_t a = 0;
     if (!rc) { e = hipMemcpy(&a, d + acc_at, 1, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hip_fail(e, "accept readback"); }
     *accepted = a;

@@ -1,4 +1,4 @@
-// device.hpp — host-visible interface of the HIP kernels (kernels.hip).  gfx950 only.
+// device.hpp — host-visible interface of the HIP kernels (kernels_*.hip).  gfx950 only.
 #pragma once
 #include <cstddef>
 #include <cstdint>

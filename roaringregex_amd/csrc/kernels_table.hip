@@ -1439,21 +1439,24 @@ uint32_t flush_mask_for(size_t nbytes, size_t nlines) {
     while (slots < 32 && (size_t)slots * 2 * 16 <= avg * 16) slots *= 2;      // (measured: profiles/r04_flush_period_ab.txt)
     return slots - 1;
 }
-int match_stripes_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                       size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask) {
+// The launch of every stride-2 stripe kernel: `kernel(p, bytes, nbytes, stripe, rest...)` on workgroups of kThreads lanes that take
+// `stripes_per_wg` stripes each; a table beyond the kernels' LDS region is refused.
+template <class... Params, class... Rest>
+static int launch_dfa2(void (*kernel)(Params...), const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, size_t nstripes,
+                       size_t stripes_per_wg, void *stream, Rest... rest) {
     if (!nstripes) return 0;
     if (Dfa2::lds_bytes(p) > kDfa2MaxTable) return (int)hipErrorInvalidValue;
-    size_t blocks = (nstripes + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(match_stripes2_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, p, bytes, nbytes, stripe, stripe_base, accept, flush_mask);
+    const size_t blocks = (nstripes + stripes_per_wg - 1) / stripes_per_wg;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, p, bytes, nbytes, stripe, rest...);
     return (int)hipGetLastError();
+}
+int match_stripes_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                       size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask) {
+    return launch_dfa2(match_stripes2_kernel, p, bytes, nbytes, stripe, nstripes, kThreads, stream, stripe_base, accept, flush_mask);
 }
 int match_stripes_dfa2_clean(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
                              size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask) {
-    if (!nstripes) return 0;
-    if (Dfa2::lds_bytes(p) > kDfa2MaxTable) return (int)hipErrorInvalidValue;
-    size_t blocks = (nstripes + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(match_stripes2_clean_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, p, bytes, nbytes, stripe, stripe_base, accept, flush_mask);
-    return (int)hipGetLastError();
+    return launch_dfa2(match_stripes2_clean_kernel, p, bytes, nbytes, stripe, nstripes, kThreads, stream, stripe_base, accept, flush_mask);
 }
 // popcount of the first `nlines` bits of a result bitmap (bits of the last word beyond them ignored), added to *count, which the
 // caller has zeroed on the same stream: a sum per lane, per wave (DPP/shuffle reduction), one atomic per wave
@@ -1541,11 +1544,7 @@ __global__ __launch_bounds__(256) void split_two_bit_kernel(const uint32_t *__re
 }
 int match_stripes_dfa2_two_bit(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
                                size_t nstripes, uint32_t *wide_bits, void *stream) {
-    if (!nstripes) return 0;
-    if (Dfa2::lds_bytes(p) > kDfa2MaxTable) return (int)hipErrorInvalidValue;
-    size_t blocks = (nstripes + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(match_stripes2_two_bit_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, p, bytes, nbytes, stripe, stripe_base, wide_bits);
-    return (int)hipGetLastError();
+    return launch_dfa2(match_stripes2_two_bit_kernel, p, bytes, nbytes, stripe, nstripes, kThreads, stream, stripe_base, wide_bits);
 }
 int split_two_bit(const uint32_t *wide, size_t nlines, uint32_t *accept_bits, uint32_t *escaped_bits, unsigned long long *escaped_total, uint64_t *list,
                   size_t cap, void *stream) {
@@ -1559,11 +1558,9 @@ int split_two_bit(const uint32_t *wide, size_t nlines, uint32_t *accept_bits, ui
 }
 int match_units_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
                      size_t nstripes, uint32_t *accept, uint32_t units_per_wg, void *stream) {
-    if (!nstripes) return 0;
-    if (Dfa2::lds_bytes(p) > kDfa2MaxTable || !units_per_wg) return (int)hipErrorInvalidValue;
-    const size_t units = (nstripes + 63) / 64, blocks = (units + units_per_wg - 1) / units_per_wg;
-    hipLaunchKernelGGL(match_units2_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, p, bytes, nbytes, stripe, stripe_base, accept, units_per_wg);
-    return (int)hipGetLastError();
+    if (nstripes && !units_per_wg) return (int)hipErrorInvalidValue;
+    // (units of 64 stripes, units_per_wg of them per workgroup)
+    return launch_dfa2(match_units2_kernel, p, bytes, nbytes, stripe, nstripes, (size_t)64 * units_per_wg, stream, stripe_base, accept, units_per_wg);
 }
 // byte-stride table engines in one-pass mode (bytes >= 0x80 are always clamped: nobody has looked at the corpus yet)
 int match_onepass_dfa(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, size_t nstripes, uint32_t *counts,
@@ -1577,11 +1574,7 @@ size_t onepass_slab_words(size_t nstripes, uint32_t stripe) {
 }
 int match_onepass_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, size_t nstripes, uint32_t *counts,
                        uint32_t *slabs, void *stream) {
-    if (!nstripes) return 0;
-    if (Dfa2::lds_bytes(p) > kDfa2MaxTable) return (int)hipErrorInvalidValue;
-    size_t blocks = (nstripes + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(match_stripes2_onepass_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, p, bytes, nbytes, stripe, counts, slabs);
-    return (int)hipGetLastError();
+    return launch_dfa2(match_stripes2_onepass_kernel, p, bytes, nbytes, stripe, nstripes, kThreads, stream, counts, slabs);
 }
 int compact_streams(const uint32_t *counts, const uint64_t *stripe_base, size_t nstripes, uint32_t stripe, const uint32_t *slabs,
                     uint32_t *accept_bits, size_t cap_words, void *stream) {

@@ -1,0 +1,81 @@
+// plan.hpp — the decisions between a pattern and its device images (host only: no HIP): which programs are lowered for a
+// requested engine and which engine AUTO ends on, which forms of a DFA table fit the device, how the search tables are planned,
+// and how a program is dumped as words (rrx_program_words).  The fit rules are stated here or nowhere: abi.cpp and the
+// sanitizer driver (tests/cpp/host_pipeline_driver.cpp) both call them.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "device.hpp"
+#include "lower.hpp"
+#include "pack.hpp"
+
+namespace rrx {
+
+constexpr uint32_t kMaxSubsetStates = 16384;   // subset construction is abandoned beyond this
+
+// The stride-2 size rule: the table (rows of `ncols | 1` entries) fits the LDS region next to the pair table.
+size_t dfa2_table_bytes(const Dfa2Program &d);
+bool dfa2_fits(const Dfa2Program &d);
+// The stride-2 form of `d` (items: lower_dfa2's items form) if there is one that fits: at most 4096 states, 1024 pair columns.
+bool lower_dfa2_that_fits(const DfaProgram &d, Dfa2Program &out, bool items = false);
+
+// Which forms of a line table fit the device (the driver packs every one that does; decide() picks among them)
+bool wide_fits(const DfaProgram &d);           // byte-indexed rows
+bool classed_fits(const DfaProgram &d);        // class-indexed rows in LDS
+bool global_fits(const DfaProgram &d);         // class-indexed rows in global memory
+
+// A DFA as the batch kernels run it: the byte-stride line table in one of its forms and, where it fits, the stride-2 table.
+struct LineTables {
+    DfaProgram dfa;
+    Dfa2Program dfa2;
+    bool has_dfa2 = false;
+    bool wide = false;           // byte-indexed rows (<= kWideMaxStates states) or class-indexed rows
+    bool global = false;         // class-indexed table too large for LDS, kept in global memory
+    // The forms of `dfa` under the requested RRX_ENGINE_*; false: no table (the global form holds 2^24 entries).
+    bool decide(int requested_engine);
+    const char *name() const;    // (stride-2: the byte-stride table still serves corpora with bytes >= 0x80)
+    // rows / cols: the order of the stride-2 table in LDS (empty: as numbered)
+    void pack(const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, Image &img, DeviceTables &t) const;
+};
+
+// What a pattern compiles to.  `engine`: the RRX_ENGINE_* it runs on, 0 where none admits the automaton.
+struct Programs {
+    RefAutomaton ref;
+    Trimmed trimmed;
+    bool has_nfa = false, has_dfa = false;
+    NfaProgram nfa;
+    NfaProgram nfa_wave;         // up to 4096 positions, no carry groups (wave-cooperative engine)
+    bool has_wave = false;
+    NfaProgram nfa_block;        // up to 65536 positions, exception edges in CSR form (wave-resident engine)
+    bool has_block = false;
+    LineTables match;
+    int engine = 0;
+    const char *engine_name() const;
+    bool accepts_empty() const;
+};
+// Lowers what the requested RRX_ENGINE_* needs and picks the engine; throws what the front end and the lowering throw.
+void plan_engines(const std::string &pattern, int requested_engine, Programs &out);
+
+// The search tables: the forward "anything, then the pattern" DFA and the reverse DFA, the line product table (nrows = 0: not
+// built), its stride-2 form, what the stripe-wise kernel runs, and that kernel's layout of it without the pointers.
+struct SearchPlan {
+    DfaProgram fwd, rev;
+    SearchLineProgram line;
+    SearchLine2Program line2;
+    dev::SearchChunkDevice layout;
+    bool nullable = false;       // the pattern accepts the empty string: every offset is a match, no table (empty_matches)
+};
+// `lds_bytes`: what the kernel needs of the LDS for a layout (dev::search_chunks_lds_bytes; the arithmetic lives with the kernel).
+// false: the tables do not fit the device; fwd / rev are built all the same where they determinise (rrx_program_words).
+using SearchLdsBytes = size_t (*)(const dev::SearchChunkDevice &);
+bool plan_search(const Reduced &red, bool use_anchored, bool accepts_empty, SearchLdsBytes lds_bytes, SearchPlan &out);
+
+// rrx_program_words: the word layouts that tests/program_replay.py reads.
+void append_words(std::vector<uint32_t> &w, const NfaProgram &p, bool csr);                   // csr: xoff / xtgt in the place of X
+void append_words(std::vector<uint32_t> &w, const DfaProgram &d, bool escaped = false);       // escaped: then the escaped flag per state
+void append_words(std::vector<uint32_t> &w, const Dfa2Program &d, bool pair_dim = false);     // pair_dim: a fifth header word
+void append_words(std::vector<uint32_t> &w, const SearchLineProgram &d, const DfaProgram &fwd);
+void append_words(std::vector<uint32_t> &w, const SearchLine2Program &d, const dev::SearchChunkDevice &layout);
+
+}  // namespace rrx

@@ -1,11 +1,12 @@
 // host_pipeline_driver.cpp — runs the host compile pipeline (pattern -> reference-numbered automaton -> trim ->
 // reduce -> NFA / DFA / stride-2 programs) over the patterns given on stdin, one per line.  Built by
 // tests/test_lowering.py with -fsanitize=address,undefined (sanitizers run on the CPU build only) from
-// csrc/frontend.cpp + csrc/lower.cpp + csrc/pack.cpp: no HIP involved.  Prints one summary line per pattern.
+// csrc/frontend.cpp + csrc/lower.cpp + csrc/pack.cpp + csrc/plan.cpp: no HIP involved.  Prints one summary line per pattern.
 //
-// Every device image whose preconditions the programs meet is packed (csrc/pack.hpp), copied, bound to the copy and decoded
-// back here - independently of the packer - against the program it was packed from.  A mismatch aborts; the line before
-// "done" counts the images checked per kind.
+// Every device image whose preconditions the programs meet - by the library's own fit rules (csrc/plan.hpp) - is packed
+// (csrc/pack.hpp), copied, bound to the copy and decoded back here - independently of the packer - against the program it was
+// packed from; so is the image of the engine and table forms that RRX_ENGINE_AUTO chooses for the pattern ("chosen").  A
+// mismatch aborts; the line before "done" counts the images checked per kind.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +18,8 @@
 #include "frontend.hpp"
 #include "lower.hpp"
 #include "pack.hpp"
+#include "plan.hpp"
+#include "../../include/rrx.h"
 
 using namespace rrx;
 
@@ -27,7 +30,7 @@ namespace {
         if (!(cond)) { std::fprintf(stderr, "image check failed: %s (line %d)\n", #cond, __LINE__); std::abort(); } \
     } while (0)
 
-struct Counts { size_t line = 0, stride2 = 0, items = 0, search = 0, lane = 0, group = 0, wave = 0, sparse = 0; } g_n;
+struct Counts { size_t line = 0, stride2 = 0, items = 0, search = 0, lane = 0, group = 0, wave = 0, sparse = 0, chosen = 0; } g_n;
 
 // the image as the device would hold it: a copy of its bytes, the descriptors bound to the copy
 struct Copy {
@@ -38,12 +41,19 @@ struct Copy {
 
 bool bit(const std::vector<uint32_t> &v, uint32_t b) { return (v[b >> 5] >> (b & 31)) & 1u; }
 
+void decode_dfa2(const Dfa2Program &p, const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, uint32_t p_region, const dev::Dfa2Device &d,
+                 const Copy &cp);
+
+// The tables of a table engine in the forms `lt` says, the stride-2 table in the order rows / cols.
 // lane l reads copy l % R of every entry: all R copies of entry i (at dword i * R + k) must agree, offsets + 4 k
-void check_line(const DfaProgram &dfa, bool wide, bool global) {
+void check_line(const LineTables &lt, const std::vector<uint32_t> &rows = {}, const std::vector<uint32_t> &cols = {}) {
+    const DfaProgram &dfa = lt.dfa;
+    const bool wide = lt.wide, global = lt.global;
     Image img;
     DeviceTables t;
-    pack_dfa_tables(dfa, wide, global, nullptr, {}, {}, img, t);
+    lt.pack(rows, cols, img, t);
     Copy cp(img);
+    if (lt.has_dfa2) decode_dfa2(lt.dfa2, rows, cols, 0, t.dfa2, cp);
     const dev::LineDfaDevice &L = t.line;
     const uint32_t R = 1u << L.rep_log2, S = L.stride / R, K = dfa.ncls;
     CHECK(L.wide == (wide ? 1u : 0u) && L.in_global == (global ? 1u : 0u) && L.nrows == dfa.nstates && (!global || R == 1));
@@ -66,23 +76,25 @@ void check_line(const DfaProgram &dfa, bool wide, bool global) {
         }
     g_n.line++;
 }
+void check_line(const DfaProgram &dfa, bool wide, bool global) {
+    LineTables lt;
+    lt.dfa = dfa; lt.wide = wide; lt.global = global;
+    check_line(lt);
+}
 
 // a stride-2 table in the order rows / cols (empty: as numbered): every (state, pair) through P and the slots gives next2
-void check_dfa2(const Dfa2Program &p, const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, uint32_t p_region) {
-    Image img;
-    dev::Dfa2Device d;
-    CHECK(pack_dfa2(p, rows, cols, img, d, p_region));
-    Copy cp(img);
+void decode_dfa2(const Dfa2Program &p, const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, uint32_t p_region, const dev::Dfa2Device &d,
+                 const Copy &cp) {
     const bool ordered = !rows.empty();
     auto rs = [&](uint32_t s) { return ordered ? rows[s] : s; };
     auto cs = [&](uint32_t c) { return ordered ? cols[c] : c; };
     const uint32_t R = 1u << d.rep_log2, dim = p.pair_dim;
     CHECK(d.nrows == p.nstates && d.stride == (p.ncols | 1u) * R && d.start_off == rs(p.start) * d.stride * 4);
-    CHECK(cp.at(d.P) == 0 && cp.at(d.T2) == (p_region ? p_region : ((dim * dev::kDfa2PStride * 2 + 15) & ~15u)));
+    CHECK(cp.at(d.P) % 16 == 0 && cp.at(d.T2) - cp.at(d.P) == (p_region ? p_region : ((dim * dev::kDfa2PStride * 2 + 15) & ~15u)));
     for (uint32_t c1 = 0; c1 < dim; c1++)
         for (uint32_t c2 = 0; c2 < dev::kDfa2PStride; c2++)
             CHECK(d.P[c1 * dev::kDfa2PStride + c2] == (c2 < dim ? cs(p.pair_col[c1 * dim + c2]) * 4 * R : 0u));
-    for (size_t b = dim * dev::kDfa2PStride * 2; b < cp.at(d.T2); b++) CHECK(cp.bytes[b] == 0);     // (the items form's P region)
+    for (size_t b = cp.at(d.P) + dim * dev::kDfa2PStride * 2; b < cp.at(d.T2); b++) CHECK(cp.bytes[b] == 0);     // (the items form's P region)
     for (uint32_t s = 0; s < p.nstates; s++)
         for (uint32_t c = 0; c < p.ncols; c++) {
             const uint32_t v = p.next2[(size_t)s * p.ncols + c];
@@ -92,6 +104,14 @@ void check_dfa2(const Dfa2Program &p, const std::vector<uint32_t> &rows, const s
             }
         }
     g_n.stride2++;
+}
+void check_dfa2(const Dfa2Program &p, const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, uint32_t p_region) {
+    Image img;
+    dev::Dfa2Device d;
+    CHECK(pack_dfa2(p, rows, cols, img, d, p_region));
+    Copy cp(img);
+    CHECK(cp.at(d.P) == 0);
+    decode_dfa2(p, rows, cols, p_region, d, cp);
 }
 
 // a seeded random order of the table's rows (state 0 keeps slot 0) and columns
@@ -123,9 +143,8 @@ void check_items(const DfaProgram &dfa) {
     g_n.items++;
 }
 
-void check_search(const SearchLine2Program &s2, const DfaProgram &fwd, const DfaProgram &rev, bool in_global) {
-    const dev::SearchChunkDevice layout = search_chunk_layout(s2, fwd, rev, in_global);
-    if (!in_global && (s2.ncols > 127 || layout.base_row + s2.nrows > 4096)) return;
+void check_search(const SearchLine2Program &s2, const DfaProgram &fwd, const DfaProgram &rev, const dev::SearchChunkDevice &layout) {
+    const bool in_global = layout.in_global != 0;
     Image img;
     dev::SearchChunkDevice d;
     pack_search(s2, fwd, rev, layout, img, d);
@@ -249,36 +268,50 @@ void check_wave(const NfaProgram &p, const Trimmed &t, bool sparse) {
     (sparse ? g_n.sparse : g_n.wave)++;
 }
 
+// The LDS the search kernel needs for a layout is the kernel's own arithmetic (kernels_search.hip); here every layout that
+// pack_search can lay out passes (row offsets of the global form: 28 bits), so that plan_search hands out the LDS form wherever
+// the table admits it and the global form elsewhere.
+size_t any_packable_layout(const dev::SearchChunkDevice &c) {
+    return c.in_global && (size_t)c.nrows * c.ncols2 * 4 >= ((size_t)1 << 28) ? dev::kSearchChunkLdsBudget + 1 : 0;
+}
+
 void check_images(const Trimmed &t, const Reduced &r, const NfaProgram *nfa, const NfaProgram *wave, const DfaProgram *dfa,
                   const Dfa2Program *dfa2, std::mt19937 &rng) {
     if (nfa) check_lane(*nfa);
     if (wave) { check_group(*wave, t); check_wave(*wave, t, false); check_wave(*wave, t, true); }
     if (dfa) {
-        const size_t classed = (size_t)dfa->nstates * (dfa->ncls + 2);
-        if (dfa->nstates <= dev::kWideMaxStates) check_line(*dfa, true, false);
-        if (classed <= dev::kClassedMaxEntries) check_line(*dfa, false, false);
-        if (classed < ((size_t)1 << 24)) check_line(*dfa, false, true);
+        if (wide_fits(*dfa)) check_line(*dfa, true, false);
+        if (classed_fits(*dfa)) check_line(*dfa, false, false);
+        if (global_fits(*dfa)) check_line(*dfa, false, true);
         check_items(*dfa);
         Dfa2Program items;
-        if (dfa2 && lower_dfa2(*dfa, 1024, items, /*items=*/true) && (size_t)items.nstates * (items.ncols | 1u) * 4 <= dev::kDfa2MaxTable)
-            check_dfa2(items, {}, {}, dev::kDfa2PItemsBytes);
+        if (dfa2 && lower_dfa2_that_fits(*dfa, items, /*items=*/true)) check_dfa2(items, {}, {}, dev::kDfa2PItemsBytes);
     }
-    if (dfa2 && (size_t)dfa2->nstates * (dfa2->ncols | 1u) * 4 <= dev::kDfa2MaxTable) {
+    if (dfa2 && dfa2_fits(*dfa2)) {
         std::vector<uint32_t> rows, cols;
         check_dfa2(*dfa2, rows, cols, 0);
         random_order(*dfa2, rng, rows, cols);
         check_dfa2(*dfa2, rows, cols, 0);
     }
-    DfaProgram fwd, rev, anchored;
-    if (!search_dfas(r, 16384, fwd, rev) || fwd.ncls >= 128) return;
-    SearchLineProgram line;
-    if (!(lower_dfa(r, 16384, anchored) && lower_search_line(fwd, &anchored, 65534, line)) && !lower_search_line(fwd, nullptr, 65534, line)) return;
-    uint32_t column[256];
-    for (int c = 0; c < 256; c++) column[c] = c == '\n' ? line.ncols - 1 : fwd.cls[c];
-    SearchLine2Program s2;
-    if (!lower_search_line2(line, column, 16383, s2)) return;
-    check_search(s2, fwd, rev, false);
-    if ((size_t)s2.nrows * s2.ncols * 4 < ((size_t)1 << 28)) check_search(s2, fwd, rev, true);      // (row offsets of the global form: 28 bits)
+    // the search tables as the library plans them, with and without the anchored table, in both layouts
+    for (const bool anchored : {true, false}) {
+        SearchPlan s;
+        (void)plan_search(r, anchored, /*accepts_empty=*/false, any_packable_layout, s);
+        if (!s.layout.nrows) continue;
+        check_search(s.line2, s.fwd, s.rev, s.layout);
+        const dev::SearchChunkDevice global = search_chunk_layout(s.line2, s.fwd, s.rev, /*in_global=*/true);
+        if (!s.layout.in_global && any_packable_layout(global) <= dev::kSearchChunkLdsBudget) check_search(s.line2, s.fwd, s.rev, global);
+    }
+}
+
+// what RRX_ENGINE_AUTO runs the pattern on: the image of that engine, for a table engine in exactly the forms it chose
+void check_chosen(const Programs &p) {
+    if (p.engine == RRX_ENGINE_DFA) check_line(p.match);
+    else if (p.engine == RRX_ENGINE_NFA) check_lane(p.nfa);
+    else if (p.engine == RRX_ENGINE_NFA_WAVE) check_group(p.nfa_wave, p.trimmed);
+    else if (p.engine == RRX_ENGINE_NFA_BLOCK) check_wave(p.nfa_block, p.trimmed, false);
+    else return;
+    g_n.chosen++;
 }
 
 }  // namespace
@@ -290,8 +323,9 @@ int main() {
     while (std::getline(std::cin, p)) {
         n++;
         try {
-            rrx::RefAutomaton a = rrx::build_reference_automaton(p.c_str());
-            rrx::Trimmed t = rrx::trim(a);
+            rrx::Programs chosen;
+            rrx::plan_engines(p, RRX_ENGINE_AUTO, chosen);
+            const rrx::Trimmed &t = chosen.trimmed;
             rrx::Reduced r = rrx::reduce(t);
             rrx::NfaProgram nfa, wave;
             rrx::DfaProgram dfa;
@@ -300,17 +334,18 @@ int main() {
             const bool has_wave = rrx::lower_nfa(r, 4096, wave, false);
             const bool has_dfa = rrx::lower_dfa(r, 16384, dfa);
             const bool has_dfa2 = has_dfa && rrx::lower_dfa2(dfa, 1024, dfa2);
-            std::printf("%zu ok useful %u nodes %zu nfa %d/%u wave %d dfa %d/%u dfa2 %d/%u\n", n, t.n, r.nodes.size(), (int)has_nfa,
+            std::printf("%zu ok useful %u nodes %zu nfa %d/%u wave %d dfa %d/%u dfa2 %d/%u engine %s\n", n, t.n, r.nodes.size(), (int)has_nfa,
                         has_nfa ? nfa.nbits : 0u, (int)has_wave, (int)has_dfa, has_dfa ? dfa.nstates : 0u, (int)has_dfa2,
-                        has_dfa2 ? dfa2.ncols : 0u);
+                        has_dfa2 ? dfa2.ncols : 0u, chosen.engine ? chosen.engine_name() : "none");
             check_images(t, r, has_nfa ? &nfa : nullptr, has_wave ? &wave : nullptr, has_dfa ? &dfa : nullptr, has_dfa2 ? &dfa2 : nullptr, rng);
+            check_chosen(chosen);
         } catch (const rrx::PatternError &e) {
             rejected++;
             std::printf("%zu rejected %s\n", n, e.what());
         }
     }
-    std::printf("packed line %zu stride2 %zu items %zu search %zu lane %zu group %zu wave %zu sparse %zu\n", g_n.line, g_n.stride2, g_n.items,
-                g_n.search, g_n.lane, g_n.group, g_n.wave, g_n.sparse);
+    std::printf("packed line %zu stride2 %zu items %zu search %zu lane %zu group %zu wave %zu sparse %zu chosen %zu\n", g_n.line, g_n.stride2, g_n.items,
+                g_n.search, g_n.lane, g_n.group, g_n.wave, g_n.sparse, g_n.chosen);
     std::printf("done %zu rejected %zu\n", n, rejected);
     return 0;
 }

@@ -355,7 +355,7 @@ def test_host_pipeline_is_clean_under_asan_and_ubsan(tmp_path):
     exe = str(tmp_path / "host_pipeline_asan")
     subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc,
                            os.path.join(root, "tests", "cpp", "host_pipeline_driver.cpp"), os.path.join(csrc, "frontend.cpp"),
-                           os.path.join(csrc, "lower.cpp"), os.path.join(csrc, "pack.cpp"), "-o", exe])
+                           os.path.join(csrc, "lower.cpp"), os.path.join(csrc, "pack.cpp"), os.path.join(csrc, "plan.cpp"), "-o", exe])
     rng = random.Random(2024)
     pats = [k["pattern"] for k in KAT["kat"]] + [b["pattern"] for b in KAT["big_states"]]
     pats += [EMAIL, U2, "a{1,300}", "(a|b)*a(a|b){12}", "(a|b)*a(a|b){40}", K1000_CONTAINS]
@@ -369,14 +369,49 @@ def test_host_pipeline_is_clean_under_asan_and_ubsan(tmp_path):
     # every device image form was packed, bound to a host copy and decoded back against its program at least once
     packed = lines[-2].split()
     assert packed[0] == "packed" and all(int(v) >= 1 for v in packed[2::2]), lines[-2]
-    # the sanitized build must agree with the shipped library on what compiles
+    # the sanitized build must agree with the shipped library on what compiles, and on the engine and table form AUTO chooses
     for p, line in zip(pats, lines):
+        engine_name = "none"
         try:
-            rr.RRegex(p)
+            engine_name = rr.RRegex(p).engine_name
             ok = True
         except rr.RRegexError as e:
             ok = "too large" in str(e)               # compiled, but no device engine admits it
         assert ok == (" ok " in line), (p[:60], line)
+        if ok:
+            assert line.rsplit(" engine ", 1)[1] == engine_name, (p[:60], line, engine_name)
+
+
+def test_table_forms_are_the_recorded_ones():
+    """Which engine a pattern gets and which forms its match table and its contains table take (csrc/plan.cpp) are pinned, for
+    the known-answer patterns and the fixed patterns under AUTO and every table engine, to tests/golden/table_forms.json
+    (make_table_forms.py): a change of a fit rule or of AUTO's order shows here, without a GPU."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "table_forms.json")) as f:
+        golden = json.load(f)
+    recorded = {e["pattern"] for e in golden["forms"]}
+    for p in [k["pattern"] for k in KAT["kat"]] + [b["pattern"] for b in KAT["big_states"]] + [EMAIL, U2, K1000, K1000_CONTAINS]:
+        assert p in recorded, p[:60]
+    assert {"ENGINE_AUTO", "ENGINE_DFA", "ENGINE_DFA_GLOBAL", "ENGINE_DFA2"} <= set(golden["engines"])
+    names = set()
+    for entry in golden["forms"]:
+        p = entry["pattern"]
+        for engine, want in zip(golden["engines"], entry["by_engine"]):
+            try:
+                r = rr.RRegex(p, getattr(rr, engine))
+            except rr.RRegexError:
+                assert want is None, (p[:60], engine, want)
+                continue
+            try:
+                contains = r.contains_engine_name
+            except rr.RRegexError:
+                contains = None
+            assert [r.engine, r.engine_name, contains, r.contains_states] == want, (p[:60], engine, want)
+            names.update((("match", r.engine_name), ("contains", contains)))
+    # the fixture reaches every form of both tables
+    for form in ("dfa-stride2-table", "dfa-wide-table", "dfa-classed-table", "dfa-global-table"):
+        assert ("match", form) in names and ("contains", form) in names, form
 
 
 def test_search_tables_find_the_earliest_ending_leftmost_match():
