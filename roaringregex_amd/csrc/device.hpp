@@ -6,6 +6,7 @@
 namespace rrx {
 namespace dev {
 
+// ---- shared geometry and structs --------------------------------------------------------------------------------
 // Geometry of the batch kernel: lane g of the grid owns the lines that START in the contiguous stripe
 // bytes [g*stripe, (g+1)*stripe) and follows its last line past the stripe end.  Every lane streams its
 // stripe straight from HBM into registers, kRound bytes (8 x 16 B) per round.
@@ -100,14 +101,6 @@ struct WaveNfaDevice {
     const uint32_t *Bcls = nullptr;              //   [ncls][64 * WL], class 0 = no position
     const uint8_t *cls = nullptr;                //   [256] byte -> class ('\n' an ordinary byte)
 };
-uint32_t wave_words_per_lane(uint32_t words);    // the instantiated WL that holds `words` 32-bit words (0: too many)
-// The SPARSE form of the same engine (kernels_wave.hip: SparseNfa): WL then counts ROWS of 2048 positions and masks / Bbyte are
-// laid out by rows - [3][WL][64] and [257][WL][64]: word w of the set = row w / 64, lane w % 64.
-uint32_t sparse_rows(uint32_t words);            // the instantiated row count that holds `words` 32-bit words (0: too many)
-int match_stripes_sparse_nfa(const WaveNfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                             size_t nstripes, uint32_t *accept_bits, void *stream);
-int match_extents_sparse_nfa(const WaveNfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
-                             uint8_t *accept, void *stream);
 
 // Plain DFA (extents kernel: '\n' is an ordinary byte).
 struct DfaDevice {
@@ -157,18 +150,22 @@ constexpr uint32_t kDfa2RegionBytes = 46 * 1024;
 constexpr uint32_t kDfa2MaxTable = kDfa2RegionBytes - 4 * 1024;       // a table this large leaves a 4 KiB window
 constexpr uint32_t kDfa2TableBudget = 30 * 1024;                      // T2 with its copies
 
-// explicit items with separators (trim 1) on the stride-2 table of their own (lower_dfa2's items form; P of kDfa2PItemsBytes):
-// the arguments of items_match below
-int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, uint8_t *accept, void *stream,
-                 const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
+// ---- launchers --------------------------------------------------------------------------------------------------
+// All launchers are asynchronous on `stream` and return a hipError_t value (0 = success).
+// accept_bits: bitmap, bit i = line i accepted; must be zeroed before the launch (the launchers do not)
+
+// ---- table engines, batch match path: kernels_table.hip
+int match_stripes_dfa(const LineDfaDevice &p, bool clamp_high, const uint8_t *bytes, size_t nbytes, uint32_t stripe,
+                      const uint64_t *stripe_base, size_t nstripes, uint32_t *accept_bits, void *stream);
 uint32_t flush_mask_for(size_t nbytes, size_t nlines);      // the stride-2 kernel's common flush period from the mean line length
 int match_stripes_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
                        size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask = 31u);
 // the same over text that may hold bytes >= 0x80: they are stepped as 0x00 (rrx_contains_corpus, where both are ordinary text of one class)
 int match_stripes_dfa2_clean(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
                              size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask = 31u);
-// *count (zeroed here, on `stream`) = set bits among the first `nlines` bits of a result bitmap
-int bitmap_count(const uint32_t *bits, size_t nlines, unsigned long long *count, void *stream);
+// the same, stripes handed out in units of 64 inside the workgroup (units_per_wg of them per workgroup of 16 waves)
+int match_units_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                     size_t nstripes, uint32_t *accept, uint32_t units_per_wg, void *stream);
 // The sampled-table engine: the stride-2 kernel on a table with an ESCAPE state writes two bits per line into
 // `wide_bits` (2 x the accept bitmap, zeroed by the caller); split_two_bit takes them apart (every word of both outputs is
 // written) and counts the escaped lines; recheck_escaped_nfa lets the exact NFA lane engine decide those and ORs its accepts in.
@@ -179,12 +176,6 @@ int match_stripes_dfa2_two_bit(const Dfa2Device &p, const uint8_t *bytes, size_t
 // needed ends at once.)
 int split_two_bit(const uint32_t *wide, size_t nlines, uint32_t *accept_bits, uint32_t *escaped_bits, unsigned long long *escaped_total, uint64_t *list,
                   size_t cap, void *stream);
-int recheck_escaped_nfa(const NfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base, size_t nstripes,
-                        const uint32_t *escaped_bits, size_t nlines, const uint64_t *list, const unsigned long long *escaped_total, size_t cap,
-                        uint32_t *accept_bits, void *stream);
-// the same, stripes handed out in units of 64 inside the workgroup (units_per_wg of them per workgroup of 16 waves)
-int match_units_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                     size_t nstripes, uint32_t *accept, uint32_t units_per_wg, void *stream);
 
 // One-pass mode (no line index yet): the stride-2 kernel writes counts[g] ('\n' per stripe, with flags) and every lane's
 // verdict stream into `slabs` (onepass_slab_words() words); after scan_counts, compact_streams moves the streams to their
@@ -195,35 +186,60 @@ int match_onepass_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes,
                        uint32_t *slabs, void *stream);
 int match_onepass_dfa(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, size_t nstripes, uint32_t *counts,
                       uint32_t *slabs, void *stream);
-int match_onepass_nfa(const NfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, size_t nstripes, uint32_t *counts,
-                      uint32_t *slabs, void *stream);
 int compact_streams(const uint32_t *counts, const uint64_t *stripe_base, size_t nstripes, uint32_t stripe, const uint32_t *slabs,
                     uint32_t *accept_bits, size_t cap_words, void *stream);
-// mail[0] = *total without the flag bit, mail[1] = flags ? *flags : 0, mail[2] = last_byte ? *last_byte : '\n': the few words a
-// synchronous entry hands back, written into pinned device-mapped host memory by a one-lane kernel at the end of the call
-int mail_results(const uint64_t *total, const uint32_t *flags, const uint8_t *last_byte, uint64_t *mail, void *stream);
+// only_if != nullptr: the kernel does nothing unless *only_if != 0 (the fallback queued behind the stripe-wise items kernel)
+int match_extents_dfa(const DfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
+                      uint8_t *accept, void *stream, const uint32_t *only_if = nullptr);
 
-// All launchers are asynchronous on `stream` and return a hipError_t value (0 = success).
+// ---- corpus index and result bitmaps: kernels_index.hip
 int count_newlines_per_stripe(const uint8_t *bytes, size_t nbytes, uint32_t stripe, uint32_t *counts, size_t nstripes, uint32_t *flags, void *stream);
 int scan_counts(const uint32_t *counts, uint64_t *base, uint64_t *chunk_sums, size_t n, void *stream);   // base[n] = total
 size_t scan_scratch_words(size_t n);                                                                       // u64 words of chunk_sums
 int expand_bits(const uint32_t *bits, size_t nlines, uint8_t *out, void *stream);
+// *count (zeroed here, on `stream`) = set bits among the first `nlines` bits of a result bitmap
+int bitmap_count(const uint32_t *bits, size_t nlines, unsigned long long *count, void *stream);
+// mail[0] = *total without the flag bit, mail[1] = flags ? *flags : 0, mail[2] = last_byte ? *last_byte : '\n': the few words a
+// synchronous entry hands back, written into pinned device-mapped host memory by a one-lane kernel at the end of the call
+int mail_results(const uint64_t *total, const uint32_t *flags, const uint8_t *last_byte, uint64_t *mail, void *stream);
+// line_off[i] = offset of the first byte of line i (built once per corpus from the stripe index; only patterns that accept
+// the empty string need it); nlines + 1 entries are the caller's to size, entry nlines is written only when the corpus ends in '\n'.
+int build_line_offsets(const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base, size_t nstripes,
+                       uint64_t *line_off, void *stream);
+// all matches of a pattern that accepts "": [k, k) for k = 0 .. length of the line.  first == nullptr: count[i]; otherwise the
+// slots first[i], first[i] + 1, ... are filled (slots >= cap are not written)
+int empty_matches(const uint64_t *line_off, size_t nlines, uint32_t *count, const uint64_t *first, uint32_t *match_start, uint32_t *match_end,
+                  void *stream, size_t cap = ~(size_t)0);
 
-// accept_bits: bitmap, bit i = line i accepted; must be zeroed before the launch (the launchers do not)
-int match_stripes_nfa(const NfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                      size_t nstripes, uint32_t *accept_bits, void *stream);
-int match_stripes_dfa(const LineDfaDevice &p, bool clamp_high, const uint8_t *bytes, size_t nbytes, uint32_t stripe,
-                      const uint64_t *stripe_base, size_t nstripes, uint32_t *accept_bits, void *stream);
+// ---- explicit items, stripe-wise: kernels_items.hip
+// explicit items (an offsets array over one buffer) stripe-wise: see kernels_items.hip.  The table is the plain one in the
+// wide line-table format with kItemColumns columns: byte values 0..127, 128 = any byte >= 0x80, kItemEndColumn = end of item
+constexpr uint32_t kItemColumns = 131, kItemEndColumn = 129;      // (130 in use, 131 keeps the row stride odd)
+size_t items_index_bytes(size_t nbytes, size_t nitems);  // item-end bitmap, flag, stripe base
+size_t items_result_bytes(size_t nitems);                // result bitmap of one match
+// resolve_base / resolve_off (one-call form, nothing known on the host): nbytes is an UPPER BOUND the index is laid out for;
+// the kernels take the batch's start and length from the offsets; *flag != 0 afterwards = batch unfit for the stripe-wise
+// kernel (items_match then does nothing when handed the flag as skip_if)
+int items_index_build(size_t nbytes, const uint64_t *off, size_t nitems, uint32_t trim, void *index, uint32_t **flag, void *stream,
+                      const uint8_t *resolve_base = nullptr, size_t min_bytes = 0);
+// explicit items with separators (trim 1) on the stride-2 table of their own (lower_dfa2's items form; P of kDfa2PItemsBytes):
+// the arguments of items_match below
+int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, uint8_t *accept, void *stream,
+                 const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
+int items_match(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
+                uint8_t *accept, void *stream, const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
 
-int match_stripes_group_nfa(const GroupNfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                            size_t nstripes, uint32_t *accept_bits, void *stream);
-int match_extents_group_nfa(const GroupNfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
-                            uint8_t *accept, void *stream);
-int match_stripes_wave_nfa(const WaveNfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                           size_t nstripes, uint32_t *accept_bits, void *stream);
-int match_extents_wave_nfa(const WaveNfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
-                           uint8_t *accept, void *stream);
+// ---- one long string on the plain DFA: kernels_long.hip
+// One long string (regex.h:156-159 consumes it byte by byte): the string is cut into chunks, every chunk is stepped
+// from EVERY table state at once (lane = (chunk, start state); the lanes of a chunk read the same text), which yields
+// one state -> state map per chunk; maps are then composed in groups until one is left.  `scratch` holds the maps.
+constexpr uint32_t kLongMaxStates = 254;         // row offsets state * 129 stay 16-bit
+constexpr uint32_t kLongGroup = 128;             // maps composed per workgroup and level
+size_t long_scratch_bytes(uint32_t nstates, size_t nbytes, uint32_t *chunk);
+int match_long_dfa(const DfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t chunk, void *scratch, uint8_t *accept,
+                   void *stream);
 
+// ---- search: kernels_search.hip
 // Search (the reference has acceptance only).  Per line: the match [s, e) with the smallest e, then the smallest s.
 // Host tables: fwd = "any bytes, then the pattern" (never dies; accepting where some match ends), rev = the pattern read right to
 // left (accepting, walking back from a match end, where a match starts).
@@ -269,45 +285,42 @@ int search_chunks_fill(const SearchChunkDevice &p, bool clean, const uint8_t *by
 size_t search_all_scratch_bytes(size_t nchunks);
 int search_chunks_all(const SearchChunkDevice &p, bool clean, const uint8_t *bytes, size_t nbytes, const uint64_t *chunk_base, size_t nchunks, size_t nlines,
                       uint64_t *first, uint32_t *match_start, uint32_t *match_end, size_t cap, void *scratch, void *stream);
-// line_off[i] = offset of the first byte of line i (built once per corpus from the stripe index; only patterns that accept
-// the empty string need it); nlines + 1 entries are the caller's to size, entry nlines is written only when the corpus ends in '\n'.
-int build_line_offsets(const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base, size_t nstripes,
-                       uint64_t *line_off, void *stream);
-// all matches of a pattern that accepts "": [k, k) for k = 0 .. length of the line.  first == nullptr: count[i]; otherwise the
-// slots first[i], first[i] + 1, ... are filled (slots >= cap are not written)
-int empty_matches(const uint64_t *line_off, size_t nlines, uint32_t *count, const uint64_t *first, uint32_t *match_start, uint32_t *match_end,
-                  void *stream, size_t cap = ~(size_t)0);
 
-// One long string (regex.h:156-159 consumes it byte by byte): the string is cut into chunks, every chunk is stepped
-// from EVERY table state at once (lane = (chunk, start state); the lanes of a chunk read the same text), which yields
-// one state -> state map per chunk; maps are then composed in groups until one is left.  `scratch` holds the maps.
-constexpr uint32_t kLongMaxStates = 254;         // row offsets state * 129 stay 16-bit
-constexpr uint32_t kLongGroup = 128;             // maps composed per workgroup and level
-// explicit items (an offsets array over one buffer) stripe-wise: see kernels_table.hip.  The table is the plain one in the
-// wide line-table format with kItemColumns columns: byte values 0..127, 128 = any byte >= 0x80, kItemEndColumn = end of item
-constexpr uint32_t kItemColumns = 131, kItemEndColumn = 129;      // (130 in use, 131 keeps the row stride odd)
-size_t items_index_bytes(size_t nbytes, size_t nitems);  // item-end bitmap, flag, stripe base
-size_t items_result_bytes(size_t nitems);                // result bitmap of one match
-// resolve_base / resolve_off (one-call form, nothing known on the host): nbytes is an UPPER BOUND the index is laid out for;
-// the kernels take the batch's start and length from the offsets; *flag != 0 afterwards = batch unfit for the stripe-wise
-// kernel (items_match then does nothing when handed the flag as skip_if)
-int items_index_build(size_t nbytes, const uint64_t *off, size_t nitems, uint32_t trim, void *index, uint32_t **flag, void *stream,
-                      const uint8_t *resolve_base = nullptr, size_t min_bytes = 0);
-int items_match(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
-                uint8_t *accept, void *stream, const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
-size_t long_scratch_bytes(uint32_t nstates, size_t nbytes, uint32_t *chunk);
-int match_long_dfa(const DfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t chunk, void *scratch, uint8_t *accept,
-                   void *stream);
+// ---- NFA lane engines: kernels_nfa.inc (built by width in kernels_nfa_w*.hip; the entry points are in kernels_coop.hip)
+int match_stripes_nfa(const NfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                      size_t nstripes, uint32_t *accept_bits, void *stream);
+int match_onepass_nfa(const NfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, size_t nstripes, uint32_t *counts,
+                      uint32_t *slabs, void *stream);
+int recheck_escaped_nfa(const NfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base, size_t nstripes,
+                        const uint32_t *escaped_bits, size_t nlines, const uint64_t *list, const unsigned long long *escaped_total, size_t cap,
+                        uint32_t *accept_bits, void *stream);
+int match_extents_nfa(const NfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
+                      uint8_t *accept, void *stream);
 // One long string on the NFA lane engines: per chunk the rows "positions reached from position p" (lane = (chunk, p)), then
 // the relations applied in order to {initial}.  `scratch` holds the rows (long_nfa_scratch_bytes).
 size_t long_nfa_scratch_bytes(const NfaDevice &p, size_t nbytes, uint32_t *chunk, uint32_t *nchunks);
 int match_long_nfa(const NfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t chunk, uint32_t nchunks, void *scratch, uint8_t *accept,
                    void *stream);
-int match_extents_nfa(const NfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
-                      uint8_t *accept, void *stream);
-// only_if != nullptr: the kernel does nothing unless *only_if != 0 (the fallback queued behind the stripe-wise items kernel)
-int match_extents_dfa(const DfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
-                      uint8_t *accept, void *stream, const uint32_t *only_if = nullptr);
+
+// ---- group-cooperative NFA: kernels_coop.hip
+int match_stripes_group_nfa(const GroupNfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                            size_t nstripes, uint32_t *accept_bits, void *stream);
+int match_extents_group_nfa(const GroupNfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
+                            uint8_t *accept, void *stream);
+
+// ---- wave-resident NFA and its sparse form: kernels_wave.hip
+uint32_t wave_words_per_lane(uint32_t words);    // the instantiated WL that holds `words` 32-bit words (0: too many)
+// The SPARSE form of the same engine (kernels_wave.hip: SparseNfa): WL then counts ROWS of 2048 positions and masks / Bbyte are
+// laid out by rows - [3][WL][64] and [257][WL][64]: word w of the set = row w / 64, lane w % 64.
+uint32_t sparse_rows(uint32_t words);            // the instantiated row count that holds `words` 32-bit words (0: too many)
+int match_stripes_sparse_nfa(const WaveNfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                             size_t nstripes, uint32_t *accept_bits, void *stream);
+int match_extents_sparse_nfa(const WaveNfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
+                             uint8_t *accept, void *stream);
+int match_stripes_wave_nfa(const WaveNfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                           size_t nstripes, uint32_t *accept_bits, void *stream);
+int match_extents_wave_nfa(const WaveNfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
+                           uint8_t *accept, void *stream);
 
 }  // namespace dev
 }  // namespace rrx

@@ -1,5 +1,6 @@
-// kernels_common.hpp — shared device code of the kernel translation units (kernels_table.hip, kernels_nfa.hip,
-// kernels_coop.hip).  Originally one file: hand-written CDNA4 (gfx950) kernels for the RoaringRegex hot path.
+// kernels_common.hpp — shared device code of every kernel translation unit (kernels_table, _index, _items, _long, _search,
+// _coop, _wave .hip and kernels_nfa.inc; the table engines on top of it: table_engines.hpp).  Originally one file:
+// hand-written CDNA4 (gfx950) kernels for the RoaringRegex hot path.
 //
 // Replaces, for a whole batch of '\n'-delimited strings at once:
 //   AcceptanceIterator::operator++(int)   regex.h:156-159   (consume the string)

@@ -13,11 +13,12 @@ extern "C" int rrx_probe_match_stamped(const rrx_regex *re, const rrx_corpus *c,
     const DeviceTables *t;
     int rc = re->tables(c->device, &t);
     if (rc) return rc;
-    if (!re->has_dfa2 || c->has_high) return fail(RRX_ERR_UNSUPPORTED, "stamps: the stride-2 engine only");
+    if (!re->match.has_dfa2 || c->has_high) return fail(RRX_ERR_UNSUPPORTED, "stamps: the stride-2 engine only");
     HIP_TRY(hipMemsetAsync(d_accept_bits, 0, rrx_corpus_bitmap_words(c) * sizeof(uint32_t), (hipStream_t)stream));
     const uint32_t upw = (uint32_t)re->opt_units_per_wg.load();
-    int e = upw ? dev::match_units_dfa2_stamped(t->dfa2, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, upw, d_stamps, d_rounds, stream)
-                : dev::match_stripes_dfa2_stamped(t->dfa2, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, d_stamps, d_rounds, stream);
+    const dev::Dfa2Device d2 = re->dfa2_device(t);
+    int e = upw ? dev::match_units_dfa2_stamped(d2, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, upw, d_stamps, d_rounds, stream)
+                : dev::match_stripes_dfa2_stamped(d2, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, d_stamps, d_rounds, stream);
     if (e) return hip_fail((hipError_t)e, "stamped launch");
     return RRX_OK;
 }
