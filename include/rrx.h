@@ -139,6 +139,9 @@ int         rrx_accepts_empty(const rrx_regex *re); /* Processor::operator*() on
                                     where the regex has no stride-2 table or this form does not fit beside the pair table              */
 #define RRX_PROGRAM_CONTAINS_DFA 16  /* the contains table (rrx_contains_corpus), DFA layout: state 0 = SKIP, class 0 a live column   */
 #define RRX_PROGRAM_CONTAINS_DFA2 17 /* its stride-2 form, DFA2 layout; 0 words where it does not fit                                */
+#define RRX_PROGRAM_CONTAINS_DFA2_ITEMS 18 /* the contains table's stride-2 ITEMS form (rrx_contains_extents / rrx_contains_items, trim 1), in exactly
+                                    the RRX_PROGRAM_DFA2_ITEMS layout; 0 words where the contains table has no stride-2 form (RRX_ENGINE_DFA /
+                                    _DFA_GLOBAL too) or the items form does not fit.  (The byte-stride forms step RRX_PROGRAM_CONTAINS_DFA.)   */
 size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t cap);
 
 /* ---- batch of strings: the replacement for calling get_acceptance_iter(line)++ per string ------------ *
@@ -236,6 +239,26 @@ size_t rrx_items_count(const rrx_items *items);
 int rrx_items_stripe_wise(const rrx_items *items);         /* 1: the batch admits the stripe-wise kernel */
 void rrx_items_free(rrx_items *items);
 int rrx_match_items(const rrx_regex *re, const rrx_items *items, uint8_t *d_accept, void *stream);
+
+/* WHICH items contain a match: rrx_contains_corpus for explicit items (an offsets array over one byte buffer - an Arrow string
+ * column), where ".*(p).*" through rrx_match_items rejects every item that holds a NUL or a UTF-8 byte and re-packing the column
+ * as '\n'-delimited text is wrong as soon as an item holds a '\n'.  Item i is d_bytes[d_off[i] .. d_off[i+1] - trim), as in
+ * rrx_match_extents.  Bit (i & 31) of d_bits[i >> 5] = 1 iff some substring of item i, the empty one included, is accepted by the
+ * pattern as a whole string (regex.h:156-162).  '\n' is an ordinary byte and may be part of a match; NUL and bytes >= 0x80 are
+ * ordinary text that no pattern takes; a pattern that accepts the empty string is contained in every item, an empty item
+ * included; an empty-language pattern in none.  d_bits holds ceil(nitems / 32) 32-bit words (4-byte aligned), zeroed and filled on
+ * `stream`, the bits of the last word beyond nitems 0 - the shape of rrx_contains_corpus' result (and of an Arrow boolean column):
+ * rrx_bitmap_count and rrx_bitmap_to_bytes apply.  nitems == 0 writes nothing and returns RRX_OK.  RRX_ERR_UNSUPPORTED exactly
+ * where rrx_contains_corpus returns it (no contains table within the state budget, or one beyond 2^24 entries); whether the regex'
+ * MATCH engine is a table engine plays no part.  Both calls are asynchronous on `stream` - except where rrx_match_extents
+ * synchronises too: a large batch inside an implausibly large allocation, or in memory whose range is not reported, has d_off[0]
+ * and d_off[nitems] read back, by the same bound rule.  Large batches (>= 65536 items, >= 8 MiB; every indexed batch that admits
+ * it) run the stripe-wise items kernels on the contains table's items forms - byte-stride up to about 126 states, stride-2 for
+ * trim 1 (RRX_OPT_ITEMS_STRIDE2; not for a regex compiled with RRX_ENGINE_DFA / RRX_ENGINE_DFA_GLOBAL) -, all others a lane per
+ * item, which stops reading an item at its first match.  Scratch and stream ordering as rrx_match_extents / rrx_match_items.    */
+int rrx_contains_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                         uint32_t *d_bits, void *stream);
+int rrx_contains_items(const rrx_regex *re, const rrx_items *items, uint32_t *d_bits, void *stream);
 
 /* ONE device-resident string of any length (regex.h:156-159: operator++ consumes the whole string; '\n' and every
  * other byte are ordinary, a NUL or a byte >= 0x80 rejects).  d_accept[0] = 1 iff accepted.  Strings of 32 KiB and

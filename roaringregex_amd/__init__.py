@@ -24,6 +24,7 @@ PROGRAM_DFA2_ORDER = 11
 PROGRAM_SAMPLED_DFA = 12
 PROGRAM_SAMPLED_DFA2 = 13
 PROGRAM_CONTAINS_DFA, PROGRAM_CONTAINS_DFA2 = 16, 17   # the contains table (rrx_contains_corpus) and its stride-2 form
+PROGRAM_CONTAINS_DFA2_ITEMS = 18                       # its stride-2 items form (rrx_contains_extents / rrx_contains_items, trim 1)
 OPT_BACKGROUND_ORDER = 1
 OPT_UNITS_PER_WORKGROUP = 2
 OPT_SAMPLED_TABLE = 3
@@ -42,6 +43,7 @@ ABI_SYMBOLS = (
     "rrx_match_extents", "rrx_items_create", "rrx_items_count", "rrx_items_stripe_wise", "rrx_items_free", "rrx_match_items",
     "rrx_match_string", "rrx_match_host", "rrx_match_cstr",
     "rrx_contains_corpus", "rrx_contains_engine_name", "rrx_contains_states", "rrx_bitmap_count",
+    "rrx_contains_extents", "rrx_contains_items",
 )
 
 
@@ -113,6 +115,8 @@ def _load():
         "rrx_contains_engine_name": (C.c_char_p, [vp]),
         "rrx_contains_states": (u32, [vp]),
         "rrx_bitmap_count": (i32, [i32, vp, sz, vp, vp]),
+        "rrx_contains_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp]),
+        "rrx_contains_items": (i32, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -440,6 +444,62 @@ class RRegex:
             _check(_L.rrx_match_extents(self._h, data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0),
                                         C.c_void_p(offsets.data_ptr()), n, trim, C.c_void_p(out.data_ptr() if n else 0),
                                         _stream_ptr(stream)))
+        return out[:n]
+
+    def contains_items_bits(self, items, out=None, stream=None):
+        """Which items of an indexed batch (Items) CONTAIN a match (rrx_contains_items): a bitmap of 32-bit words, an int32 tensor,
+        bit (i & 31) of word i >> 5 = some substring of item i is accepted.  '\\n', NUL and bytes >= 0x80 are ordinary text inside an
+        item.  The bits of the last word beyond the last item are 0.  Asynchronous on `stream`."""
+        import torch
+        n = items.num_items
+        nw = (n + 31) // 32
+        with _on(items.device, stream):
+            if out is None:
+                out = torch.empty(nw, dtype=torch.int32, device=items.data.device)
+            assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= nw
+            _check(_L.rrx_contains_items(self._h, items._h, C.c_void_p(out.data_ptr() if nw else 0), _stream_ptr(stream)))
+        return out[:nw]
+
+    def contains_items(self, items, out=None, stream=None):
+        """contains[i] = 1 iff item i of the indexed batch contains a match (one byte per item: bitmap + expansion)."""
+        import torch
+        n = items.num_items
+        with _on(items.device, stream):
+            bits = self.contains_items_bits(items, stream=stream)
+            if out is None:
+                out = torch.empty(n, dtype=torch.uint8, device=items.data.device)
+            assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
+            _check(_L.rrx_bitmap_to_bytes(items.device, C.c_void_p(bits.data_ptr() if n else 0), n,
+                                          C.c_void_p(out.data_ptr() if n else 0), _stream_ptr(stream)))
+        return out[:n]
+
+    def contains_extents_bits(self, data, offsets, trim=0, out=None, stream=None):
+        """The same for a batch nobody has indexed (rrx_contains_extents): item i = data[offsets[i] : offsets[i+1] - trim] -> the
+        bitmap of the items that contain a match, ceil(n / 32) int32 words."""
+        import torch
+        n = offsets.numel() - 1
+        nw = (n + 31) // 32
+        assert data.is_cuda and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+        with _on(data.device.index, stream):
+            if out is None:
+                out = torch.empty(nw, dtype=torch.int32, device=data.device)
+            assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= nw
+            _check(_L.rrx_contains_extents(self._h, data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0),
+                                           C.c_void_p(offsets.data_ptr()), n, trim, C.c_void_p(out.data_ptr() if nw else 0),
+                                           _stream_ptr(stream)))
+        return out[:nw]
+
+    def contains_extents(self, data, offsets, trim=0, out=None, stream=None):
+        """contains[i] = 1 iff item i = data[offsets[i] : offsets[i+1] - trim] contains a match (one byte per item)."""
+        import torch
+        n = offsets.numel() - 1
+        with _on(data.device.index, stream):
+            bits = self.contains_extents_bits(data, offsets, trim=trim, stream=stream)
+            if out is None:
+                out = torch.empty(n, dtype=torch.uint8, device=data.device)
+            assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
+            _check(_L.rrx_bitmap_to_bytes(data.device.index, C.c_void_p(bits.data_ptr() if n else 0), n,
+                                          C.c_void_p(out.data_ptr() if n else 0), _stream_ptr(stream)))
         return out[:n]
 
     def match_string(self, data, stream=None):

@@ -113,6 +113,20 @@ struct MailboxGuard {
 
 }  // namespace
 
+// The one accepting state of `d` if every byte class keeps it where it is (the FOUND state of a contains table), else ~0u.
+static uint32_t absorbing_accepting_state(const DfaProgram &d) {
+    uint32_t found = ~0u;
+    for (uint32_t s = 0; s < d.nstates; s++) {
+        if (!d.accepting[s]) continue;
+        if (found != ~0u) return ~0u;
+        found = s;
+    }
+    if (found != ~0u)
+        for (uint32_t k = 0; k < d.ncls; k++)
+            if (d.next[(size_t)found * d.ncls + k] != found) return ~0u;
+    return found;
+}
+
 struct rrx_regex : Programs {                            // (plan.hpp: the programs, the match tables' forms, the engine)
     std::string pattern;
     // Order of the stride-2 table's rows and columns in LDS (empty: as numbered).  The order costs no memory and decides which
@@ -403,6 +417,7 @@ struct rrx_regex : Programs {                            // (plan.hpp: the progr
         if (contains_state == 0) {
             (void)build_search();                        // (what the search entries cannot use does not matter here: the forward table does)
             contains_state = search.fwd.nstates != 0 && contains_dfa(search.fwd, contains.dfa) && contains.decide(requested_engine) ? 1 : -1;
+            if (contains_state == 1) contains_found = absorbing_accepting_state(contains.dfa);
         }
         return contains_state == 1 ? RRX_OK
                                    : fail(RRX_ERR_UNSUPPORTED, search.fwd.nstates ? "contains table too large for the device (the global form holds 2^24 entries)"
@@ -413,6 +428,41 @@ struct rrx_regex : Programs {                            // (plan.hpp: the progr
         std::lock_guard<std::mutex> lock(mu);
         const int rc = build_contains();
         return rc ? rc : upload_once(contains_on_device, device, false, [&](Image &img, DeviceTables &t) { contains.pack({}, {}, img, t); return true; }, out);
+    }
+
+    // "Which items contain a match" (rrx_contains_extents / rrx_contains_items): the contains table joined to the items kernels.  Its
+    // byte-stride items form is pack_items on contains.dfa - column 0 and column 128 (any byte >= 0x80) are filled from class 0, a
+    // live column here, which is what NUL and high bytes are to this table; it exists while the row offsets fit 16 bits.  Its
+    // stride-2 items form (trim 1) exists where the contains table has a stride-2 form at all - not under RRX_ENGINE_DFA /
+    // _DFA_GLOBAL - and the items form fits the same LDS region.  Misses are cached as items_table / items2_table cache theirs.
+    // The lane-per-item kernel runs on the plain arrays of contains_tables() and stops a lane in contains_found, the table's
+    // one accepting state if that state is absorbing (~0u: none - the empty language).
+    mutable std::map<int, OnDevice<dev::LineDfaDevice>> contains_items_on_device;
+    mutable std::map<int, OnDevice<dev::Dfa2Device>> contains_items2_on_device;
+    mutable Dfa2Program contains_items2_prog;
+    mutable int contains_items2_state = 0;             // 0 not tried, 1 there, 2 does not fit
+    mutable uint32_t contains_found = ~0u;             // (set by build_contains)
+    bool contains_items2_program_locked() const {      // host side (call with `mu` held, after build_contains)
+        if (contains.has_dfa2 && contains_items2_state == 0)
+            contains_items2_state = lower_dfa2_that_fits(contains.dfa, contains_items2_prog, /*items=*/true) ? 1 : 2;
+        return contains_items2_state == 1;
+    }
+    const dev::Dfa2Device *contains_items2_table(int device) const {
+        std::lock_guard<std::mutex> lock(mu);
+        const dev::Dfa2Device *d = nullptr;
+        if (build_contains()) return d;
+        auto pack = [&](Image &img, dev::Dfa2Device &t) {
+            return contains_items2_program_locked() && pack_dfa2(contains_items2_prog, {}, {}, img, t, dev::kDfa2PItemsBytes);
+        };
+        (void)upload_once(contains_items2_on_device, device, true, pack, &d);
+        return d;
+    }
+    const dev::LineDfaDevice *contains_items_table(int device) const {
+        std::lock_guard<std::mutex> lock(mu);
+        const dev::LineDfaDevice *d = nullptr;
+        if (build_contains()) return d;
+        (void)upload_once(contains_items_on_device, device, true, [&](Image &img, dev::LineDfaDevice &t) { return pack_items(contains.dfa, img, t); }, &d);
+        return d;
     }
 
     // Upload the program for `device` once; returns the device-side descriptors.
@@ -603,6 +653,10 @@ size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t ca
         if (re->build_contains()) return 0;
         if (kind == RRX_PROGRAM_CONTAINS_DFA) append_words(w, re->contains.dfa);
         else if (re->contains.has_dfa2) append_words(w, re->contains.dfa2);
+    } else if (kind == RRX_PROGRAM_CONTAINS_DFA2_ITEMS) {
+        std::lock_guard<std::mutex> lock(re->mu);
+        if (re->build_contains()) return 0;
+        if (re->contains_items2_program_locked()) append_words(w, re->contains_items2_prog, /*pair_dim=*/true);
     } else if (kind == RRX_PROGRAM_DFA2_ORDER && re->match.has_dfa2) {
         std::lock_guard<std::mutex> lock(re->mu);
         if (re->t2_row_slot.size() != re->match.dfa2.nstates || re->t2_col_slot.size() != re->match.dfa2.ncols) return 0;
@@ -1080,6 +1134,33 @@ static ItemsTable pick_items_table(const rrx_regex *re, int device, uint32_t tri
     if (!t.items2) t.items1 = re->items_table(device);
     return t;
 }
+// The most a one-call batch of items at `d_bytes` can span (the index, the stripe and the grids are sized for it; the kernels take
+// the real extent from the offsets): what is left of the allocation that holds d_bytes.
+// The tail of the allocation is only a BOUND: a batch carved out of a memory pool (a caching allocator's block, a slice of a
+// column store) would size the index, the stripe and the grids for all of the pool behind it - a 24 MiB batch 6 GiB into a
+// 10 GiB pool: 512 MiB of scratch and two workgroups' worth of stripes.  So the bound is trusted only while it is plausible
+// for the batch: at most 128 bytes per item (string columns; 16 MiB at least).  Beyond that - and for memory whose range
+// the runtime does not report (pools, managed and virtual memory: bound 0) - the batch's real extent is read back, one
+// synchronisation on `stream`, as round 2 did for every batch.
+static int items_extent_bound(const void *d_bytes, const uint64_t *d_off, size_t nitems, void *stream, size_t *out) {
+    size_t bound = 0;
+    hipDeviceptr_t abase = nullptr;
+    size_t asize = 0;
+    if (hipMemGetAddressRange(&abase, &asize, const_cast<void *>(d_bytes)) == hipSuccess && abase)
+        bound = (size_t)(static_cast<const uint8_t *>(abase) + asize - static_cast<const uint8_t *>(d_bytes));
+    else (void)hipGetLastError();
+    const size_t plausible = std::max<size_t>(nitems * 128, (size_t)16 << 20);
+    if (!bound || bound > plausible) {
+        uint64_t first = 0, last = 0;
+        HIP_TRY(hipMemcpyAsync(&first, d_off, sizeof first, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_TRY(hipMemcpyAsync(&last, d_off + nitems, sizeof last, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        const size_t extent = last > first ? (size_t)last : 0;
+        bound = bound ? std::min(bound, extent) : extent;
+    }
+    *out = bound;
+    return RRX_OK;
+}
 int rrx_match_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                       uint8_t *d_accept, void *stream) {
     if (!re || (nitems && (!d_off || !d_accept))) return fail(RRX_ERR_ARG, "null argument");
@@ -1102,28 +1183,8 @@ int rrx_match_extents(const rrx_regex *re, int device, const void *d_bytes, cons
     const bool items = it.items1 || it.items2;
     size_t bound = 0;
     if (items) {
-        hipDeviceptr_t abase = nullptr;
-        size_t asize = 0;
-        if (hipMemGetAddressRange(&abase, &asize, const_cast<void *>(d_bytes)) == hipSuccess && abase)
-            bound = (size_t)(static_cast<const uint8_t *>(abase) + asize - b);
-        else (void)hipGetLastError();
-    }
-    // The tail of the allocation is only a BOUND: a batch carved out of a memory pool (a caching allocator's block, a slice of a
-    // column store) would size the index, the stripe and the grids for all of the pool behind it - a 24 MiB batch 6 GiB into a
-    // 10 GiB pool: 512 MiB of scratch and two workgroups' worth of stripes.  So the bound is trusted only while it is plausible
-    // for the batch: at most 128 bytes per item (string columns; 16 MiB at least).  Beyond that - and for memory whose range
-    // the runtime does not report (pools, managed and virtual memory: bound 0) - the batch's real extent is read back, one
-    // synchronisation on `stream`, as round 2 did for every batch.  (The kernels take the extent from the offsets either way.)
-    if (items) {
-        const size_t plausible = std::max<size_t>(nitems * 128, (size_t)16 << 20);
-        if (!bound || bound > plausible) {
-            uint64_t first = 0, last = 0;
-            HIP_TRY(hipMemcpyAsync(&first, d_off, sizeof first, hipMemcpyDeviceToHost, (hipStream_t)stream));
-            HIP_TRY(hipMemcpyAsync(&last, d_off + nitems, sizeof last, hipMemcpyDeviceToHost, (hipStream_t)stream));
-            HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-            const size_t extent = last > first ? (size_t)last : 0;
-            bound = bound ? std::min(bound, extent) : extent;
-        }
+        rc = items_extent_bound(d_bytes, d_off, nitems, stream, &bound);
+        if (rc) return rc;
     }
     if (items && bound >= kItemsStripesMinBytes) {
         hipStream_t st = (hipStream_t)stream;
@@ -1216,6 +1277,78 @@ int rrx_match_items(const rrx_regex *re, const rrx_items *it, uint8_t *d_accept,
     }
     // the batch or the pattern does not admit the stripe-wise kernel (the index said so once: no second attempt)
     return match_extents_lanes(re, t, it->d_bytes, it->d_off, it->nitems, it->trim, d_accept, stream);
+}
+
+// ---- "which items contain a match": rrx_match_extents / rrx_match_items decision for decision, on the contains tables - the
+// stripe-wise items kernels where the contains table has an items form (whatever the regex' MATCH engine is), the lane-per-item
+// kernel of kernels_contains_items.hip elsewhere.  The stripe-wise kernels write into scratch (padded, bit nitems may be set); the
+// caller's bitmap receives a masked copy.
+static int contains_extents_lanes(const rrx_regex *re, const DeviceTables *t, const uint8_t *b, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                  uint32_t *d_bits, void *stream, const uint32_t *only_if = nullptr) {
+    return launched(dev::contains_extents_dfa(t->dfa, re->contains.global, re->contains_found, b, d_off, nitems, trim, d_bits, stream, only_if),
+                    "contains_extents launch");
+}
+static ItemsTable pick_contains_items_table(const rrx_regex *re, int device, uint32_t trim) {
+    ItemsTable t;
+    if (trim == 1 && re->items_stride2.load()) t.items2 = re->contains_items2_table(device);
+    if (!t.items2) t.items1 = re->contains_items_table(device);
+    return t;
+}
+int rrx_contains_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                         uint32_t *d_bits, void *stream) {
+    if (!re || (nitems && (!d_off || !d_bits))) return fail(RRX_ERR_ARG, "null argument");
+    const DeviceTables *t;
+    int rc = re->contains_tables(device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if (!nitems) return RRX_OK;
+    const uint8_t *b = static_cast<const uint8_t *>(d_bytes);
+    ItemsTable it;
+    if (trim <= 1 && nitems >= kItemsStripesMin) it = pick_contains_items_table(re, device, trim);
+    const bool items = it.items1 || it.items2;
+    size_t bound = 0;
+    if (items) {
+        rc = items_extent_bound(d_bytes, d_off, nitems, stream, &bound);
+        if (rc) return rc;
+    }
+    if (items && bound >= kItemsStripesMinBytes) {
+        // both kernels are queued, each predicated on the index pass's fit flag: on an unfit batch the copy out of the scratch gives
+        // zeros and the lane-per-item kernel behind it rewrites every word
+        hipStream_t st = (hipStream_t)stream;
+        std::lock_guard<std::mutex> lock(re->onepass_mu);
+        void *buf = nullptr;
+        const size_t ib = dev::items_index_bytes(bound, nitems);
+        rc = re->onepass_for(device, ib + dev::items_result_bytes(nitems), &buf, st);      // (ordered behind the scratch's last user)
+        if (rc) return rc;
+        uint32_t *d_flag = nullptr;
+        int le = dev::items_index_build(bound, d_off, nitems, trim, buf, &d_flag, stream, b, kItemsStripesMinBytes);
+        if (!le) le = it.items2 ? dev::items_contains2(*it.items2, b, bound, nitems, buf, static_cast<uint8_t *>(buf) + ib, d_bits, stream, d_off, d_flag)
+                                : dev::items_contains(*it.items1, b, bound, nitems, trim, buf, static_cast<uint8_t *>(buf) + ib, d_bits, stream, d_off, d_flag);
+        if (!le) rc = contains_extents_lanes(re, t, b, d_off, nitems, trim, d_bits, stream, d_flag);
+        const int rc2 = re->onepass_done(device, st);            // (whatever was queued: the next user waits for it)
+        if (le) return hip_fail((hipError_t)le, "contains_items_stripes launch");
+        return rc ? rc : rc2;
+    }
+    return contains_extents_lanes(re, t, b, d_off, nitems, trim, d_bits, stream);
+}
+int rrx_contains_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_bits, void *stream) {
+    if (!re || !it || (it->nitems && !d_bits)) return fail(RRX_ERR_ARG, "null argument");
+    const DeviceTables *t;
+    int rc = re->contains_tables(it->device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(it->device));
+    if (!it->nitems) return RRX_OK;
+    if (it->stripes) {
+        const ItemsTable tab = pick_contains_items_table(re, it->device, it->trim);
+        if (tab.items1 || tab.items2) {
+            std::lock_guard<std::mutex> lock(it->mu);
+            int le = tab.items2 ? dev::items_contains2(*tab.items2, it->d_bytes + it->first, it->nbytes, it->nitems, it->d_index, it->d_result, d_bits, stream)
+                                : dev::items_contains(*tab.items1, it->d_bytes + it->first, it->nbytes, it->nitems, it->trim, it->d_index, it->d_result, d_bits, stream);
+            return launched(le, "contains_items launch");
+        }
+    }
+    // the batch or the pattern does not admit the stripe-wise kernel
+    return contains_extents_lanes(re, t, it->d_bytes, it->d_off, it->nitems, it->trim, d_bits, stream);
 }
 
 // One device-resident string of any length.  Long strings take the chunk-map path when the automaton has a small

@@ -229,6 +229,24 @@ int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_
 int items_match(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
                 uint8_t *accept, void *stream, const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
 
+// the same kernels on the contains items tables (rrx_contains_extents / rrx_contains_items): the arguments of items_match2 /
+// items_match, but the result is the bitmap itself - ceil(nitems / 32) words into `bits` (any 4-byte alignment), the bits of the
+// last word beyond nitems 0; an unfit batch (*skip_if != 0) leaves zeros
+int items_contains2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, uint32_t *bits, void *stream,
+                    const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
+int items_contains(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
+                   uint32_t *bits, void *stream, const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
+
+// ---- contains for explicit items, a lane per item: kernels_contains_items.hip
+// `p`: the contains table in its plain form ('\n', NUL and bytes >= 0x80 are ordinary bytes of their class; nothing kills).
+// found: its one accepting state if that state is absorbing - a lane stops reading there -, ~0u: none.  in_global: leave the
+// table in HBM/L2 whatever its size.  Whole words of `bits` are written with plain stores (ceil(nitems / 32) of them, the bits
+// beyond nitems 0): nothing to clear beforehand.  only_if as for match_extents_dfa.
+int contains_extents_dfa(const DfaDevice &p, bool in_global, uint32_t found, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
+                         uint32_t *bits, void *stream, const uint32_t *only_if = nullptr);
+// the first ceil(nitems / 32) words of a stripe-wise result bitmap into `bits`, the last one masked to nitems
+int copy_result_bits(const uint32_t *result, size_t nitems, uint32_t *bits, void *stream);
+
 // ---- one long string on the plain DFA: kernels_long.hip
 // One long string (regex.h:156-159 consumes it byte by byte): the string is cut into chunks, every chunk is stepped
 // from EVERY table state at once (lane = (chunk, start state); the lanes of a chunk read the same text), which yields

@@ -1,5 +1,6 @@
 // kernels_items.hip — explicit items (an offsets array over one byte buffer) matched stripe-wise: the item-end bitmap and its
-// index kernel, the byte-stride and stride-2 items kernels and their launchers.  Engines: table_engines.hpp.
+// index kernel, the byte-stride and stride-2 items kernels and their launchers (match: a byte per item; contains: a bitmap).
+// Engines: table_engines.hpp.
 #include "table_engines.hpp"
 
 namespace rrx {
@@ -430,11 +431,12 @@ int items_index_build(size_t nbytes, const uint64_t *off, size_t nitems, uint32_
                        (uint64_t)(items_ends_bytes(nbytes, stripe) / 4), resolve_base, (uint64_t)min_bytes, (uint32_t)__builtin_ctz(stripe), nstripes, base);
     return (int)hipGetLastError();
 }
-// one byte per item into `accept` (16-byte aligned); `result` = items_result_bytes(nitems) of scratch.  resolve_off != nullptr:
-// the one-call form - `bytes` is the buffer the offsets index, `nbytes` the upper bound the index was laid out for, the
-// kernel takes the batch's start and length from the offsets and does nothing if *skip_if != 0.
-int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, uint8_t *accept, void *stream,
-                 const uint64_t *resolve_off, const uint32_t *skip_if) {
+// The stripe-wise kernels into `result` = items_result_bytes(nitems) of scratch: a bitmap of the items' verdicts, padded, bit nitems
+// possibly set by the batch's closing end.  resolve_off != nullptr: the one-call form - `bytes` is the buffer the offsets index,
+// `nbytes` the upper bound the index was laid out for, the kernel takes the batch's start and length from the offsets and does
+// nothing if *skip_if != 0 (the bitmap stays zero).
+static int items_run2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, void *stream,
+                      const uint64_t *resolve_off, const uint32_t *skip_if) {
     if (!p.P || !p.T2 || Dfa2::lds_bytes(p) > kDfa2MaxTable || !nitems || !nbytes) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t stripe = items_stripe(nbytes, nitems);
@@ -446,12 +448,10 @@ int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_
     if (e != hipSuccess) return (int)e;
     const size_t blocks = (nstripes + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(match_items_stripes2_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, p, bytes, nbytes, stripe, base, ends, bits, resolve_off, nitems, skip_if);
-    const int rc = (int)hipGetLastError();
-    if (rc) return rc;
-    return expand_bits(bits, nitems, accept, stream);
+    return (int)hipGetLastError();
 }
-int items_match(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
-                uint8_t *accept, void *stream, const uint64_t *resolve_off, const uint32_t *skip_if) {
+static int items_run(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
+                     void *stream, const uint64_t *resolve_off, const uint32_t *skip_if) {
     if (!p.wide || p.in_global || p.stride != (kItemColumns << p.rep_log2) || trim > 1 || !nitems || !nbytes) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t stripe = items_stripe(nbytes, nitems);
@@ -480,9 +480,29 @@ int items_match(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, siz
         hipLaunchKernelGGL(match_items_stripes_kernel<2>, dim3((unsigned)blocks), dim3(kThreads), lds, st, p, bytes, nbytes, stripe, base, ends, bits, stage_off, stage_words,
                            resolve_off, nitems, skip_if);
     }
-    const int rc = (int)hipGetLastError();
-    if (rc) return rc;
-    return expand_bits(bits, nitems, accept, stream);
+    return (int)hipGetLastError();
+}
+// one byte per item into `accept` (16-byte aligned)
+int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, uint8_t *accept, void *stream,
+                 const uint64_t *resolve_off, const uint32_t *skip_if) {
+    const int rc = items_run2(p, bytes, nbytes, nitems, index, result, stream, resolve_off, skip_if);
+    return rc ? rc : expand_bits(static_cast<const uint32_t *>(result), nitems, accept, stream);
+}
+int items_match(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
+                uint8_t *accept, void *stream, const uint64_t *resolve_off, const uint32_t *skip_if) {
+    const int rc = items_run(p, bytes, nbytes, nitems, trim, index, result, stream, resolve_off, skip_if);
+    return rc ? rc : expand_bits(static_cast<const uint32_t *>(result), nitems, accept, stream);
+}
+// the same kernels on the contains items tables: ceil(nitems / 32) words into `bits`, the bits of the last word beyond nitems 0
+int items_contains2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, uint32_t *bits, void *stream,
+                    const uint64_t *resolve_off, const uint32_t *skip_if) {
+    const int rc = items_run2(p, bytes, nbytes, nitems, index, result, stream, resolve_off, skip_if);
+    return rc ? rc : copy_result_bits(static_cast<const uint32_t *>(result), nitems, bits, stream);
+}
+int items_contains(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
+                   uint32_t *bits, void *stream, const uint64_t *resolve_off, const uint32_t *skip_if) {
+    const int rc = items_run(p, bytes, nbytes, nitems, trim, index, result, stream, resolve_off, skip_if);
+    return rc ? rc : copy_result_bits(static_cast<const uint32_t *>(result), nitems, bits, stream);
 }
 
 }  // namespace dev
