@@ -62,6 +62,23 @@ hipError_t upload(int device, const Image &img, DeviceAlloc &out, hipStream_t st
     return e;
 }
 
+// Everything that hangs off one LineTables on the device side (under rrx_regex::mu): the table, the host side of its items forms
+// and, per device, what has been uploaded - its tables, its byte-stride items table (the plain table in the wide line-table format
+// with one more column: 0..127 byte values, '\n' an ordinary byte, 128 = any byte >= 0x80, 129 = END OF ITEM: verdict of the row,
+// back to the start row) and its stride-2 items table.  A regex has two: of its match table and of its contains table.
+struct TableSet {
+    const char *const word;                              // "match" / "contains": how its items launches are named in error texts
+    LineTables own;
+    LineTables &lt;                                      // `own`, or Programs::match
+    ItemsForms items;
+    uint32_t found = ~0u;                                // contains: the one accepting state if it is absorbing (build_contains)
+    std::map<int, OnDevice<DeviceTables>> on_device;
+    std::map<int, OnDevice<dev::LineDfaDevice>> items_on_device;
+    std::map<int, OnDevice<dev::Dfa2Device>> items2_on_device;
+    explicit TableSet(const char *w) : word(w), lt(own) {}
+    TableSet(const char *w, LineTables &of) : word(w), lt(of) {}
+};
+
 // Small results a call has to hand back to the host (line totals, flags) are written by the call's last kernel into a slot
 // of pinned, device-mapped host memory; the host then only waits for the stream.  (Round 2 read them with three
 // hipMemcpyAsync into pageable stack variables and a synchronize: one call in twelve of the one-shot entry took 10.6 ms
@@ -232,7 +249,7 @@ struct rrx_regex : Programs {                            // (plan.hpp: the progr
     // numbered order and keeps it (its own arrays agree with each other; results never depend on the order).
     void apply_t2_order(std::vector<uint32_t> &&rows, std::vector<uint32_t> &&cols, const Dfa2OrderStats &st) const {
         std::vector<int> up;
-        { std::lock_guard<std::mutex> lock(mu); for (auto &kv : on_device) up.push_back(kv.first); }
+        { std::lock_guard<std::mutex> lock(mu); for (auto &kv : match_set.on_device) up.push_back(kv.first); }
         std::vector<std::pair<int, OnDevice<dev::Dfa2Device>>> done;
         for (int device : up) {
             Image img;
@@ -250,8 +267,8 @@ struct rrx_regex : Programs {                            // (plan.hpp: the progr
         self->t2_row_slot.swap(rows); self->t2_col_slot.swap(cols);
         t2_order_stats = st;
         for (auto &u : done) {
-            auto it = on_device.find(u.first);
-            if (it != on_device.end()) it->second.d.dfa2 = u.second.d;
+            auto it = match_set.on_device.find(u.first);
+            if (it != match_set.on_device.end()) it->second.d.dfa2 = u.second.d;
             kept.push_back(std::move(u.second.mem));
         }
     }
@@ -269,17 +286,13 @@ struct rrx_regex : Programs {                            // (plan.hpp: the progr
     }
     dev::Dfa2Device dfa2_device(const DeviceTables *t) const { std::lock_guard<std::mutex> lock(mu); return t->dfa2; }
     mutable std::mutex mu;
-    mutable std::map<int, OnDevice<DeviceTables>> on_device;
+    // The match tables by engine (tables()) and the contains tables (contains_tables(): built at their first use, build_contains),
+    // each with its items tables (items_table / items2_table)
+    mutable TableSet match_set{"match", match}, contains_set{"contains"};
     // search (built on first use; plan.hpp: plan_search)
     mutable int search_state = 0;        // 0 = not built, 1 = built, -1 = does not fit
     mutable SearchPlan search;
     mutable std::map<int, OnDevice<dev::SearchChunkDevice>> search_on_device;
-    // The plain table in the wide line-table format with one more column: 0..127 byte values ('\n' an ordinary byte), 128 = any
-    // byte >= 0x80, 129 = END OF ITEM (verdict of the row, back to the start row).  For explicit items stepped stripe-wise.
-    mutable std::map<int, OnDevice<dev::LineDfaDevice>> items_on_device;
-    mutable std::map<int, OnDevice<dev::Dfa2Device>> items2_on_device;
-    mutable Dfa2Program items2_prog;                   // lowered at the first batch of items with separators
-    mutable int items2_state = 0;                      // 0 not tried, 1 there, 2 does not fit
     std::atomic<int> items_stride2{1};                 // RRX_OPT_ITEMS_STRIDE2 (0: the byte-stride items kernel for trim 1 as well)
     // Scratch of the single-string entries (rrx_match_string / rrx_match_cstr): one grow-only device buffer per device,
     // kept across calls (a hipMalloc + hipFree pair per string cost more than the match itself).  `scratch_mu` is held
@@ -348,13 +361,6 @@ struct rrx_regex : Programs {                            // (plan.hpp: the progr
             (void)hipHostFree(h_sampled_seen);
         }
     }
-    // The stride-2 table of explicit items with a separator byte each (trim 1; lower_dfa2's items form): nullptr where the regex
-    // has no stride-2 table or the items form - one symbol more - does not fit the same LDS region.
-    bool items2_program_locked() const {                 // host side (call with `mu` held)
-        if (match.has_dfa2 && items2_state == 0) items2_state = lower_dfa2_that_fits(match.dfa, items2_prog, /*items=*/true) ? 1 : 2;
-        return items2_state == 1;
-    }
-    bool items2_program() const { std::lock_guard<std::mutex> lock(mu); return items2_program_locked(); }
     // The image that `pack` fills (false: none) on `device`, uploaded at the first use (call with `mu` held).  No image or a failed
     // upload: an error, tried again at the next call - or with `keep_miss` a miss cached for good (*out = nullptr, RRX_OK).
     template <class D, class Pack> int upload_once(std::map<int, OnDevice<D>> &cache, int device, bool keep_miss, Pack pack, const D **out) const {
@@ -371,18 +377,20 @@ struct rrx_regex : Programs {                            // (plan.hpp: the progr
         *out = it->second.mem.p ? &it->second.d : nullptr;
         return RRX_OK;
     }
-    // The items tables: nullptr where the regex has none that fits (the caller runs the other kernel)
-    const dev::Dfa2Device *items2_table(int device) const {
+    // The items tables of `set` on `device`, for explicit items stepped stripe-wise: nullptr where it has none that fits (the caller
+    // runs the other kernel) - no contains table at all; byte-stride: more states than 16-bit row offsets allow; stride-2 (a separator
+    // byte per item, trim 1): no stride-2 line table, or the items form - one symbol more - is beyond the same LDS region.
+    bool built(const TableSet &set) const { return &set == &match_set || build_contains() == RRX_OK; }      // (call with `mu` held)
+    const dev::Dfa2Device *items2_table(TableSet &set, int device) const {
         std::lock_guard<std::mutex> lock(mu);
         const dev::Dfa2Device *d = nullptr;
-        auto pack = [&](Image &img, dev::Dfa2Device &t) { return items2_program_locked() && pack_dfa2(items2_prog, {}, {}, img, t, dev::kDfa2PItemsBytes); };
-        (void)upload_once(items2_on_device, device, true, pack, &d);
+        if (built(set)) (void)upload_once(set.items2_on_device, device, true, [&](Image &img, dev::Dfa2Device &t) { return set.items.pack2(set.lt, img, t); }, &d);
         return d;
     }
-    const dev::LineDfaDevice *items_table(int device) const {       // (none: more states than 16-bit row offsets allow)
+    const dev::LineDfaDevice *items_table(TableSet &set, int device) const {
         std::lock_guard<std::mutex> lock(mu);
         const dev::LineDfaDevice *d = nullptr;
-        (void)upload_once(items_on_device, device, true, [&](Image &img, dev::LineDfaDevice &t) { return pack_items(match.dfa, img, t); }, &d);
+        if (built(set)) (void)upload_once(set.items_on_device, device, true, [&](Image &img, dev::LineDfaDevice &t) { return set.items.pack(set.lt, img, t); }, &d);
         return d;
     }
 
@@ -410,14 +418,18 @@ struct rrx_regex : Programs {                            // (plan.hpp: the progr
     // state (lower.hpp: contains_dfa), in the forms of the match path and by its fit rules (plan.hpp: LineTables) - the stride-2
     // form, the wide / classed LDS line table, the global line table; a regex compiled with RRX_ENGINE_DFA / _DFA_GLOBAL keeps it
     // on the byte-stride LDS / global table.  Host side (call with `mu` held).
+    // Its items forms join it to the items kernels (rrx_contains_extents / rrx_contains_items): in the byte-stride form column 0 and
+    // column 128 (any byte >= 0x80) are filled from class 0, a live column here, which is what NUL and high bytes are to this table;
+    // the stride-2 form exists where the contains table has one at all - not under RRX_ENGINE_DFA / _DFA_GLOBAL.  The lane-per-item
+    // kernel runs on the plain arrays of contains_tables() and stops a lane in contains_set.found, the table's one accepting state if
+    // that state is absorbing (~0u: none - the empty language).
     mutable int contains_state = 0;      // 0 = not built, 1 = built, -1 = no table
-    mutable LineTables contains;
-    mutable std::map<int, OnDevice<DeviceTables>> contains_on_device;
     int build_contains() const {
         if (contains_state == 0) {
             (void)build_search();                        // (what the search entries cannot use does not matter here: the forward table does)
-            contains_state = search.fwd.nstates != 0 && contains_dfa(search.fwd, contains.dfa) && contains.decide(requested_engine) ? 1 : -1;
-            if (contains_state == 1) contains_found = absorbing_accepting_state(contains.dfa);
+            LineTables &lt = contains_set.lt;
+            contains_state = search.fwd.nstates != 0 && contains_dfa(search.fwd, lt.dfa) && lt.decide(requested_engine) ? 1 : -1;
+            if (contains_state == 1) contains_set.found = absorbing_accepting_state(lt.dfa);
         }
         return contains_state == 1 ? RRX_OK
                                    : fail(RRX_ERR_UNSUPPORTED, search.fwd.nstates ? "contains table too large for the device (the global form holds 2^24 entries)"
@@ -427,48 +439,13 @@ struct rrx_regex : Programs {                            // (plan.hpp: the progr
     int contains_tables(int device, const DeviceTables **out) const {
         std::lock_guard<std::mutex> lock(mu);
         const int rc = build_contains();
-        return rc ? rc : upload_once(contains_on_device, device, false, [&](Image &img, DeviceTables &t) { contains.pack({}, {}, img, t); return true; }, out);
-    }
-
-    // "Which items contain a match" (rrx_contains_extents / rrx_contains_items): the contains table joined to the items kernels.  Its
-    // byte-stride items form is pack_items on contains.dfa - column 0 and column 128 (any byte >= 0x80) are filled from class 0, a
-    // live column here, which is what NUL and high bytes are to this table; it exists while the row offsets fit 16 bits.  Its
-    // stride-2 items form (trim 1) exists where the contains table has a stride-2 form at all - not under RRX_ENGINE_DFA /
-    // _DFA_GLOBAL - and the items form fits the same LDS region.  Misses are cached as items_table / items2_table cache theirs.
-    // The lane-per-item kernel runs on the plain arrays of contains_tables() and stops a lane in contains_found, the table's
-    // one accepting state if that state is absorbing (~0u: none - the empty language).
-    mutable std::map<int, OnDevice<dev::LineDfaDevice>> contains_items_on_device;
-    mutable std::map<int, OnDevice<dev::Dfa2Device>> contains_items2_on_device;
-    mutable Dfa2Program contains_items2_prog;
-    mutable int contains_items2_state = 0;             // 0 not tried, 1 there, 2 does not fit
-    mutable uint32_t contains_found = ~0u;             // (set by build_contains)
-    bool contains_items2_program_locked() const {      // host side (call with `mu` held, after build_contains)
-        if (contains.has_dfa2 && contains_items2_state == 0)
-            contains_items2_state = lower_dfa2_that_fits(contains.dfa, contains_items2_prog, /*items=*/true) ? 1 : 2;
-        return contains_items2_state == 1;
-    }
-    const dev::Dfa2Device *contains_items2_table(int device) const {
-        std::lock_guard<std::mutex> lock(mu);
-        const dev::Dfa2Device *d = nullptr;
-        if (build_contains()) return d;
-        auto pack = [&](Image &img, dev::Dfa2Device &t) {
-            return contains_items2_program_locked() && pack_dfa2(contains_items2_prog, {}, {}, img, t, dev::kDfa2PItemsBytes);
-        };
-        (void)upload_once(contains_items2_on_device, device, true, pack, &d);
-        return d;
-    }
-    const dev::LineDfaDevice *contains_items_table(int device) const {
-        std::lock_guard<std::mutex> lock(mu);
-        const dev::LineDfaDevice *d = nullptr;
-        if (build_contains()) return d;
-        (void)upload_once(contains_items_on_device, device, true, [&](Image &img, dev::LineDfaDevice &t) { return pack_items(contains.dfa, img, t); }, &d);
-        return d;
+        return rc ? rc : upload_once(contains_set.on_device, device, false, [&](Image &img, DeviceTables &t) { contains_set.lt.pack({}, {}, img, t); return true; }, out);
     }
 
     // Upload the program for `device` once; returns the device-side descriptors.
     int tables(int device, const DeviceTables **out) const {
         std::lock_guard<std::mutex> lock(mu);
-        return upload_once(on_device, device, false, [&](Image &img, DeviceTables &t) {
+        return upload_once(match_set.on_device, device, false, [&](Image &img, DeviceTables &t) {
             if (engine == RRX_ENGINE_NFA_BLOCK || engine == RRX_ENGINE_NFA_SPARSE) {
                 const bool sparse = engine == RRX_ENGINE_NFA_SPARSE;
                 pack_wave_nfa(nfa_block, trimmed, sparse ? dev::sparse_rows(nfa_block.W) : dev::wave_words_per_lane(nfa_block.W), sparse, img, t.block);
@@ -651,12 +628,12 @@ size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t ca
     } else if (kind == RRX_PROGRAM_CONTAINS_DFA || kind == RRX_PROGRAM_CONTAINS_DFA2) {
         std::lock_guard<std::mutex> lock(re->mu);
         if (re->build_contains()) return 0;
-        if (kind == RRX_PROGRAM_CONTAINS_DFA) append_words(w, re->contains.dfa);
-        else if (re->contains.has_dfa2) append_words(w, re->contains.dfa2);
-    } else if (kind == RRX_PROGRAM_CONTAINS_DFA2_ITEMS) {
+        if (kind == RRX_PROGRAM_CONTAINS_DFA) append_words(w, re->contains_set.lt.dfa);
+        else if (re->contains_set.lt.has_dfa2) append_words(w, re->contains_set.lt.dfa2);
+    } else if (kind == RRX_PROGRAM_CONTAINS_DFA2_ITEMS || (kind == RRX_PROGRAM_DFA2_ITEMS && re->match.has_dfa2)) {
+        TableSet &set = kind == RRX_PROGRAM_DFA2_ITEMS ? re->match_set : re->contains_set;
         std::lock_guard<std::mutex> lock(re->mu);
-        if (re->build_contains()) return 0;
-        if (re->contains_items2_program_locked()) append_words(w, re->contains_items2_prog, /*pair_dim=*/true);
+        if (re->built(set) && set.items.stride2(set.lt)) append_words(w, set.items.dfa2, /*pair_dim=*/true);
     } else if (kind == RRX_PROGRAM_DFA2_ORDER && re->match.has_dfa2) {
         std::lock_guard<std::mutex> lock(re->mu);
         if (re->t2_row_slot.size() != re->match.dfa2.nstates || re->t2_col_slot.size() != re->match.dfa2.ncols) return 0;
@@ -668,8 +645,6 @@ size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t ca
         std::lock_guard<std::mutex> lock(re->mu);
         if (kind == RRX_PROGRAM_SAMPLED_DFA) append_words(w, re->sampled_dfa, /*escaped=*/true);
         else append_words(w, re->sampled_dfa2);
-    } else if (kind == RRX_PROGRAM_DFA2_ITEMS && re->match.has_dfa2) {
-        if (re->items2_program()) append_words(w, re->items2_prog, /*pair_dim=*/true);
     } else if (kind == RRX_ENGINE_DFA2 && re->match.has_dfa2) {
         append_words(w, re->match.dfa2);
     } else if (kind == RRX_ENGINE_DFA && re->has_dfa) {
@@ -874,17 +849,17 @@ int rrx_contains_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_bi
     if (!c->nlines) return RRX_OK;
     // the kernels merge words with atomic OR: start from an all-zero bitmap
     HIP_TRY(hipMemsetAsync(d_bits, 0, rrx_corpus_bitmap_words(c) * sizeof(uint32_t), (hipStream_t)stream));
-    return launched(launch_line_tables(re, c, re->contains, t, /*stride2_over_high=*/true, d_bits, stream), "contains launch");
+    return launched(launch_line_tables(re, c, re->contains_set.lt, t, /*stride2_over_high=*/true, d_bits, stream), "contains launch");
 }
 const char *rrx_contains_engine_name(const rrx_regex *re) {
     if (!re) { (void)fail(RRX_ERR_ARG, "null argument"); return nullptr; }
     std::lock_guard<std::mutex> lock(re->mu);
-    return re->build_contains() ? nullptr : re->contains.name();
+    return re->build_contains() ? nullptr : re->contains_set.lt.name();
 }
 uint32_t rrx_contains_states(const rrx_regex *re) {
     if (!re) { (void)fail(RRX_ERR_ARG, "null argument"); return 0; }
     std::lock_guard<std::mutex> lock(re->mu);
-    return re->build_contains() ? 0 : re->contains.dfa.nstates;
+    return re->build_contains() ? 0 : re->contains_set.lt.dfa.nstates;
 }
 int rrx_bitmap_count(int device, const uint32_t *d_bits, size_t nlines, uint64_t *d_count, void *stream) {
     if (!d_count || (nlines && !d_bits)) return fail(RRX_ERR_ARG, "null argument");
@@ -1115,23 +1090,25 @@ int rrx_bitmap_to_bytes(int device, const uint32_t *d_bits, size_t nlines, uint8
 // below these a batch stays on the lane-per-item kernel (the index costs more than it saves)
 static constexpr size_t kItemsStripesMin = (size_t)1 << 16;
 static constexpr size_t kItemsStripesMinBytes = (size_t)8 << 20;
-// a lane (lane group, workgroup) per item
-static int match_extents_lanes(const rrx_regex *re, const DeviceTables *t, const uint8_t *b, const uint64_t *d_off, size_t nitems, uint32_t trim,
-                               uint8_t *d_accept, void *stream, const uint32_t *only_if = nullptr) {
-    int e = re->engine == RRX_ENGINE_NFA_SPARSE ? dev::match_extents_sparse_nfa(t->block, b, d_off, nitems, trim, d_accept, stream)
-            : re->engine == RRX_ENGINE_NFA_BLOCK ? dev::match_extents_wave_nfa(t->block, b, d_off, nitems, trim, d_accept, stream)
-            : re->engine == RRX_ENGINE_NFA_WAVE ? dev::match_extents_group_nfa(t->group, b, d_off, nitems, trim, d_accept, stream)
-            : re->engine == RRX_ENGINE_NFA ? dev::match_extents_nfa(t->nfa, b, d_off, nitems, trim, d_accept, stream)
-                                         : dev::match_extents_dfa(t->dfa, b, d_off, nitems, trim, d_accept, stream, only_if);
-    return launched(e, "match_extents launch");
+// A lane (lane group, workgroup) per item: the match set on the regex' engine, one byte per item; the contains set on the plain
+// arrays of its table, the bitmap itself.
+static int extents_lanes(const rrx_regex *re, const TableSet &set, const DeviceTables *t, const uint8_t *b, const uint64_t *d_off, size_t nitems,
+                         uint32_t trim, dev::ItemVerdicts out, void *stream, const uint32_t *only_if = nullptr) {
+    int e = &set == &re->contains_set ? dev::contains_extents_dfa(t->dfa, set.lt.global, set.found, b, d_off, nitems, trim, out.bits, stream, only_if)
+            : re->engine == RRX_ENGINE_NFA_SPARSE ? dev::match_extents_sparse_nfa(t->block, b, d_off, nitems, trim, out.bytes, stream)
+            : re->engine == RRX_ENGINE_NFA_BLOCK ? dev::match_extents_wave_nfa(t->block, b, d_off, nitems, trim, out.bytes, stream)
+            : re->engine == RRX_ENGINE_NFA_WAVE ? dev::match_extents_group_nfa(t->group, b, d_off, nitems, trim, out.bytes, stream)
+            : re->engine == RRX_ENGINE_NFA ? dev::match_extents_nfa(t->nfa, b, d_off, nitems, trim, out.bytes, stream)
+                                         : dev::match_extents_dfa(t->dfa, b, d_off, nitems, trim, out.bytes, stream, only_if);
+    return e ? hip_fail((hipError_t)e, (std::string(set.word) + "_extents launch").c_str()) : RRX_OK;
 }
 // The table of the stripe-wise items kernels on `device`: the stride-2 items table for trim 1 (unless RRX_OPT_ITEMS_STRIDE2 is 0),
-// else - or where that one does not fit - the byte-stride items table; both nullptr: the regex has none (the lane-per-item kernel).
+// else - or where that one does not fit - the byte-stride items table; both nullptr: the set has none (the lane-per-item kernel).
 struct ItemsTable { const dev::LineDfaDevice *items1 = nullptr; const dev::Dfa2Device *items2 = nullptr; };
-static ItemsTable pick_items_table(const rrx_regex *re, int device, uint32_t trim) {
+static ItemsTable pick_items_table(const rrx_regex *re, TableSet &set, int device, uint32_t trim) {
     ItemsTable t;
-    if (trim == 1 && re->items_stride2.load()) t.items2 = re->items2_table(device);
-    if (!t.items2) t.items1 = re->items_table(device);
+    if (trim == 1 && re->items_stride2.load()) t.items2 = re->items2_table(set, device);
+    if (!t.items2) t.items1 = re->items_table(set, device);
     return t;
 }
 // The most a one-call batch of items at `d_bytes` can span (the index, the stripe and the grids are sized for it; the kernels take
@@ -1161,6 +1138,46 @@ static int items_extent_bound(const void *d_bytes, const uint64_t *d_off, size_t
     *out = bound;
     return RRX_OK;
 }
+// A one-call batch of items on `set` (`t`: its tables on `device`), the verdicts into `out`.
+// A large batch on a table with an items form runs stripe-wise over the byte buffer, the item ends taken from a bitmap built from
+// the offsets (kernels_items.hip: match_items_stripes_kernel) and the table a copy of the plain one with an END OF ITEM column.
+// Needs: the entry's own conditions (stripes_ok), trim 0 or 1, at most 126 table states, no item without a byte to carry its mark.
+// ASYNCHRONOUS: nothing is read back.  The host knows neither off[0] nor off[nitems]; it sizes the index for the most the batch can
+// span - what is left of the allocation that holds d_bytes - and the kernels take the real extent from the offsets.  Whether the
+// batch is fit (alignment, no degenerate item, large enough) is decided on the device: both kernels are queued, each predicated on
+// the index pass's fit flag - the stripe-wise kernel does nothing on an unfit batch (a bitmap copied out of its scratch: zeros) and
+// the lane-per-item kernel behind it, which writes every byte or word, nothing on a fit one.
+// (r4) trim 1 on a table with a stride-2 form: the stride-2 items table (it also serves automata whose byte-stride items table is
+// beyond the LDS - a{1,300}: 302 rows of 130 columns)
+static int extents_batch(const rrx_regex *re, TableSet &set, const DeviceTables *t, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems,
+                         uint32_t trim, bool stripes_ok, dev::ItemVerdicts out, void *stream) {
+    const uint8_t *b = static_cast<const uint8_t *>(d_bytes);
+    ItemsTable it;
+    if (stripes_ok && trim <= 1 && nitems >= kItemsStripesMin) it = pick_items_table(re, set, device, trim);
+    const bool items = it.items1 || it.items2;
+    size_t bound = 0;
+    if (items) {
+        const int rc = items_extent_bound(d_bytes, d_off, nitems, stream, &bound);
+        if (rc) return rc;
+    }
+    if (!items || bound < kItemsStripesMinBytes) return extents_lanes(re, set, t, b, d_off, nitems, trim, out, stream);
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(re->onepass_mu);
+    void *buf = nullptr;
+    const size_t ib = dev::items_index_bytes(bound, nitems);
+    int rc = re->onepass_for(device, ib + dev::items_result_bytes(nitems), &buf, st);      // (ordered behind the scratch's last user)
+    if (rc) return rc;
+    uint32_t *d_flag = nullptr;
+    int le = dev::items_index_build(bound, d_off, nitems, trim, buf, &d_flag, stream, b, kItemsStripesMinBytes);
+    if (!le) le = it.items2 ? dev::items_match2(*it.items2, b, bound, nitems, buf, static_cast<uint8_t *>(buf) + ib, out, stream, d_off, d_flag)
+                            : dev::items_match(*it.items1, b, bound, nitems, trim, buf, static_cast<uint8_t *>(buf) + ib, out, stream, d_off, d_flag);
+    if (!le) rc = extents_lanes(re, set, t, b, d_off, nitems, trim, out, stream, d_flag);
+    const int rc2 = re->onepass_done(device, st);                // (whatever was queued: the next user waits for it)
+    if (le) return hip_fail((hipError_t)le, (std::string(set.word) + "_items_stripes launch").c_str());
+    return rc ? rc : rc2;
+}
+// The match entries go stripe-wise only on the table engine and into a 16-byte aligned byte array (expand_bits)
+static bool match_stripes_ok(const rrx_regex *re, const uint8_t *d_accept) { return re->engine == RRX_ENGINE_DFA && !(reinterpret_cast<uintptr_t>(d_accept) & 15); }
 int rrx_match_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                       uint8_t *d_accept, void *stream) {
     if (!re || (nitems && (!d_off || !d_accept))) return fail(RRX_ERR_ARG, "null argument");
@@ -1168,41 +1185,7 @@ int rrx_match_extents(const rrx_regex *re, int device, const void *d_bytes, cons
     int rc = re->tables(device, &t);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(device));
-    const uint8_t *b = static_cast<const uint8_t *>(d_bytes);
-    // A large batch on a table engine runs stripe-wise over the byte buffer, the item ends taken from a bitmap built from
-    // the offsets (kernels_table.hip: match_items_stripes_kernel) and the table a copy of the plain one with an END OF ITEM
-    // column.  Needs: trim 0 or 1, at most 126 table states, 16-byte alignment, no item without a byte to carry its mark.
-    // ASYNCHRONOUS: nothing is read back.  The host knows neither off[0] nor off[nitems]; it sizes the index for the most
-    // the batch can span - what is left of the allocation that holds d_bytes - and the kernels take the real extent from the
-    // offsets.  Whether the batch is fit (alignment, no degenerate item, large enough) is decided on the device: the
-    // stripe-wise kernel does nothing on an unfit batch and the lane-per-item kernel queued behind it does nothing on a fit one.
-    // (r4) trim 1 on a regex with a stride-2 table: the stride-2 items table (it also serves automata whose byte-stride items table
-    // is beyond the LDS - a{1,300}: 302 rows of 130 columns)
-    ItemsTable it;
-    if (re->engine == RRX_ENGINE_DFA && trim <= 1 && nitems >= kItemsStripesMin && !(reinterpret_cast<uintptr_t>(d_accept) & 15)) it = pick_items_table(re, device, trim);
-    const bool items = it.items1 || it.items2;
-    size_t bound = 0;
-    if (items) {
-        rc = items_extent_bound(d_bytes, d_off, nitems, stream, &bound);
-        if (rc) return rc;
-    }
-    if (items && bound >= kItemsStripesMinBytes) {
-        hipStream_t st = (hipStream_t)stream;
-        std::lock_guard<std::mutex> lock(re->onepass_mu);
-        void *buf = nullptr;
-        const size_t ib = dev::items_index_bytes(bound, nitems);
-        rc = re->onepass_for(device, ib + dev::items_result_bytes(nitems), &buf, st);      // (ordered behind the scratch's last user)
-        if (rc) return rc;
-        uint32_t *d_flag = nullptr;
-        int le = dev::items_index_build(bound, d_off, nitems, trim, buf, &d_flag, stream, b, kItemsStripesMinBytes);
-        if (!le) le = it.items2 ? dev::items_match2(*it.items2, b, bound, nitems, buf, static_cast<uint8_t *>(buf) + ib, d_accept, stream, d_off, d_flag)
-                                : dev::items_match(*it.items1, b, bound, nitems, trim, buf, static_cast<uint8_t *>(buf) + ib, d_accept, stream, d_off, d_flag);
-        if (!le) rc = match_extents_lanes(re, t, b, d_off, nitems, trim, d_accept, stream, d_flag);
-        const int rc2 = re->onepass_done(device, st);            // (whatever was queued: the next user waits for it)
-        if (le) return hip_fail((hipError_t)le, "match_items_stripes launch");
-        return rc ? rc : rc2;
-    }
-    return match_extents_lanes(re, t, b, d_off, nitems, trim, d_accept, stream);
+    return extents_batch(re, re->match_set, t, device, d_bytes, d_off, nitems, trim, match_stripes_ok(re, d_accept), d_accept, stream);      // (no items: an empty launch)
 }
 
 // A batch of items indexed once (item-end bitmap + stripe base), matched by many patterns: rrx_corpus' counterpart for an
@@ -1216,15 +1199,15 @@ struct rrx_items {
     uint64_t first = 0;
     uint32_t trim = 0;
     bool stripes = false;
-    void *d_index = nullptr;
+    DeviceAlloc d_index;
     mutable std::mutex mu;
-    mutable void *d_result = nullptr;    // result bitmap of a match (one match at a time per handle)
+    DeviceAlloc d_result;                // result bitmap of a match (one match at a time per handle)
 };
 int rrx_items_create(int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, void *stream, rrx_items **out) {
     if (!out || (nitems && (!d_bytes || !d_off))) return fail(RRX_ERR_ARG, "null argument");
     *out = nullptr;
     HIP_TRY(hipSetDevice(device));
-    rrx_items *it = new rrx_items();
+    std::unique_ptr<rrx_items> it(new rrx_items());      // (its device memory goes with it on every early return)
     it->device = device; it->d_bytes = static_cast<const uint8_t *>(d_bytes); it->d_off = d_off; it->nitems = nitems; it->trim = trim;
     hipStream_t st = (hipStream_t)stream;
     if (nitems && trim <= 1) {
@@ -1232,32 +1215,37 @@ int rrx_items_create(int device, const void *d_bytes, const uint64_t *d_off, siz
         hipError_t e = hipMemcpyAsync(&first, d_off, sizeof first, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(&last, d_off + nitems, sizeof last, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { delete it; return hip_fail(e, "items offsets readback"); }
+        if (e != hipSuccess) return hip_fail(e, "items offsets readback");
         it->first = first;
         if (last > first && !(reinterpret_cast<uintptr_t>(it->d_bytes + first) & 15)) {
             it->nbytes = (size_t)(last - first);
-            e = hipMalloc(&it->d_index, dev::items_index_bytes(it->nbytes, nitems));
-            if (e == hipSuccess) e = hipMalloc(&it->d_result, dev::items_result_bytes(nitems));
-            if (e != hipSuccess) { rrx_items_free(it); return hip_fail(e, "hipMalloc(items index)"); }
+            e = it->d_index.alloc(device, dev::items_index_bytes(it->nbytes, nitems));
+            if (e == hipSuccess) e = it->d_result.alloc(device, dev::items_result_bytes(nitems));
+            if (e != hipSuccess) return hip_fail(e, "hipMalloc(items index)");
             uint32_t *d_flag = nullptr;
-            int le = dev::items_index_build(it->nbytes, d_off, nitems, trim, it->d_index, &d_flag, stream);
+            int le = dev::items_index_build(it->nbytes, d_off, nitems, trim, it->d_index.p, &d_flag, stream);
             uint32_t degenerate = 1;
             if (!le) { e = hipMemcpyAsync(&degenerate, d_flag, sizeof degenerate, hipMemcpyDeviceToHost, st); if (e == hipSuccess) e = hipStreamSynchronize(st); }
-            if (le || e != hipSuccess) { rrx_items_free(it); return le ? hip_fail((hipError_t)le, "items index launch") : hip_fail(e, "items index"); }
+            if (le || e != hipSuccess) return le ? hip_fail((hipError_t)le, "items index launch") : hip_fail(e, "items index");
             it->stripes = degenerate == 0;
         }
     }
-    *out = it;
+    *out = it.release();
     return RRX_OK;
 }
 size_t rrx_items_count(const rrx_items *it) { return it ? it->nitems : 0; }
 int rrx_items_stripe_wise(const rrx_items *it) { return it && it->stripes ? 1 : 0; }
-void rrx_items_free(rrx_items *it) {
-    if (!it) return;
-    (void)hipSetDevice(it->device);
-    if (it->d_index) (void)hipFree(it->d_index);
-    if (it->d_result) (void)hipFree(it->d_result);
-    delete it;
+void rrx_items_free(rrx_items *it) { delete it; }
+
+// An indexed batch on `set` (`t`: its tables on the batch's device): stripe-wise where the index admits it (it said so once: no
+// second attempt), the entry's own conditions hold (stripes_ok) and the set has an items table; else a lane per item.
+static int items_batch(const rrx_regex *re, TableSet &set, const DeviceTables *t, const rrx_items *it, bool stripes_ok, dev::ItemVerdicts out, void *stream) {
+    const ItemsTable tab = it->stripes && stripes_ok ? pick_items_table(re, set, it->device, it->trim) : ItemsTable();
+    if (!tab.items1 && !tab.items2) return extents_lanes(re, set, t, it->d_bytes, it->d_off, it->nitems, it->trim, out, stream);
+    std::lock_guard<std::mutex> lock(it->mu);
+    const int le = tab.items2 ? dev::items_match2(*tab.items2, it->d_bytes + it->first, it->nbytes, it->nitems, it->d_index.p, it->d_result.p, out, stream)
+                              : dev::items_match(*tab.items1, it->d_bytes + it->first, it->nbytes, it->nitems, it->trim, it->d_index.p, it->d_result.p, out, stream);
+    return le ? hip_fail((hipError_t)le, (std::string(set.word) + "_items launch").c_str()) : RRX_OK;
 }
 int rrx_match_items(const rrx_regex *re, const rrx_items *it, uint8_t *d_accept, void *stream) {
     if (!re || !it || (it->nitems && !d_accept)) return fail(RRX_ERR_ARG, "null argument");
@@ -1266,34 +1254,12 @@ int rrx_match_items(const rrx_regex *re, const rrx_items *it, uint8_t *d_accept,
     int rc = re->tables(it->device, &t);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(it->device));
-    if (it->stripes && re->engine == RRX_ENGINE_DFA && !(reinterpret_cast<uintptr_t>(d_accept) & 15)) {
-        const ItemsTable tab = pick_items_table(re, it->device, it->trim);
-        if (tab.items1 || tab.items2) {
-            std::lock_guard<std::mutex> lock(it->mu);
-            int le = tab.items2 ? dev::items_match2(*tab.items2, it->d_bytes + it->first, it->nbytes, it->nitems, it->d_index, it->d_result, d_accept, stream)
-                                : dev::items_match(*tab.items1, it->d_bytes + it->first, it->nbytes, it->nitems, it->trim, it->d_index, it->d_result, d_accept, stream);
-            return launched(le, "match_items launch");
-        }
-    }
-    // the batch or the pattern does not admit the stripe-wise kernel (the index said so once: no second attempt)
-    return match_extents_lanes(re, t, it->d_bytes, it->d_off, it->nitems, it->trim, d_accept, stream);
+    return items_batch(re, re->match_set, t, it, match_stripes_ok(re, d_accept), d_accept, stream);
 }
 
-// ---- "which items contain a match": rrx_match_extents / rrx_match_items decision for decision, on the contains tables - the
-// stripe-wise items kernels where the contains table has an items form (whatever the regex' MATCH engine is), the lane-per-item
-// kernel of kernels_contains_items.hip elsewhere.  The stripe-wise kernels write into scratch (padded, bit nitems may be set); the
-// caller's bitmap receives a masked copy.
-static int contains_extents_lanes(const rrx_regex *re, const DeviceTables *t, const uint8_t *b, const uint64_t *d_off, size_t nitems, uint32_t trim,
-                                  uint32_t *d_bits, void *stream, const uint32_t *only_if = nullptr) {
-    return launched(dev::contains_extents_dfa(t->dfa, re->contains.global, re->contains_found, b, d_off, nitems, trim, d_bits, stream, only_if),
-                    "contains_extents launch");
-}
-static ItemsTable pick_contains_items_table(const rrx_regex *re, int device, uint32_t trim) {
-    ItemsTable t;
-    if (trim == 1 && re->items_stride2.load()) t.items2 = re->contains_items2_table(device);
-    if (!t.items2) t.items1 = re->contains_items_table(device);
-    return t;
-}
+// "Which items contain a match": the same two paths on the contains set - stripe-wise wherever the contains table has an items form,
+// whatever the regex' MATCH engine is and at any alignment of the bitmap (the stripe-wise kernels write into scratch, the caller's
+// bitmap receives a masked copy).  An empty batch still reports a regex without a contains table.
 int rrx_contains_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                          uint32_t *d_bits, void *stream) {
     if (!re || (nitems && (!d_off || !d_bits))) return fail(RRX_ERR_ARG, "null argument");
@@ -1302,34 +1268,7 @@ int rrx_contains_extents(const rrx_regex *re, int device, const void *d_bytes, c
     if (rc) return rc;
     HIP_TRY(hipSetDevice(device));
     if (!nitems) return RRX_OK;
-    const uint8_t *b = static_cast<const uint8_t *>(d_bytes);
-    ItemsTable it;
-    if (trim <= 1 && nitems >= kItemsStripesMin) it = pick_contains_items_table(re, device, trim);
-    const bool items = it.items1 || it.items2;
-    size_t bound = 0;
-    if (items) {
-        rc = items_extent_bound(d_bytes, d_off, nitems, stream, &bound);
-        if (rc) return rc;
-    }
-    if (items && bound >= kItemsStripesMinBytes) {
-        // both kernels are queued, each predicated on the index pass's fit flag: on an unfit batch the copy out of the scratch gives
-        // zeros and the lane-per-item kernel behind it rewrites every word
-        hipStream_t st = (hipStream_t)stream;
-        std::lock_guard<std::mutex> lock(re->onepass_mu);
-        void *buf = nullptr;
-        const size_t ib = dev::items_index_bytes(bound, nitems);
-        rc = re->onepass_for(device, ib + dev::items_result_bytes(nitems), &buf, st);      // (ordered behind the scratch's last user)
-        if (rc) return rc;
-        uint32_t *d_flag = nullptr;
-        int le = dev::items_index_build(bound, d_off, nitems, trim, buf, &d_flag, stream, b, kItemsStripesMinBytes);
-        if (!le) le = it.items2 ? dev::items_contains2(*it.items2, b, bound, nitems, buf, static_cast<uint8_t *>(buf) + ib, d_bits, stream, d_off, d_flag)
-                                : dev::items_contains(*it.items1, b, bound, nitems, trim, buf, static_cast<uint8_t *>(buf) + ib, d_bits, stream, d_off, d_flag);
-        if (!le) rc = contains_extents_lanes(re, t, b, d_off, nitems, trim, d_bits, stream, d_flag);
-        const int rc2 = re->onepass_done(device, st);            // (whatever was queued: the next user waits for it)
-        if (le) return hip_fail((hipError_t)le, "contains_items_stripes launch");
-        return rc ? rc : rc2;
-    }
-    return contains_extents_lanes(re, t, b, d_off, nitems, trim, d_bits, stream);
+    return extents_batch(re, re->contains_set, t, device, d_bytes, d_off, nitems, trim, /*stripes_ok=*/true, d_bits, stream);
 }
 int rrx_contains_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_bits, void *stream) {
     if (!re || !it || (it->nitems && !d_bits)) return fail(RRX_ERR_ARG, "null argument");
@@ -1338,17 +1277,7 @@ int rrx_contains_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_bit
     if (rc) return rc;
     HIP_TRY(hipSetDevice(it->device));
     if (!it->nitems) return RRX_OK;
-    if (it->stripes) {
-        const ItemsTable tab = pick_contains_items_table(re, it->device, it->trim);
-        if (tab.items1 || tab.items2) {
-            std::lock_guard<std::mutex> lock(it->mu);
-            int le = tab.items2 ? dev::items_contains2(*tab.items2, it->d_bytes + it->first, it->nbytes, it->nitems, it->d_index, it->d_result, d_bits, stream)
-                                : dev::items_contains(*tab.items1, it->d_bytes + it->first, it->nbytes, it->nitems, it->trim, it->d_index, it->d_result, d_bits, stream);
-            return launched(le, "contains_items launch");
-        }
-    }
-    // the batch or the pattern does not admit the stripe-wise kernel
-    return contains_extents_lanes(re, t, it->d_bytes, it->d_off, it->nitems, it->trim, d_bits, stream);
+    return items_batch(re, re->contains_set, t, it, /*stripes_ok=*/true, d_bits, stream);
 }
 
 // One device-resident string of any length.  Long strings take the chunk-map path when the automaton has a small

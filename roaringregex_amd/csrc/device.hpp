@@ -222,20 +222,21 @@ size_t items_result_bytes(size_t nitems);                // result bitmap of one
 // kernel (items_match then does nothing when handed the flag as skip_if)
 int items_index_build(size_t nbytes, const uint64_t *off, size_t nitems, uint32_t trim, void *index, uint32_t **flag, void *stream,
                       const uint8_t *resolve_base = nullptr, size_t min_bytes = 0);
-// explicit items with separators (trim 1) on the stride-2 table of their own (lower_dfa2's items form; P of kDfa2PItemsBytes):
-// the arguments of items_match below
-int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, uint8_t *accept, void *stream,
+// Where the verdicts of a stripe-wise launch go, out of its result bitmap: one byte per item into `bytes` (16-byte aligned;
+// expand_bits), or the bitmap itself into `bits` - ceil(nitems / 32) words at any 4-byte alignment, the bits of the last word beyond
+// nitems 0 (copy_result_bits); an unfit batch (*skip_if != 0) leaves zeros there.
+struct ItemVerdicts {
+    uint8_t *bytes = nullptr;
+    uint32_t *bits = nullptr;
+    ItemVerdicts(uint8_t *b) : bytes(b) {}
+    ItemVerdicts(uint32_t *w) : bits(w) {}
+};
+// The stripe-wise kernels on an items table - of the match table or of the contains table: the kernels are the same.  items_match2:
+// explicit items with separators (trim 1) on the stride-2 table of their own (lower_dfa2's items form; P of kDfa2PItemsBytes).
+int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, ItemVerdicts out, void *stream,
                  const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
 int items_match(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
-                uint8_t *accept, void *stream, const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
-
-// the same kernels on the contains items tables (rrx_contains_extents / rrx_contains_items): the arguments of items_match2 /
-// items_match, but the result is the bitmap itself - ceil(nitems / 32) words into `bits` (any 4-byte alignment), the bits of the
-// last word beyond nitems 0; an unfit batch (*skip_if != 0) leaves zeros
-int items_contains2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, uint32_t *bits, void *stream,
-                    const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
-int items_contains(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
-                   uint32_t *bits, void *stream, const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
+                ItemVerdicts out, void *stream, const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
 
 // ---- contains for explicit items, a lane per item: kernels_contains_items.hip
 // `p`: the contains table in its plain form ('\n', NUL and bytes >= 0x80 are ordinary bytes of their class; nothing kills).

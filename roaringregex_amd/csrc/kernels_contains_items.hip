@@ -1,6 +1,6 @@
 // kernels_contains_items.hip — "which items contain a match" (rrx_contains_extents / rrx_contains_items): the lane-per-item
 // kernel on the plain contains table and the copy of a stripe-wise result out of its scratch bitmap.  The stripe-wise forms are
-// the items kernels themselves on the contains items tables (kernels_items.hip: items_contains / items_contains2).
+// the items kernels themselves on the contains items tables (kernels_items.hip: items_match / items_match2).
 #include "table_engines.hpp"
 
 namespace rrx {

@@ -482,27 +482,20 @@ static int items_run(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes
     }
     return (int)hipGetLastError();
 }
-// one byte per item into `accept` (16-byte aligned)
-int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, uint8_t *accept, void *stream,
+// ... and the verdicts out of `result` to where the caller wants them (device.hpp: ItemVerdicts)
+static int items_deliver(const void *result, size_t nitems, ItemVerdicts out, void *stream) {
+    const uint32_t *bits = static_cast<const uint32_t *>(result);
+    return out.bits ? copy_result_bits(bits, nitems, out.bits, stream) : expand_bits(bits, nitems, out.bytes, stream);
+}
+int items_match2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, ItemVerdicts out, void *stream,
                  const uint64_t *resolve_off, const uint32_t *skip_if) {
     const int rc = items_run2(p, bytes, nbytes, nitems, index, result, stream, resolve_off, skip_if);
-    return rc ? rc : expand_bits(static_cast<const uint32_t *>(result), nitems, accept, stream);
+    return rc ? rc : items_deliver(result, nitems, out, stream);
 }
 int items_match(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
-                uint8_t *accept, void *stream, const uint64_t *resolve_off, const uint32_t *skip_if) {
+                ItemVerdicts out, void *stream, const uint64_t *resolve_off, const uint32_t *skip_if) {
     const int rc = items_run(p, bytes, nbytes, nitems, trim, index, result, stream, resolve_off, skip_if);
-    return rc ? rc : expand_bits(static_cast<const uint32_t *>(result), nitems, accept, stream);
-}
-// the same kernels on the contains items tables: ceil(nitems / 32) words into `bits`, the bits of the last word beyond nitems 0
-int items_contains2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, size_t nitems, const void *index, void *result, uint32_t *bits, void *stream,
-                    const uint64_t *resolve_off, const uint32_t *skip_if) {
-    const int rc = items_run2(p, bytes, nbytes, nitems, index, result, stream, resolve_off, skip_if);
-    return rc ? rc : copy_result_bits(static_cast<const uint32_t *>(result), nitems, bits, stream);
-}
-int items_contains(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, size_t nitems, uint32_t trim, const void *index, void *result,
-                   uint32_t *bits, void *stream, const uint64_t *resolve_off, const uint32_t *skip_if) {
-    const int rc = items_run(p, bytes, nbytes, nitems, trim, index, result, stream, resolve_off, skip_if);
-    return rc ? rc : copy_result_bits(static_cast<const uint32_t *>(result), nitems, bits, stream);
+    return rc ? rc : items_deliver(result, nitems, out, stream);
 }
 
 }  // namespace dev

@@ -31,6 +31,15 @@ void LineTables::pack(const std::vector<uint32_t> &rows, const std::vector<uint3
     pack_dfa_tables(dfa, wide, global, has_dfa2 ? &dfa2 : nullptr, rows, cols, img, t);
 }
 
+bool ItemsForms::stride2(const LineTables &lt) {
+    if (lt.has_dfa2 && state2 == 0) state2 = lower_dfa2_that_fits(lt.dfa, dfa2, /*items=*/true) ? 1 : 2;
+    return state2 == 1;
+}
+bool ItemsForms::pack(const LineTables &lt, Image &img, dev::LineDfaDevice &t) const { return pack_items(lt.dfa, img, t); }
+bool ItemsForms::pack2(const LineTables &lt, Image &img, dev::Dfa2Device &t) {
+    return stride2(lt) && pack_dfa2(dfa2, {}, {}, img, t, dev::kDfa2PItemsBytes);
+}
+
 void plan_engines(const std::string &pattern, int engine, Programs &p) {
     p.ref = build_reference_automaton(pattern);
     p.trimmed = trim(p.ref);

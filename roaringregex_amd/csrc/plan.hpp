@@ -39,6 +39,18 @@ struct LineTables {
     void pack(const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, Image &img, DeviceTables &t) const;
 };
 
+// The items tables of one LineTables, host side (explicit items stepped stripe-wise: kernels_items.hip).  The byte-stride form is
+// pack_items on the table's DFA.  The stride-2 form (items with a separator byte each, trim 1) is lower_dfa2's items form - one
+// symbol more than the line table's -, lowered at its first use, and only where the line table has a stride-2 form at all.
+struct ItemsForms {
+    Dfa2Program dfa2;            // the stride-2 items program (where stride2() holds)
+    bool stride2(const LineTables &lt);          // false: `lt` has no stride-2 form, or the items form does not fit the same LDS region
+    bool pack(const LineTables &lt, Image &img, dev::LineDfaDevice &t) const;       // false: more states than 16-bit row offsets allow
+    bool pack2(const LineTables &lt, Image &img, dev::Dfa2Device &t);               // false: no stride2()
+private:
+    int state2 = 0;              // 0 not tried, 1 there, 2 does not fit
+};
+
 // What a pattern compiles to.  `engine`: the RRX_ENGINE_* it runs on, 0 where none admits the automaton.
 struct Programs {
     RefAutomaton ref;

@@ -123,10 +123,23 @@ void random_order(const Dfa2Program &p, std::mt19937 &rng, std::vector<uint32_t>
     std::shuffle(cols.begin(), cols.end(), rng);
 }
 
-void check_items(const DfaProgram &dfa) {
+// The items tables of `dfa` as the library forms them (ItemsForms): the stride-2 items table where the DFA has a stride-2 form
+// (has_dfa2) and the items form fits, and the byte-stride items table.
+void check_items(const DfaProgram &dfa, bool has_dfa2) {
+    LineTables lt;
+    lt.dfa = dfa; lt.has_dfa2 = has_dfa2;
+    ItemsForms forms;
+    if (forms.stride2(lt)) {
+        Image img2;
+        dev::Dfa2Device d2;
+        CHECK(forms.pack2(lt, img2, d2));
+        Copy cp2(img2);
+        CHECK(cp2.at(d2.P) == 0);
+        decode_dfa2(forms.dfa2, {}, {}, dev::kDfa2PItemsBytes, d2, cp2);
+    }
     Image img;
     dev::LineDfaDevice L;
-    if (!pack_items(dfa, img, L)) return;
+    if (!forms.pack(lt, img, L)) return;
     Copy cp(img);
     const uint32_t R = 1u << L.rep_log2, S = L.stride / R, row_bytes = L.stride * 4;
     CHECK(S == dev::kItemColumns && L.wide == 1 && L.start_off == dfa.start * row_bytes);
@@ -283,9 +296,7 @@ void check_images(const Trimmed &t, const Reduced &r, const NfaProgram *nfa, con
         if (wide_fits(*dfa)) check_line(*dfa, true, false);
         if (classed_fits(*dfa)) check_line(*dfa, false, false);
         if (global_fits(*dfa)) check_line(*dfa, false, true);
-        check_items(*dfa);
-        Dfa2Program items;
-        if (dfa2 && lower_dfa2_that_fits(*dfa, items, /*items=*/true)) check_dfa2(items, {}, {}, dev::kDfa2PItemsBytes);
+        check_items(*dfa, dfa2 != nullptr);
     }
     if (dfa2 && dfa2_fits(*dfa2)) {
         std::vector<uint32_t> rows, cols;

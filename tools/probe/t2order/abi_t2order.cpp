@@ -4,7 +4,7 @@
 extern "C" int rrx_probe_set_t2_order(rrx_regex *re, const uint32_t *row_slot, uint32_t nrows, const uint32_t *col_slot, uint32_t ncols) {
     if (!re->match.has_dfa2 || nrows != re->match.dfa2.nstates || ncols != re->match.dfa2.ncols || row_slot[0] != 0) return fail(RRX_ERR_ARG, "order does not fit the table");
     std::lock_guard<std::mutex> lock(re->mu);
-    if (!re->on_device.empty()) return fail(RRX_ERR_ARG, "tables already uploaded");
+    if (!re->match_set.on_device.empty()) return fail(RRX_ERR_ARG, "tables already uploaded");
     re->t2_row_slot.assign(row_slot, row_slot + nrows);
     re->t2_col_slot.assign(col_slot, col_slot + ncols);
     return RRX_OK;
