@@ -75,12 +75,14 @@ int         rrx_order_table(rrx_regex *re, const void *sample, uint32_t lanes, u
  * first rrx_match_corpus; a search that is already running is not stopped.  RRX_ERR_ARG for an unknown option.          */
 /* RRX_OPT_FLUSH_SLOTS (default 0 = automatic): the stride-2 batch kernel lets all lanes flush their result bits together every
  * `value` slots (16 bytes of a lane's text; 1, 2, 4, 8, 16 or 32); automatic: from the corpus' mean line length, about eight
- * line ends per period.  A tuning knob: results never depend on it.                                                       */
+ * line ends per period.  A tuning knob: results never depend on it.  A period of 32 - the automatic choice from 33 bytes per
+ * line on - runs the kernel that has it compiled in, every other one the kernel that takes it per launch
+ * (rrx_match_flush_slots tells which).                                                                                    */
 /* RRX_OPT_SAMPLED_TABLE (default 1): 0 keeps an automaton whose subset construction explodes on the NFA lane engine for every
  * launch (see rrx_learn_table).                                                                                          */
-/* RRX_OPT_UNITS_PER_WORKGROUP (default 0 = off): the stride-2 batch kernel hands its stripes out in units of 64 inside the
- * workgroup, `value` (16 ... 65536) of them per workgroup of 16 waves, a wave taking its next unit from a counter in LDS.
- * Same results; measured no faster than one stripe per lane on any config (profiles/r04_unit_handout_ab.txt).           */
+/* RRX_OPT_UNITS_PER_WORKGROUP: ACCEPTED AND IGNORED.  It chose a kernel that handed its stripes out in units of 64 inside the
+ * workgroup; that kernel was no faster on any config (profiles/r04_unit_handout_ab.txt) and is gone.  The value is still
+ * checked (0 ... 65536, RRX_ERR_ARG otherwise) so that callers written for it keep working; it changes nothing.          */
 /* RRX_OPT_SEARCH_ANCHORED (default 1): the search kernels' forward table is the product of "any bytes, then the pattern" with
  * the pattern's own table, which tells the matches that start at the line start (no walk back to find the start); 0 builds the
  * forward table alone - fewer rows, every match start walked back to - which is also what a product beyond 65534 rows falls
@@ -159,9 +161,20 @@ size_t rrx_corpus_num_lines(const rrx_corpus *c);
 size_t rrx_corpus_num_bytes(const rrx_corpus *c);
 void   rrx_corpus_free(rrx_corpus *c);
 size_t rrx_corpus_bitmap_words(const rrx_corpus *c);   /* 32-bit words of the accept bitmap: ceil(lines / 32) */
+/* 1: the stride-2 table kernel can run on this corpus as ONE launch, without the clear of the bitmap in front of it - every
+ * workgroup stores the bitmap words it alone writes, and a word it shares with its neighbour is settled through an exchange slot
+ * (DESIGN.md 6.1).  0: some bitmap word lies in the line ranges of three workgroups (lines longer than a workgroup's text:
+ * 1024 stripes) - every launch clears the bitmap and merges with atomics, as every other engine does.  Decided once, with the
+ * index.  *span_words (may be NULL): the longest run of bitmap words of one workgroup behind its first; a regex whose table
+ * leaves a shorter result window in LDS (1024 ... 11776 words, by the size of its table) takes the clear on this corpus too,
+ * and so does a launch on a stream that is being captured.  Read-only.                                                     */
+int    rrx_corpus_one_launch(const rrx_corpus *c, uint32_t *span_words);
+/* The common flush period, in slots, of the stride-2 table kernel for this regex on this corpus (RRX_OPT_FLUSH_SLOTS, or the
+ * automatic choice); *compiled_in (may be NULL) = 1 if that is the kernel with the period compiled in.  Read-only.         */
+uint32_t rrx_match_flush_slots(const rrx_regex *re, const rrx_corpus *c, int *compiled_in);
 /* THE HOT PATH.  Writes the accept BITMAP: bit (i & 31) of d_accept_bits[i >> 5] = 1 iff string i is accepted
  * (i.e. *it has a value, regex.h:160-162; its Match is then [start of string i, its terminator)).
- * d_accept_bits holds rrx_corpus_bitmap_words() words; it is zeroed and filled on `stream`.                  */
+ * d_accept_bits holds rrx_corpus_bitmap_words() words; every one of them is written on `stream`, whatever it held.  */
 int rrx_match_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_accept_bits, void *stream);
 /* The same for a device-resident buffer that has no rrx_corpus yet, in ONE call: with the lane engines (tables, NFA) the
  * text is read once (the newline index is a by-product of the match: per-stripe counts, a scan, a compaction of the

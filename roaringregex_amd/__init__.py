@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "rrx_engine", "rrx_engine_name", "rrx_useful_states", "rrx_byte_classes", "rrx_table_order", "rrx_order_table", "rrx_set_option", "rrx_learn_table", "rrx_sampled_table", "rrx_sampled_escapes", "rrx_words_per_set", "rrx_accepts_empty",
     "rrx_program_words",
     "rrx_corpus_create", "rrx_corpus_create_ex", "rrx_corpus_stripe_bytes", "rrx_corpus_num_lines", "rrx_corpus_num_bytes", "rrx_corpus_free", "rrx_corpus_bitmap_words",
+    "rrx_corpus_one_launch", "rrx_match_flush_slots",
     "rrx_match_corpus", "rrx_match_device", "rrx_search_corpus", "rrx_search_all_count", "rrx_search_all_fill", "rrx_search_all", "rrx_bitmap_to_bytes",
     "rrx_match_extents", "rrx_items_create", "rrx_items_count", "rrx_items_stripe_wise", "rrx_items_free", "rrx_match_items",
     "rrx_match_string", "rrx_match_host", "rrx_match_cstr",
@@ -95,6 +96,8 @@ def _load():
         "rrx_corpus_num_bytes": (sz, [vp]),
         "rrx_corpus_free": (None, [vp]),
         "rrx_corpus_bitmap_words": (sz, [vp]),
+        "rrx_corpus_one_launch": (i32, [vp, C.POINTER(u32)]),
+        "rrx_match_flush_slots": (u32, [vp, vp, C.POINTER(i32)]),
         "rrx_match_corpus": (i32, [vp, vp, vp, vp]),
         "rrx_match_device": (i32, [vp, i32, vp, sz, vp, sz, C.POINTER(sz), vp]),
         "rrx_bitmap_to_bytes": (i32, [i32, vp, sz, vp, vp]),
@@ -245,6 +248,19 @@ class Corpus:
     @property
     def stripe(self):
         return _L.rrx_corpus_stripe_bytes(self._h)
+
+    @property
+    def one_launch(self):
+        """True if the stride-2 table kernel needs no cleared bitmap on this corpus (rrx_corpus_one_launch): no bitmap word
+        lies in the line ranges of three workgroups."""
+        return bool(_L.rrx_corpus_one_launch(self._h, None))
+
+    @property
+    def one_launch_span(self):
+        """The longest run of bitmap words of one workgroup behind its first (0 where one_launch is False)."""
+        span = C.c_uint32(0)
+        _L.rrx_corpus_one_launch(self._h, C.byref(span))
+        return span.value
 
 
 class Items:
@@ -620,6 +636,13 @@ class RRegex:
         """rrx_set_option(RRX_OPT_FLUSH_SLOTS): 0 = automatic, or 1 ... 32 slots between two common flushes of the stride-2 kernel."""
         _check(_L.rrx_set_option(self._h, OPT_FLUSH_SLOTS, int(slots)))
 
+    def flush_slots(self, corpus):
+        """(slots, compiled_in): the stride-2 kernel's common flush period for this regex on `corpus`, and whether it is the
+        kernel with the period compiled in (rrx_match_flush_slots)."""
+        fixed = C.c_int(0)
+        slots = _L.rrx_match_flush_slots(self._h, corpus._h, C.byref(fixed))
+        return slots, bool(fixed.value)
+
     def set_search_anchored(self, enabled):
         """rrx_set_option(RRX_OPT_SEARCH_ANCHORED): False builds the search kernels' forward table without the product that tells
         the matches starting at the line start (fewer rows; every match start is walked back to).  Before the first search."""
@@ -631,8 +654,8 @@ class RRegex:
         _check(_L.rrx_set_option(self._h, OPT_ITEMS_STRIDE2, 1 if enabled else 0))
 
     def set_units_per_workgroup(self, units):
-        """rrx_set_option(RRX_OPT_UNITS_PER_WORKGROUP): the stride-2 batch kernel hands its stripes out in units of 64 inside
-        the workgroup, `units` of them per workgroup (0: one stripe per lane and launch)."""
+        """rrx_set_option(RRX_OPT_UNITS_PER_WORKGROUP): accepted and ignored - the kernel that handed its stripes out in units
+        inside the workgroup is gone (it never won); the value is still checked (0 ... 65536)."""
         _check(_L.rrx_set_option(self._h, OPT_UNITS_PER_WORKGROUP, int(units)))
 
     @property

@@ -153,7 +153,6 @@ struct rrx_regex : Programs {                            // (plan.hpp: the progr
     mutable Dfa2OrderStats t2_order_stats;               // (under `mu`)
     std::atomic<int> opt_background_order{1};            // RRX_OPT_BACKGROUND_ORDER
     std::atomic<int> opt_search_anchored{1};             // RRX_OPT_SEARCH_ANCHORED
-    std::atomic<int> opt_units_per_wg{0};                // RRX_OPT_UNITS_PER_WORKGROUP (0: one stripe per lane and launch)
     std::atomic<int> opt_sampled_table{1};               // RRX_OPT_SAMPLED_TABLE
     std::atomic<int> opt_flush_slots{0};                 // RRX_OPT_FLUSH_SLOTS (0: from the corpus' mean line length)
     // ---- the sampled table: AUTO ended on the NFA lane engine because the subset construction explodes; the sets a
@@ -466,9 +465,17 @@ struct rrx_corpus {
     const uint8_t *d_bytes = nullptr;
     size_t nbytes = 0, nstripes = 0, nlines = 0;
     uint32_t stripe = 0;            // bytes per lane for this corpus
-    uint32_t *d_counts = nullptr;   // [nstripes] newlines per stripe, then one flags word
+    uint32_t *d_counts = nullptr;   // [nstripes] newlines per stripe, then one flags word and the two of dev::own_words_check
     uint64_t *d_base = nullptr;     // [nstripes+1] exclusive prefix
     bool has_high = false;          // some byte >= 0x80 occurs
+    // The stride-2 batch kernel without a cleared bitmap (dev::match_stripes_dfa2 with exchange slots), decided with the index:
+    // no bitmap word lies in the ranges of three workgroups, and the longest range is own_span words past its first one (a
+    // regex whose LDS window is shorter takes the clear).  The slot arrays: one per stream that has matched this corpus - the
+    // launches of one stream are ordered, which is all the exchange needs -, zeroed once, all zero again after every launch.
+    bool own_words = false;
+    uint32_t own_span = 0;
+    static constexpr size_t kMaxSlotArrays = 64;         // (streams beyond these take the clear)
+    mutable std::map<hipStream_t, unsigned long long *> slot_arrays;      // (under `mu`)
     // A sample of the text as the batch kernel's half-waves see it - the first kSampleBytes bytes of kSampleGroups x 32
     // consecutive stripes, lane-major, in pinned host memory - taken with the index on large corpora: what a table engine
     // orders its table by at its first match (order_dfa2).  nullptr: none.
@@ -598,9 +605,8 @@ int rrx_set_option(rrx_regex *re, int option, int64_t value) {
         re->opt_search_anchored.store(value ? 1 : 0);
         return RRX_OK;
     }
-    if (option == RRX_OPT_UNITS_PER_WORKGROUP) {
+    if (option == RRX_OPT_UNITS_PER_WORKGROUP) {             // the kernel is gone: the value is checked as it was, and ignored
         if (value < 0 || value > 65536) return fail(RRX_ERR_ARG, "units per workgroup: 0 (off) or 16 ... 65536");
-        re->opt_units_per_wg.store(value && value < 16 ? 16 : (int)value);
         return RRX_OK;
     }
     return fail(RRX_ERR_ARG, "unknown option");
@@ -661,7 +667,7 @@ int rrx_corpus_create(int device, const void *d_bytes, size_t nbytes, void *stre
 int rrx_corpus_create_ex(int device, const void *d_bytes, size_t nbytes, uint32_t stripe_bytes, void *stream, rrx_corpus **out) {
     if (!out || (nbytes && !d_bytes)) return fail(RRX_ERR_ARG, "null argument");
     if (stripe_bytes && (stripe_bytes < dev::kMinStripe || stripe_bytes > dev::kMaxStripe || (stripe_bytes & (stripe_bytes - 1))))
-        return fail(RRX_ERR_ARG, "stripe must be a power of two in [1024, 16384]");
+        return fail(RRX_ERR_ARG, "stripe must be a power of two in [512, 16384]");
     if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(RRX_ERR_ARG, "corpus base must be 16-byte aligned");
     *out = nullptr;
     HIP_TRY(hipSetDevice(device));
@@ -681,14 +687,15 @@ int rrx_corpus_create_ex(int device, const void *d_bytes, size_t nbytes, uint32_
         }
     }
     c->nstripes = (nbytes + c->stripe - 1) / c->stripe;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->d_counts), (c->nstripes + 1) * sizeof(uint32_t));
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->d_counts), (c->nstripes + 3) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->d_base), (c->nstripes + 1 + dev::scan_scratch_words(c->nstripes)) * sizeof(uint64_t));
     if (e != hipSuccess) { rrx_corpus_free(c); return hip_fail(e, "hipMalloc(line index)"); }
     uint32_t *d_flags = c->d_counts + c->nstripes;
-    e = hipMemsetAsync(d_flags, 0, sizeof(uint32_t), (hipStream_t)stream);
+    e = hipMemsetAsync(d_flags, 0, 3 * sizeof(uint32_t), (hipStream_t)stream);
     if (e != hipSuccess) { rrx_corpus_free(c); return hip_fail(e, "hipMemsetAsync(flags)"); }
     int rc = dev::count_newlines_per_stripe(c->d_bytes, nbytes, c->stripe, c->d_counts, c->nstripes, d_flags, stream);
     if (!rc) rc = dev::scan_counts(c->d_counts, c->d_base, c->d_base + c->nstripes + 1, c->nstripes, stream);
+    if (!rc && c->nstripes) rc = dev::own_words_check(c->d_base, c->nstripes, c->d_bytes + nbytes - 1, d_flags + 1, stream);
     if (rc) { rrx_corpus_free(c); return hip_fail((hipError_t)rc, "line index launch"); }
     MailboxGuard mail;
     if (int mrc = mailbox_acquire(device, &mail.m)) { rrx_corpus_free(c); return mrc; }
@@ -707,7 +714,7 @@ int rrx_corpus_create_ex(int device, const void *d_bytes, size_t nbytes, uint32_
         }
     }
     mail.stream = (hipStream_t)stream; mail.queued = true;
-    rc = dev::mail_results(c->d_base + c->nstripes, d_flags, nbytes ? c->d_bytes + nbytes - 1 : nullptr, mail.m.dev, stream);
+    rc = dev::mail_results(c->d_base + c->nstripes, d_flags, nbytes ? c->d_bytes + nbytes - 1 : nullptr, mail.m.dev, stream, d_flags + 1);
     if (rc) { rrx_corpus_free(c); return hip_fail((hipError_t)rc, "line index launch"); }
     e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) { rrx_corpus_free(c); return hip_fail(e, "line index readback"); }
@@ -716,6 +723,8 @@ int rrx_corpus_create_ex(int device, const void *d_bytes, size_t nbytes, uint32_
     const uint32_t flags = (uint32_t)mail.m.host[1];
     const uint8_t last = nbytes ? (uint8_t)mail.m.host[2] : (uint8_t)'\n';
     c->has_high = (flags & 1u) != 0;
+    c->own_words = c->nstripes && mail.m.host[3] == 0;
+    c->own_span = (uint32_t)mail.m.host[4];
     c->nlines = (size_t)total + ((nbytes && last != '\n') ? 1 : 0);
     // with the line count known: the stripe this corpus wants (stripe_for_lines); if it is another one, index once more
     if (!stripe_bytes && c->nlines) {
@@ -731,6 +740,10 @@ int rrx_corpus_create_ex(int device, const void *d_bytes, size_t nbytes, uint32_
 size_t rrx_corpus_num_lines(const rrx_corpus *c) { return c->nlines; }
 size_t rrx_corpus_num_bytes(const rrx_corpus *c) { return c->nbytes; }
 uint32_t rrx_corpus_stripe_bytes(const rrx_corpus *c) { return c->stripe; }
+int rrx_corpus_one_launch(const rrx_corpus *c, uint32_t *span_words) {
+    if (span_words) *span_words = c->own_words ? c->own_span : 0;
+    return c->own_words ? 1 : 0;
+}
 void rrx_corpus_free(rrx_corpus *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -740,6 +753,7 @@ void rrx_corpus_free(rrx_corpus *c) {
     if (c->d_chunk_base && c->d_chunk_base != c->d_base) (void)hipFree(c->d_chunk_base);
     if (c->d_all_scratch) (void)hipFree(c->d_all_scratch);
     if (c->h_sample) (void)hipHostFree(c->h_sample);
+    for (auto &kv : c->slot_arrays) (void)hipFree(kv.second);      // (hipFree waits for the launches that still use them)
     delete c;
 }
 
@@ -790,14 +804,50 @@ static int match_corpus_sampled(const rrx_regex *re, const rrx_corpus *c, const 
     return rc2;
 }
 
-// The table engine of a LineTables on a corpus (`bits` zeroed): the stride-2 table where there is one - on a corpus with bytes
-// >= 0x80 only if the caller allows the instantiation that steps them as 0x00 (stride2_over_high) -, else the line table.
+// The exchange slots of `c` for a launch on `stream` that needs no cleared bitmap, or nullptr: the launch clears.  That is the
+// case where the corpus' index says so (three workgroups in one word), where a workgroup's range is longer than the window the
+// regex' table leaves, and on a stream that is being captured: a graph may be replayed on any stream, beside launches that use
+// the array of this one, and nothing is allocated during a capture.
+static unsigned long long *own_words_for(const rrx_corpus *c, const dev::Dfa2Device &d2, hipStream_t stream) {
+    if (!c->own_words || c->own_span >= dev::dfa2_window_words(d2)) return nullptr;
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capture) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (capture != hipStreamCaptureStatusNone) return nullptr;
+    std::lock_guard<std::mutex> lock(c->mu);
+    auto it = c->slot_arrays.find(stream);
+    if (it != c->slot_arrays.end()) return it->second;
+    if (c->slot_arrays.size() >= rrx_corpus::kMaxSlotArrays) return nullptr;
+    const size_t bytes = ((c->nstripes + dev::kThreads - 1) / dev::kThreads + 1) * sizeof(unsigned long long);
+    unsigned long long *slots = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&slots), bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (hipMemsetAsync(slots, 0, bytes, stream) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(slots); return nullptr; }
+    c->slot_arrays.emplace(stream, slots);
+    return slots;
+}
+static uint32_t flush_mask_of(const rrx_regex *re, const rrx_corpus *c) {
+    return re->opt_flush_slots.load() ? (uint32_t)re->opt_flush_slots.load() - 1u : dev::flush_mask_for(c->nbytes, c->nlines);
+}
+uint32_t rrx_match_flush_slots(const rrx_regex *re, const rrx_corpus *c, int *compiled_in) {
+    const uint32_t mask = flush_mask_of(re, c);
+    if (compiled_in) *compiled_in = dev::dfa2_flush_at_compile_time(mask) ? 1 : 0;
+    return mask + 1;
+}
+
+// The table engine of a LineTables on a corpus: the stride-2 table where there is one - on a corpus with bytes >= 0x80 only if
+// the caller allows the instantiation that steps them as 0x00 (stride2_over_high) -, else the line table.  The kernels merge
+// words with atomic OR into a bitmap that is cleared here first - but for the stride-2 kernel where it can settle every word
+// itself (own_words_for): that call is ONE launch.
 static int launch_line_tables(const rrx_regex *re, const rrx_corpus *c, const LineTables &lt, const DeviceTables *t, bool stride2_over_high, uint32_t *bits,
                               void *stream) {
-    if (!lt.has_dfa2 || (c->has_high && !stride2_over_high)) return dev::match_stripes_dfa(t->line, c->has_high, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, bits, stream);
-    const dev::Dfa2Device d2 = re->dfa2_device(t);
-    const uint32_t flush_mask = re->opt_flush_slots.load() ? (uint32_t)re->opt_flush_slots.load() - 1u : dev::flush_mask_for(c->nbytes, c->nlines);
-    return (c->has_high ? dev::match_stripes_dfa2_clean : dev::match_stripes_dfa2)(d2, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, bits, stream, flush_mask);
+    const size_t words = rrx_corpus_bitmap_words(c);
+    const bool stride2 = lt.has_dfa2 && (!c->has_high || stride2_over_high);
+    dev::Dfa2Device d2;
+    unsigned long long *slots = nullptr;
+    if (stride2) { d2 = re->dfa2_device(t); slots = own_words_for(c, d2, (hipStream_t)stream); }
+    if (!slots) HIP_TRY(hipMemsetAsync(bits, 0, words * sizeof(uint32_t), (hipStream_t)stream));
+    if (!stride2) return launched(dev::match_stripes_dfa(t->line, c->has_high, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, bits, stream), "match_stripes launch");
+    return launched(dev::match_stripes_dfa2(d2, c->has_high, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, bits, stream, flush_mask_of(re, c), slots, words),
+                    "match_stripes launch");
 }
 
 int rrx_match_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_accept_bits, void *stream) {
@@ -821,7 +871,10 @@ int rrx_match_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_accep
             re->relearn_sampled(c->h_sample, c->sample_lanes, kSampleBytes);     // (this launch and the next ones: the NFA engine, until the new table is in)
         if (re->sampled_ready.load(std::memory_order_acquire) && !re->sampled_retired.load()) return match_corpus_sampled(re, c, t, d_accept_bits, stream);
     }
-    // the kernel merges words with atomic OR: start from an all-zero bitmap
+    // (a corpus with bytes >= 0x80 leaves the stride-2 table for the byte-stride one)
+    if (re->engine != RRX_ENGINE_NFA_SPARSE && re->engine != RRX_ENGINE_NFA_BLOCK && re->engine != RRX_ENGINE_NFA_WAVE && re->engine != RRX_ENGINE_NFA)
+        return launch_line_tables(re, c, re->match, t, /*stride2_over_high=*/false, d_accept_bits, stream);
+    // the NFA kernels merge words with atomic OR: start from an all-zero bitmap
     HIP_TRY(hipMemsetAsync(d_accept_bits, 0, rrx_corpus_bitmap_words(c) * sizeof(uint32_t), (hipStream_t)stream));
     int e = re->engine == RRX_ENGINE_NFA_SPARSE
                 ? dev::match_stripes_sparse_nfa(t->block, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, stream)
@@ -829,12 +882,7 @@ int rrx_match_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_accep
                 ? dev::match_stripes_wave_nfa(t->block, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, stream)
             : re->engine == RRX_ENGINE_NFA_WAVE
                 ? dev::match_stripes_group_nfa(t->group, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, stream)
-            : re->engine == RRX_ENGINE_NFA
-                ? dev::match_stripes_nfa(t->nfa, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, stream)
-            : (re->match.has_dfa2 && !c->has_high && re->opt_units_per_wg.load())
-                ? dev::match_units_dfa2(re->dfa2_device(t), c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, (uint32_t)re->opt_units_per_wg.load(), stream)
-                // (a corpus with bytes >= 0x80 leaves the stride-2 table for the byte-stride one)
-                : launch_line_tables(re, c, re->match, t, /*stride2_over_high=*/false, d_accept_bits, stream);
+                : dev::match_stripes_nfa(t->nfa, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_accept_bits, stream);
     return launched(e, "match_stripes launch");
 }
 
@@ -847,9 +895,7 @@ int rrx_contains_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_bi
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (!c->nlines) return RRX_OK;
-    // the kernels merge words with atomic OR: start from an all-zero bitmap
-    HIP_TRY(hipMemsetAsync(d_bits, 0, rrx_corpus_bitmap_words(c) * sizeof(uint32_t), (hipStream_t)stream));
-    return launched(launch_line_tables(re, c, re->contains_set.lt, t, /*stride2_over_high=*/true, d_bits, stream), "contains launch");
+    return launch_line_tables(re, c, re->contains_set.lt, t, /*stride2_over_high=*/true, d_bits, stream);
 }
 const char *rrx_contains_engine_name(const rrx_regex *re) {
     if (!re) { (void)fail(RRX_ERR_ARG, "null argument"); return nullptr; }

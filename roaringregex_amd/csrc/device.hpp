@@ -158,14 +158,17 @@ constexpr uint32_t kDfa2TableBudget = 30 * 1024;                      // T2 with
 int match_stripes_dfa(const LineDfaDevice &p, bool clamp_high, const uint8_t *bytes, size_t nbytes, uint32_t stripe,
                       const uint64_t *stripe_base, size_t nstripes, uint32_t *accept_bits, void *stream);
 uint32_t flush_mask_for(size_t nbytes, size_t nlines);      // the stride-2 kernel's common flush period from the mean line length
-int match_stripes_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                       size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask = 31u);
-// the same over text that may hold bytes >= 0x80: they are stepped as 0x00 (rrx_contains_corpus, where both are ordinary text of one class)
-int match_stripes_dfa2_clean(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                             size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask = 31u);
-// the same, stripes handed out in units of 64 inside the workgroup (units_per_wg of them per workgroup of 16 waves)
-int match_units_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                     size_t nstripes, uint32_t *accept, uint32_t units_per_wg, void *stream);
+// clean: the text may hold bytes >= 0x80: they are stepped as 0x00 (rrx_contains_corpus, where both are ordinary text of one class).
+// flush_mask 31 runs the kernel with the period compiled in (dfa2_flush_at_compile_time), every other value the one that takes it
+// per launch.  slots != nullptr: the launch needs NO cleared bitmap - every word of the first `nwords` of `accept` is stored, the
+// words two workgroups share through `slots` (one u64 per workgroup and one more, all zero between launches, used by one launch
+// at a time).  Only where no bitmap word lies in three workgroups' ranges and every range fits dfa2_window_words(p):
+// own_words_check yields both figures for a corpus.
+int match_stripes_dfa2(const Dfa2Device &p, bool clean, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                       size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask = 31u, unsigned long long *slots = nullptr,
+                       size_t nwords = 0);
+uint32_t dfa2_window_words(const Dfa2Device &p);             // words of the workgroup's result window in LDS
+bool dfa2_flush_at_compile_time(uint32_t flush_mask);
 // The sampled-table engine: the stride-2 kernel on a table with an ESCAPE state writes two bits per line into
 // `wide_bits` (2 x the accept bitmap, zeroed by the caller); split_two_bit takes them apart (every word of both outputs is
 // written) and counts the escaped lines; recheck_escaped_nfa lets the exact NFA lane engine decide those and ORs its accepts in.
@@ -199,9 +202,15 @@ size_t scan_scratch_words(size_t n);                                            
 int expand_bits(const uint32_t *bits, size_t nlines, uint8_t *out, void *stream);
 // *count (zeroed here, on `stream`) = set bits among the first `nlines` bits of a result bitmap
 int bitmap_count(const uint32_t *bits, size_t nlines, unsigned long long *count, void *stream);
-// mail[0] = *total without the flag bit, mail[1] = flags ? *flags : 0, mail[2] = last_byte ? *last_byte : '\n': the few words a
+// mail[0] = *total without the flag bit, mail[1] = flags ? *flags : 0, mail[2] = last_byte ? *last_byte : '\n', mail[3] and
+// mail[4] = own ? own[0], own[1] : 0 (own_words_check): the few words a
 // synchronous entry hands back, written into pinned device-mapped host memory by a one-lane kernel at the end of the call
-int mail_results(const uint64_t *total, const uint32_t *flags, const uint8_t *last_byte, uint64_t *mail, void *stream);
+int mail_results(const uint64_t *total, const uint32_t *flags, const uint8_t *last_byte, uint64_t *mail, void *stream, const uint32_t *own = nullptr);
+// Once per corpus, for the launches that need no cleared bitmap: over the first bitmap words of the batch kernel's workgroups
+// (workgroup b starts at stripe b * kThreads; the last one's range ends with the bitmap) - own[0] is set to 1 unless they are
+// strictly increasing, own[1] is raised to the largest distance from a workgroup's first word to the last word of its range
+// (`own`: two words zeroed by the caller; nstripes > 0).  mail_results then hands them back as mail[3] and mail[4].
+int own_words_check(const uint64_t *stripe_base, size_t nstripes, const uint8_t *last_byte, uint32_t *own, void *stream);
 // line_off[i] = offset of the first byte of line i (built once per corpus from the stripe index; only patterns that accept
 // the empty string need it); nlines + 1 entries are the caller's to size, entry nlines is written only when the corpus ends in '\n'.
 int build_line_offsets(const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base, size_t nstripes,

@@ -8,15 +8,38 @@ namespace dev {
 namespace {
 
 __global__ void mail_results_kernel(const uint64_t *__restrict__ total, const uint32_t *__restrict__ flags, const uint8_t *__restrict__ last_byte,
-                                    uint64_t *__restrict__ mail) {
+                                    uint64_t *__restrict__ mail, const uint32_t *__restrict__ own) {
     if (threadIdx.x || blockIdx.x) return;
     mail[0] = line_of(*total);
     mail[1] = flags ? *flags : 0u;
     mail[2] = last_byte ? *last_byte : (uint64_t)'\n';
+    mail[3] = own ? own[0] : 0u;
+    mail[4] = own ? own[1] : 0u;
     __threadfence_system();
 }
 
 // ============================================================================================ line index
+// Can the batch kernel's workgroups store their result words without a cleared bitmap?  Lane = workgroup.  The lines of
+// workgroup b lie in the bitmap words [first word of b, first word of b + 1]: where the first words are strictly increasing no
+// word has more than two writers (own[0] stays 0); own[1] = the longest such range, which has to fit the kernel's LDS window.
+// The last workgroup's range ends with the bitmap.
+__global__ __launch_bounds__(256) void own_words_kernel(const uint64_t *__restrict__ stripe_base, size_t nstripes, size_t nworkgroups,
+                                                        const uint8_t *__restrict__ last_byte, uint32_t *__restrict__ own) {
+    const size_t b = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= nworkgroups) return;
+    const uint64_t first = line_of(stripe_base[b * kThreads]) >> 5;
+    uint64_t last;
+    if (b + 1 < nworkgroups) {
+        last = line_of(stripe_base[(b + 1) * kThreads]) >> 5;
+        if (last <= first) { atomicOr(&own[0], 1u); return; }
+    } else {
+        const uint64_t nlines = line_of(stripe_base[nstripes]) + (*last_byte != '\n' ? 1u : 0u);      // (> 0: the corpus is not empty)
+        last = (nlines - 1) >> 5;
+    }
+    const uint64_t span = last - first;
+    atomicMax(&own[1], span < 0xffffffffull ? (uint32_t)span : 0xffffffffu);
+}
+
 // counts[g] = number of '\n' in stripe g, streamed exactly like the match kernel streams it.  Also raises
 // *flags bit 0 if any byte >= 0x80 occurs (the match kernel then clamps such bytes to the dead column).
 __global__ __launch_bounds__(256) void count_newlines_kernel(const uint8_t *__restrict__ bytes, size_t nbytes, uint32_t stripe,
@@ -301,8 +324,14 @@ int bitmap_count(const uint32_t *bits, size_t nlines, unsigned long long *count,
     hipLaunchKernelGGL(bitmap_count_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bits, nlines, count);
     return (int)hipGetLastError();
 }
-int mail_results(const uint64_t *total, const uint32_t *flags, const uint8_t *last_byte, uint64_t *mail, void *stream) {
-    hipLaunchKernelGGL(mail_results_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, total, flags, last_byte, mail);
+int mail_results(const uint64_t *total, const uint32_t *flags, const uint8_t *last_byte, uint64_t *mail, void *stream, const uint32_t *own) {
+    hipLaunchKernelGGL(mail_results_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, total, flags, last_byte, mail, own);
+    return (int)hipGetLastError();
+}
+int own_words_check(const uint64_t *stripe_base, size_t nstripes, const uint8_t *last_byte, uint32_t *own, void *stream) {
+    const size_t nworkgroups = (nstripes + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(own_words_kernel, dim3((unsigned)((nworkgroups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, stripe_base, nstripes, nworkgroups,
+                       last_byte, own);
     return (int)hipGetLastError();
 }
 int build_line_offsets(const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base, size_t nstripes,

@@ -17,48 +17,28 @@ namespace {
 // a kernel around this body whose hook writes a timestamp per workgroup and phase (where a launch's fixed cost goes).
 struct NoPhaseHook { __device__ __forceinline__ void operator()(int) const {} __device__ __forceinline__ void round(int) const {} };
 enum { kPhaseEntry = 0, kPhaseTablesLoaded, kPhaseFirstRound, kPhaseMainDone, kPhaseFollowDone, kPhaseWindowOut, kPhases };
-// A round's text as ONE burst of eight loads.  ASM: issued from one inline-asm block whose destinations are early-clobber, so the
-// address can never share registers with a destination (the unit kernel's register allocation put the address into the last
-// load's destination: a wait state inside the burst, whose loads then stop merging into one request per 128-byte line).  The
-// compiler does not count loads it cannot see, so the block ends with the wait itself: nothing was ever scheduled between a
-// round's request and its first use anyway (the other waves of the SIMD cover the fetch).
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-template <bool ASM>
+// A round's text as ONE burst of eight loads (they merge into one request per 128-byte line).  The address is kept alive past
+// the burst by an empty asm statement: where it dies with the last load, the register allocator may put it into that load's
+// destination - a wait state inside the burst, whose loads then no longer merge (the unit kernel of round 4: -13 %).
 __device__ __forceinline__ void feed_load(uint4 (&buf)[kRound / 16], const uint4 *p) {
-    static_assert(kRound / 16 == 8, "eight slots");
-    if constexpr (!ASM) {
 #pragma unroll
-        for (int i = 0; i < 8; i++) buf[i] = load_text(p + i);
-    } else {
-        u32x4 a, b, c, d, e, f, g, h;
-        asm volatile("global_load_dwordx4 %0, %8, off\n\t"
-                     "global_load_dwordx4 %1, %8, off offset:16\n\t"
-                     "global_load_dwordx4 %2, %8, off offset:32\n\t"
-                     "global_load_dwordx4 %3, %8, off offset:48\n\t"
-                     "global_load_dwordx4 %4, %8, off offset:64\n\t"
-                     "global_load_dwordx4 %5, %8, off offset:80\n\t"
-                     "global_load_dwordx4 %6, %8, off offset:96\n\t"
-                     "global_load_dwordx4 %7, %8, off offset:112\n\t"
-                     "s_waitcnt vmcnt(0)"
-                     : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d), "=&v"(e), "=&v"(f), "=&v"(g), "=&v"(h)
-                     : "v"(p)
-                     : "memory");
-        const u32x4 t[8] = {a, b, c, d, e, f, g, h};
-#pragma unroll
-        for (int i = 0; i < 8; i++) buf[i] = make_uint4(t[i].x, t[i].y, t[i].z, t[i].w);
-    }
+    for (int i = 0; i < kRound / 16; i++) buf[i] = load_text(p + i);
+    asm volatile("" : : "v"(p));
 }
 // One stripe of one lane: lane-local state only (what the caller keeps across stripes is the engine, the window and `g`).
 // KB: result bits per line - 1 (accepted), or 2 (accepted, ESCAPED: the sampled-table engine, whose table does not know every
 // transition; the table's line ends then shift two bits in, and everything that counts results counts bits).
 // CLEAN: the text may hold bytes >= 0x80 (the one-pass entry, which has no index that could tell; rrx_contains_corpus on a corpus
 // that holds some).  They are stepped as 0x00 - the same byte class on every table - under the wave-uniform test below.
-template <bool ONEPASS, class PhaseHook, bool FEED_ASM = false, int KB = 1, bool CLEAN = ONEPASS>
+// FLUSH_SLOTS: the common flush period in 16-byte slots.  A power of two: known at compile time - the test folds per unrolled slot,
+// and from a whole round on (32: `(r & 3) == 3`) it is one test per round; 0: the period is `flush_mask + 1`, decided per launch.
+template <bool ONEPASS, class PhaseHook, int FLUSH_SLOTS, int KB = 1, bool CLEAN = ONEPASS>
 __device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, const uint64_t window_word, uint32_t *const stage, const uint32_t stage_words,
                                             const uint8_t *__restrict__ bytes, const size_t nbytes, const uint32_t stripe,
                                             const uint64_t *__restrict__ stripe_base, uint32_t *__restrict__ accept_bits,
                                             uint32_t *__restrict__ counts, uint32_t *__restrict__ slabs, const uint32_t slab_row, PhaseHook &phase,
-                                            const uint32_t flush_mask = 31u) {
+                                            const uint32_t flush_mask) {
+    static_assert(FLUSH_SLOTS >= 0 && (FLUSH_SLOTS & (FLUSH_SLOTS - 1)) == 0, "0 or a power of two");
     const size_t start = g * (size_t)stripe;
     if (start < nbytes) {                                            // (no early return: the write-out below is collective)
     const size_t stripe_end = start + stripe;
@@ -88,7 +68,7 @@ __device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, con
     constexpr int kSlots = kRound / 16;
     const int rounds = (int)((my_end - start) / kRound);
     uint4 buf[kSlots];
-    if (rounds > 0) feed_load<FEED_ASM>(buf, src);
+    if (rounds > 0) feed_load(buf, src);
     // The line that straddles my stripe end is followed into the next stripe's text (below).  Its first 128 bytes are
     // requested while the last round is still being stepped: loaded on demand, 16 bytes at a time, they were a chain of
     // L2 round trips at the end of every wave's life, and the waves of a workgroup - of the whole chip, launched together
@@ -113,19 +93,23 @@ __device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, con
                 eng.consume_dword(st, buf[i].z, res.bits);
                 eng.consume_dword(st, buf[i].w, res.bits);
             }
-            // All lanes flush TOGETHER every (flush_mask + 1) slots - a period the host picks from the corpus' mean line length so
-            // that about eight results gather in it (short lines: every other slot; 512 bytes for long ones).  The overflow
-            // check behind it is for the lanes that meet far more: left to it alone, lanes overflow at different times and the
-            // wave walks the flush path at nearly every slot (5-byte lines: +1.25 VALU per byte).
-            if ((((uint32_t)r * kSlots + (uint32_t)i) & flush_mask) == flush_mask) res.flush();
+            // All lanes flush TOGETHER every FLUSH_SLOTS (0: flush_mask + 1) slots - a period the host picks from the corpus' mean
+            // line length so that about eight results gather in it (short lines: every other slot; 512 bytes for long ones).  The
+            // overflow check behind it is for the lanes that meet far more: left to it alone, lanes overflow at different times and
+            // the wave walks the flush path at nearly every slot (5-byte lines: +1.25 VALU per byte).
+            bool together;
+            if constexpr (FLUSH_SLOTS == 0) together = (((uint32_t)r * kSlots + (uint32_t)i) & flush_mask) == flush_mask;
+            else if constexpr (FLUSH_SLOTS >= kSlots) together = i == kSlots - 1 && (r & (FLUSH_SLOTS / kSlots - 1)) == FLUSH_SLOTS / kSlots - 1;
+            else together = (i & (FLUSH_SLOTS - 1)) == FLUSH_SLOTS - 1;
+            if (together) res.flush();
             else if (res.bits >> 15) res.flush();            // <= 16 more results fit before the next check
         }
         if (r + 1 < rounds) {
-            feed_load<FEED_ASM>(buf, src + (r + 1) * kSlots);
+            feed_load(buf, src + (r + 1) * kSlots);
         } else {
             last_word = buf[kSlots - 1].w;
             if (start + (size_t)(rounds + 1) * kRound <= nbytes) {
-                feed_load<FEED_ASM>(buf, src + (r + 1) * kSlots);
+                feed_load(buf, src + (r + 1) * kSlots);
                 ahead = true;
             }
         }
@@ -196,11 +180,28 @@ __device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, con
     }
 }
 
-template <bool ONEPASS, class PhaseHook = NoPhaseHook, int KB = 1, bool CLEAN = ONEPASS>
+// A bitmap word that two neighbouring workgroups share, settled without a cleared bitmap: both exchange their bits into the
+// boundary's 64-bit slot (zero between launches).  Whoever finds it empty has left its bits there and is done; the other one
+// finds them, stores the whole word and empties the slot again.  Nobody waits for anybody.
+__device__ __forceinline__ void settle_shared_word(unsigned long long *slot, uint32_t *word, uint32_t mine) {
+    const unsigned long long old = atomicExch(slot, (1ull << 63) | mine);
+    if (old) {
+        *word = (uint32_t)old | mine;
+        *slot = 0;
+    }
+}
+// OWN_WORDS (one result bit per line, indexed): the bitmap need not be cleared before the launch.  The workgroup's lines lie
+// in the words [window_word, next workgroup's first word]; the words strictly between are its own and leave the window as
+// plain stores, zeros included; the two at the ends go through the exchange slots (`slots[b]`: the boundary in front of
+// workgroup b).  The first workgroup owns its first word, the last one every word up to `nwords`, the size of the bitmap.
+// The host launches this form only where the first words of the workgroups are strictly increasing - no word with three
+// writers - and every workgroup's range fits the window (rrx_corpus_one_launch; abi.cpp: own_words_for).
+template <bool ONEPASS, int FLUSH_SLOTS, class PhaseHook = NoPhaseHook, int KB = 1, bool CLEAN = ONEPASS, bool OWN_WORDS = false>
 __device__ __forceinline__ void dfa2_body(const Dfa2Device &prog, const uint8_t *__restrict__ bytes, size_t nbytes, uint32_t stripe,
                                           const uint64_t *__restrict__ stripe_base, uint32_t *__restrict__ accept_bits,
                                           uint32_t *__restrict__ counts, uint32_t *__restrict__ slabs, PhaseHook phase = PhaseHook(),
-                                          uint32_t flush_mask = 31u) {
+                                          uint32_t flush_mask = 31u, unsigned long long *__restrict__ slots = nullptr, uint64_t nwords = 0) {
+    static_assert(!OWN_WORDS || (!ONEPASS && KB == 1), "the exchange slots serve the indexed kernels with one bit per line");
     phase(kPhaseEntry);
     // T2 first: its entries hold 16-bit LDS addresses; the result window takes what T2 leaves of its region (16 KiB and
     // more for tables up to 30 KiB, 4 KiB at least).  The arrays are static, so P's base is a link-time constant.
@@ -221,9 +222,21 @@ __device__ __forceinline__ void dfa2_body(const Dfa2Device &prog, const uint8_t 
     const size_t g0 = (size_t)blockIdx.x * kThreads;
     uint64_t window_word = 0;
     if (!ONEPASS) window_word = (line_of(stripe_base[g0]) * KB) >> 5;       // the workgroup's first stripe exists: uniform load
-    dfa2_stripe<ONEPASS, PhaseHook, false, KB, CLEAN>(eng, g0 + threadIdx.x, window_word, stage, stage_words, bytes, nbytes, stripe, stripe_base, accept_bits, counts, slabs,
-                         gridDim.x * kThreads, phase, flush_mask);
-    if (!ONEPASS) {
+    dfa2_stripe<ONEPASS, PhaseHook, FLUSH_SLOTS, KB, CLEAN>(eng, g0 + threadIdx.x, window_word, stage, stage_words, bytes, nbytes, stripe, stripe_base, accept_bits,
+                                                            counts, slabs, gridDim.x * kThreads, phase, flush_mask);
+    if constexpr (OWN_WORDS) {
+        __syncthreads();
+        const bool last = blockIdx.x + 1 == gridDim.x;
+        const uint64_t next_word = last ? nwords : line_of(stripe_base[g0 + kThreads]) >> 5;      // (stripe_base has an entry behind the last stripe)
+        uint64_t span = next_word - window_word;                     // >= 1; the host has seen to it that the range fits the window
+        if (span > stage_words) span = stage_words;                  // (never: and then no store would leave the bitmap either)
+        for (uint32_t i = threadIdx.x + 1; i < (uint32_t)span; i += kThreads) accept_bits[window_word + i] = stage[i];
+        if (threadIdx.x == 0) {
+            if (blockIdx.x == 0) accept_bits[window_word] = stage[0];
+            else settle_shared_word(&slots[blockIdx.x], &accept_bits[window_word], stage[0]);
+        }
+        if (threadIdx.x == 64 && !last && span < stage_words) settle_shared_word(&slots[blockIdx.x + 1], &accept_bits[next_word], stage[(uint32_t)span]);
+    } else if (!ONEPASS) {
         // ---- write the window out: consecutive lanes, consecutive words (the atomics merge into whole lines in L2;
         // the first and the last word of the window are shared with the neighbouring workgroups)
         __syncthreads();
@@ -234,87 +247,34 @@ __device__ __forceinline__ void dfa2_body(const Dfa2Device &prog, const uint8_t 
     }
     phase(kPhaseWindowOut);
 }
-// The same stripes handed out in UNITS inside the workgroup.  A launch of one generation - 1 GiB: 512 workgroups,
-// two per CU - ends in a drain: a SIMD issues from its oldest wave first, its eight waves finish their stripes at 122 ... 228 us and
-// for the last third of the kernel a CU runs on a few waves (profiles/r03_phase_stamps.txt).  Here the workgroup owns
-// `units_per_wg` units of 64 consecutive stripes - several per wave - and a wave that has finished one takes the next from a
-// counter in LDS: the waves the scheduler favours do more units, all sixteen end within one unit of each other.  The unit loop
-// is the outermost scope: nothing lives across iterations but the unit number (scalar); the result window covers the line
-// range of the whole workgroup as before.
-// MEASURED (round 4, profiles/r04_unit_handout_ab.txt, same process A/B): with one unit per wave it runs exactly as the kernel
-// above (0.699 / 0.698 of peak on the 8 GiB headline, 0.605 / 0.596 on a{1,300}); with stripes cut small enough to hand out
-// several units per wave it is SLOWER on every config (email 1 GiB 0.606 -> 0.57-0.58, URL 1 GiB 0.598 -> 0.56-0.58, 8 GiB
-// 0.698 -> 0.66-0.69): what a one-generation launch loses at its end is not an imbalance between waves that a finer hand-out
-// could level.  Kept as an option (RRX_OPT_UNITS_PER_WORKGROUP), off by default.
-template <class PhaseHook = NoPhaseHook>
-__device__ __forceinline__ void dfa2_units_body(const Dfa2Device &prog, const uint8_t *__restrict__ bytes, size_t nbytes, uint32_t stripe,
-                                                const uint64_t *__restrict__ stripe_base, uint32_t *__restrict__ accept_bits, uint32_t units_per_wg,
-                                                PhaseHook phase = PhaseHook()) {
-    phase(kPhaseEntry);
-    __shared__ __attribute__((aligned(16))) struct {
-        uint8_t t2_and_stage[kDfa2RegionBytes];
-        uint16_t p[kDfa2PBytes / 2];
-    } lds;
-    Dfa2 eng;
-    eng.load(prog, lds.p, lds.t2_and_stage);
-    const uint32_t stage_off = (uint32_t)((Dfa2::lds_bytes(prog) + 15) & ~(size_t)15);
-    uint32_t *const stage = reinterpret_cast<uint32_t *>(lds.t2_and_stage + stage_off);
-    const uint32_t stage_words = (kDfa2RegionBytes - stage_off) / 4 - 1;                  // the last word of the region is the unit counter
-    uint32_t &next_unit = stage[stage_words];
-    for (uint32_t i = threadIdx.x; i < stage_words; i += kThreads) stage[i] = 0;
-    if (threadIdx.x == 0) next_unit = kThreads / 64;                 // the first unit of every wave is its own number
-    __syncthreads();
-    phase(kPhaseTablesLoaded);
-    const size_t g_wg = (size_t)blockIdx.x * units_per_wg * 64;      // the workgroup's first stripe (exists: the grid is sized that way)
-    const uint64_t window_word = line_of(stripe_base[g_wg]) >> 5;
-    uint32_t unit = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    while (unit < units_per_wg) {
-        // (the lane number is made anew in every turn, by an instruction the compiler will not hoist: one more register live
-        // across the stripe body and the allocator puts a round's load address into the registers its last load writes - a
-        // wait state inside the burst of eight loads, which then no longer merge into one request per line: -13 %)
-        uint32_t lane;
-        asm volatile("v_and_b32 %0, 63, %1" : "=v"(lane) : "v"(threadIdx.x));
-        dfa2_stripe<false, PhaseHook, true>(eng, g_wg + (size_t)unit * 64 + lane, window_word, stage, stage_words, bytes, nbytes, stripe, stripe_base, accept_bits,
-                           nullptr, nullptr, 0u, phase);
-        uint32_t ticket = 0;
-        if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0) ticket = atomicAdd(&next_unit, 1u);
-        unit = __builtin_amdgcn_readfirstlane(ticket);
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < stage_words; i += kThreads) {
-        const uint32_t v = stage[i];
-        if (v) atomicOr(&accept_bits[window_word + i], v);
-    }
-    phase(kPhaseWindowOut);
-}
-// (waves_per_eu: left to itself the allocator takes 65 registers here - one workgroup per CU instead of two)
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void match_units2_kernel(
-    Dfa2Device prog, const uint8_t *__restrict__ bytes, size_t nbytes, uint32_t stripe, const uint64_t *__restrict__ stripe_base,
-    uint32_t *__restrict__ accept_bits, uint32_t units_per_wg) {
-    dfa2_units_body(prog, bytes, nbytes, stripe, stripe_base, accept_bits, units_per_wg);
-}
+// (the unit hand-out inside the workgroup, round 4's option, never won and is gone: profiles/r04_unit_handout_ab.txt)
+template <int FLUSH_SLOTS, bool OWN_WORDS>
 __global__ __launch_bounds__(kThreads) void match_stripes2_kernel(Dfa2Device prog, const uint8_t *__restrict__ bytes, size_t nbytes,
                                                                    uint32_t stripe, const uint64_t *__restrict__ stripe_base,
-                                                                   uint32_t *__restrict__ accept_bits, uint32_t flush_mask) {
-    dfa2_body<false>(prog, bytes, nbytes, stripe, stripe_base, accept_bits, nullptr, nullptr, NoPhaseHook(), flush_mask);
+                                                                   uint32_t *__restrict__ accept_bits, uint32_t flush_mask,
+                                                                   unsigned long long *__restrict__ slots, uint64_t nwords) {
+    dfa2_body<false, FLUSH_SLOTS, NoPhaseHook, 1, false, OWN_WORDS>(prog, bytes, nbytes, stripe, stripe_base, accept_bits, nullptr, nullptr, NoPhaseHook(), flush_mask,
+                                                                    slots, nwords);
 }
 // the same over text that may hold bytes >= 0x80, stepped as 0x00 (rrx_contains_corpus: such bytes are ordinary text there, of the
 // class of NUL, and UTF-8 text stays on the two-bytes-per-lookup kernel)
+template <int FLUSH_SLOTS, bool OWN_WORDS>
 __global__ __launch_bounds__(kThreads) void match_stripes2_clean_kernel(
     Dfa2Device prog, const uint8_t *__restrict__ bytes, size_t nbytes, uint32_t stripe, const uint64_t *__restrict__ stripe_base,
-    uint32_t *__restrict__ accept_bits, uint32_t flush_mask) {
-    dfa2_body<false, NoPhaseHook, 1, true>(prog, bytes, nbytes, stripe, stripe_base, accept_bits, nullptr, nullptr, NoPhaseHook(), flush_mask);
+    uint32_t *__restrict__ accept_bits, uint32_t flush_mask, unsigned long long *__restrict__ slots, uint64_t nwords) {
+    dfa2_body<false, FLUSH_SLOTS, NoPhaseHook, 1, true, OWN_WORDS>(prog, bytes, nbytes, stripe, stripe_base, accept_bits, nullptr, nullptr, NoPhaseHook(), flush_mask,
+                                                                   slots, nwords);
 }
 // two result bits per line (accepted, escaped) into a bitmap of twice the size: the sampled-table engine's first pass
 __global__ __launch_bounds__(kThreads) void match_stripes2_two_bit_kernel(Dfa2Device prog, const uint8_t *__restrict__ bytes, size_t nbytes,
                                                                            uint32_t stripe, const uint64_t *__restrict__ stripe_base,
                                                                            uint32_t *__restrict__ wide_bits) {
-    dfa2_body<false, NoPhaseHook, 2>(prog, bytes, nbytes, stripe, stripe_base, wide_bits, nullptr, nullptr);
+    dfa2_body<false, 32, NoPhaseHook, 2>(prog, bytes, nbytes, stripe, stripe_base, wide_bits, nullptr, nullptr);
 }
 __global__ __launch_bounds__(kThreads) void match_stripes2_onepass_kernel(Dfa2Device prog, const uint8_t *__restrict__ bytes, size_t nbytes,
                                                                            uint32_t stripe, uint32_t *__restrict__ counts,
                                                                            uint32_t *__restrict__ slabs) {
-    dfa2_body<true>(prog, bytes, nbytes, stripe, nullptr, nullptr, counts, slabs);
+    dfa2_body<true, 32>(prog, bytes, nbytes, stripe, nullptr, nullptr, counts, slabs);
 }
 
 // One-pass mode, last step: lane = stripe.  The stream of stripe g (counts[g] results, the first of them dropped if the
@@ -397,13 +357,24 @@ static int launch_dfa2(void (*kernel)(Params...), const Dfa2Device &p, const uin
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, p, bytes, nbytes, stripe, rest...);
     return (int)hipGetLastError();
 }
-int match_stripes_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                       size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask) {
-    return launch_dfa2(match_stripes2_kernel, p, bytes, nbytes, stripe, nstripes, kThreads, stream, stripe_base, accept, flush_mask);
+uint32_t dfa2_window_words(const Dfa2Device &p) {
+    const size_t stage_off = (Dfa2::lds_bytes(p) + 15) & ~(size_t)15;
+    return stage_off < kDfa2RegionBytes ? (uint32_t)((kDfa2RegionBytes - stage_off) / 4) : 0u;
 }
-int match_stripes_dfa2_clean(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                             size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask) {
-    return launch_dfa2(match_stripes2_clean_kernel, p, bytes, nbytes, stripe, nstripes, kThreads, stream, stripe_base, accept, flush_mask);
+bool dfa2_flush_at_compile_time(uint32_t flush_mask) { return flush_mask == 31u; }
+// The period the automatic choice gives text of 33 bytes per line and more - URL, kwlog, a{1,300}, both long-line workloads - is
+// compiled in; every other one is a launch parameter.  `slots` != nullptr: the form that needs no cleared bitmap.
+int match_stripes_dfa2(const Dfa2Device &p, bool clean, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                       size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask, unsigned long long *slots, size_t nwords) {
+    const bool fixed = dfa2_flush_at_compile_time(flush_mask);
+#define GO(K) launch_dfa2(K, p, bytes, nbytes, stripe, nstripes, kThreads, stream, stripe_base, accept, flush_mask, slots, (uint64_t)nwords)
+    if (clean) {
+        if (slots) return fixed ? GO((match_stripes2_clean_kernel<32, true>)) : GO((match_stripes2_clean_kernel<0, true>));
+        return fixed ? GO((match_stripes2_clean_kernel<32, false>)) : GO((match_stripes2_clean_kernel<0, false>));
+    }
+    if (slots) return fixed ? GO((match_stripes2_kernel<32, true>)) : GO((match_stripes2_kernel<0, true>));
+    return fixed ? GO((match_stripes2_kernel<32, false>)) : GO((match_stripes2_kernel<0, false>));
+#undef GO
 }
 // ---- the sampled-table engine's second step: the two-bit bitmap (bit 2i = line i accepted, bit 2i + 1 = line i ended in the
 // ESCAPE state) taken apart into the accept bitmap - every word written, nothing to clear beforehand - and the bitmap of the
@@ -480,12 +451,6 @@ int split_two_bit(const uint32_t *wide, size_t nlines, uint32_t *accept_bits, ui
     hipLaunchKernelGGL(split_two_bit_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, wide, words, accept_bits, escaped_bits, escaped_total,
                        list, cap);
     return (int)hipGetLastError();
-}
-int match_units_dfa2(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                     size_t nstripes, uint32_t *accept, uint32_t units_per_wg, void *stream) {
-    if (nstripes && !units_per_wg) return (int)hipErrorInvalidValue;
-    // (units of 64 stripes, units_per_wg of them per workgroup)
-    return launch_dfa2(match_units2_kernel, p, bytes, nbytes, stripe, nstripes, (size_t)64 * units_per_wg, stream, stripe_base, accept, units_per_wg);
 }
 // byte-stride table engines in one-pass mode (bytes >= 0x80 are always clamped: nobody has looked at the corpus yet)
 int match_onepass_dfa(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, size_t nstripes, uint32_t *counts,
