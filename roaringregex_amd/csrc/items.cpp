@@ -1,0 +1,278 @@
+// items.cpp — explicit items (an offsets array: rrx_match_extents / rrx_contains_extents, and rrx_items, the batch indexed once)
+// and single strings (rrx_match_string, rrx_match_cstr).
+#include <algorithm>
+#include <cstring>
+
+#include "handles.hpp"
+
+using namespace rrx;
+
+static constexpr size_t kLongStringBytes = 32 * 1024;   // shorter single strings stay on one lane (NFA engines)
+// Table engines: the chunk maps by convergence cost a handful of short launches (60-80 us), a sequential lane 94 ns per byte
+// (tools/probe/facade_latency.py: 1.9 ms for 20 KB against 59 us; 130 us for 1 KB): from 1 KiB on the chunks win.
+static constexpr size_t kLongStringBytesTable = 1024;
+static constexpr uint32_t kLongNfaMaxBits = 256;        // NFA engines: chunk relations cost bytes x positions lane steps
+
+extern "C" {
+
+// below these a batch stays on the lane-per-item kernel (the index costs more than it saves)
+static constexpr size_t kItemsStripesMin = (size_t)1 << 16;
+static constexpr size_t kItemsStripesMinBytes = (size_t)8 << 20;
+// A lane (lane group, workgroup) per item: the match set on the regex' engine, one byte per item; the contains set on the plain
+// arrays of its table, the bitmap itself.
+static int extents_lanes(const rrx_regex *re, const TableSet &set, const DeviceTables *t, const uint8_t *b, const uint64_t *d_off, size_t nitems,
+                         uint32_t trim, dev::ItemVerdicts out, void *stream, const uint32_t *only_if = nullptr) {
+    int e = 0;
+    if (&set == &re->contains_set) e = dev::contains_extents_dfa(t->dfa, set.lt.global, set.found, b, d_off, nitems, trim, out.bits, stream, only_if);
+    else switch (re->engine) {
+    case RRX_ENGINE_NFA_SPARSE: e = dev::match_extents_sparse_nfa(t->block, b, d_off, nitems, trim, out.bytes, stream); break;
+    case RRX_ENGINE_NFA_BLOCK: e = dev::match_extents_wave_nfa(t->block, b, d_off, nitems, trim, out.bytes, stream); break;
+    case RRX_ENGINE_NFA_WAVE: e = dev::match_extents_group_nfa(t->group, b, d_off, nitems, trim, out.bytes, stream); break;
+    case RRX_ENGINE_NFA: e = dev::match_extents_nfa(t->nfa, b, d_off, nitems, trim, out.bytes, stream); break;
+    default: e = dev::match_extents_dfa(t->dfa, b, d_off, nitems, trim, out.bytes, stream, only_if);
+    }
+    return e ? hip_fail((hipError_t)e, (std::string(set.word) + "_extents launch").c_str()) : RRX_OK;
+}
+// The table of the stripe-wise items kernels on `device`: the stride-2 items table for trim 1 (unless RRX_OPT_ITEMS_STRIDE2 is 0),
+// else - or where that one does not fit - the byte-stride items table; both nullptr: the set has none (the lane-per-item kernel).
+struct ItemsTable { const dev::LineDfaDevice *items1 = nullptr; const dev::Dfa2Device *items2 = nullptr; };
+static ItemsTable pick_items_table(const rrx_regex *re, TableSet &set, int device, uint32_t trim) {
+    ItemsTable t;
+    if (trim == 1 && re->items_stride2.load()) t.items2 = re->items2_table(set, device);
+    if (!t.items2) t.items1 = re->items_table(set, device);
+    return t;
+}
+// The most a one-call batch of items at `d_bytes` can span (the index, the stripe and the grids are sized for it; the kernels take
+// the real extent from the offsets): what is left of the allocation that holds d_bytes.
+// The tail of the allocation is only a BOUND: a batch carved out of a memory pool (a caching allocator's block, a slice of a
+// column store) would size the index, the stripe and the grids for all of the pool behind it - a 24 MiB batch 6 GiB into a
+// 10 GiB pool: 512 MiB of scratch and two workgroups' worth of stripes.  So the bound is trusted only while it is plausible
+// for the batch: at most 128 bytes per item (string columns; 16 MiB at least).  Beyond that - and for memory whose range
+// the runtime does not report (pools, managed and virtual memory: bound 0) - the batch's real extent is read back, one
+// synchronisation on `stream`, as round 2 did for every batch.
+static int items_extent_bound(const void *d_bytes, const uint64_t *d_off, size_t nitems, void *stream, size_t *out) {
+    size_t bound = 0;
+    hipDeviceptr_t abase = nullptr;
+    size_t asize = 0;
+    if (hipMemGetAddressRange(&abase, &asize, const_cast<void *>(d_bytes)) == hipSuccess && abase)
+        bound = (size_t)(static_cast<const uint8_t *>(abase) + asize - static_cast<const uint8_t *>(d_bytes));
+    else (void)hipGetLastError();
+    const size_t plausible = std::max<size_t>(nitems * 128, (size_t)16 << 20);
+    if (!bound || bound > plausible) {
+        uint64_t first = 0, last = 0;
+        HIP_TRY(hipMemcpyAsync(&first, d_off, sizeof first, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_TRY(hipMemcpyAsync(&last, d_off + nitems, sizeof last, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        const size_t extent = last > first ? (size_t)last : 0;
+        bound = bound ? std::min(bound, extent) : extent;
+    }
+    *out = bound;
+    return RRX_OK;
+}
+// A one-call batch of items on `set` (`t`: its tables on `device`), the verdicts into `out`.
+// A large batch on a table with an items form runs stripe-wise over the byte buffer, the item ends taken from a bitmap built from
+// the offsets (kernels_items.hip: match_items_stripes_kernel) and the table a copy of the plain one with an END OF ITEM column.
+// Needs: the entry's own conditions (stripes_ok), trim 0 or 1, at most 126 table states, no item without a byte to carry its mark.
+// ASYNCHRONOUS: nothing is read back.  The host knows neither off[0] nor off[nitems]; it sizes the index for the most the batch can
+// span - what is left of the allocation that holds d_bytes - and the kernels take the real extent from the offsets.  Whether the
+// batch is fit (alignment, no degenerate item, large enough) is decided on the device: both kernels are queued, each predicated on
+// the index pass's fit flag - the stripe-wise kernel does nothing on an unfit batch (a bitmap copied out of its scratch: zeros) and
+// the lane-per-item kernel behind it, which writes every byte or word, nothing on a fit one.
+// (r4) trim 1 on a table with a stride-2 form: the stride-2 items table (it also serves automata whose byte-stride items table is
+// beyond the LDS - a{1,300}: 302 rows of 130 columns)
+static int extents_batch(const rrx_regex *re, TableSet &set, const DeviceTables *t, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems,
+                         uint32_t trim, bool stripes_ok, dev::ItemVerdicts out, void *stream) {
+    const uint8_t *b = static_cast<const uint8_t *>(d_bytes);
+    ItemsTable it;
+    if (stripes_ok && trim <= 1 && nitems >= kItemsStripesMin) it = pick_items_table(re, set, device, trim);
+    const bool items = it.items1 || it.items2;
+    size_t bound = 0;
+    if (items) {
+        const int rc = items_extent_bound(d_bytes, d_off, nitems, stream, &bound);
+        if (rc) return rc;
+    }
+    if (!items || bound < kItemsStripesMinBytes) return extents_lanes(re, set, t, b, d_off, nitems, trim, out, stream);
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(re->onepass_mu);
+    void *buf = nullptr;
+    const size_t ib = dev::items_index_bytes(bound, nitems);
+    int rc = re->onepass_for(device, ib + dev::items_result_bytes(nitems), &buf, st);      // (ordered behind the scratch's last user)
+    if (rc) return rc;
+    uint32_t *d_flag = nullptr;
+    int le = dev::items_index_build(bound, d_off, nitems, trim, buf, &d_flag, stream, b, kItemsStripesMinBytes);
+    if (!le) le = it.items2 ? dev::items_match2(*it.items2, b, bound, nitems, buf, static_cast<uint8_t *>(buf) + ib, out, stream, d_off, d_flag)
+                            : dev::items_match(*it.items1, b, bound, nitems, trim, buf, static_cast<uint8_t *>(buf) + ib, out, stream, d_off, d_flag);
+    if (!le) rc = extents_lanes(re, set, t, b, d_off, nitems, trim, out, stream, d_flag);
+    const int rc2 = re->onepass_done(device, st);                // (whatever was queued: the next user waits for it)
+    if (le) return hip_fail((hipError_t)le, (std::string(set.word) + "_items_stripes launch").c_str());
+    return rc ? rc : rc2;
+}
+// The match entries go stripe-wise only on the table engine and into a 16-byte aligned byte array (expand_bits)
+static bool match_stripes_ok(const rrx_regex *re, const uint8_t *d_accept) { return re->engine == RRX_ENGINE_DFA && !(reinterpret_cast<uintptr_t>(d_accept) & 15); }
+int rrx_match_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                      uint8_t *d_accept, void *stream) {
+    if (!re || (nitems && (!d_off || !d_accept))) return fail(RRX_ERR_ARG, "null argument");
+    const DeviceTables *t;
+    int rc = re->tables(device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    return extents_batch(re, re->match_set, t, device, d_bytes, d_off, nitems, trim, match_stripes_ok(re, d_accept), d_accept, stream);      // (no items: an empty launch)
+}
+
+int rrx_items_create(int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, void *stream, rrx_items **out) {
+    if (!out || (nitems && (!d_bytes || !d_off))) return fail(RRX_ERR_ARG, "null argument");
+    *out = nullptr;
+    HIP_TRY(hipSetDevice(device));
+    std::unique_ptr<rrx_items> it(new rrx_items());      // (its device memory goes with it on every early return)
+    it->device = device; it->d_bytes = static_cast<const uint8_t *>(d_bytes); it->d_off = d_off; it->nitems = nitems; it->trim = trim;
+    hipStream_t st = (hipStream_t)stream;
+    if (nitems && trim <= 1) {
+        uint64_t first = 0, last = 0;
+        hipError_t e = hipMemcpyAsync(&first, d_off, sizeof first, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&last, d_off + nitems, sizeof last, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return hip_fail(e, "items offsets readback");
+        it->first = first;
+        if (last > first && !(reinterpret_cast<uintptr_t>(it->d_bytes + first) & 15)) {
+            it->nbytes = (size_t)(last - first);
+            e = it->d_index.alloc(device, dev::items_index_bytes(it->nbytes, nitems));
+            if (e == hipSuccess) e = it->d_result.alloc(device, dev::items_result_bytes(nitems));
+            if (e != hipSuccess) return hip_fail(e, "hipMalloc(items index)");
+            uint32_t *d_flag = nullptr;
+            int le = dev::items_index_build(it->nbytes, d_off, nitems, trim, it->d_index.p, &d_flag, stream);
+            uint32_t degenerate = 1;
+            if (!le) { e = hipMemcpyAsync(&degenerate, d_flag, sizeof degenerate, hipMemcpyDeviceToHost, st); if (e == hipSuccess) e = hipStreamSynchronize(st); }
+            if (le || e != hipSuccess) return le ? hip_fail((hipError_t)le, "items index launch") : hip_fail(e, "items index");
+            it->stripes = degenerate == 0;
+        }
+    }
+    *out = it.release();
+    return RRX_OK;
+}
+size_t rrx_items_count(const rrx_items *it) { return it ? it->nitems : 0; }
+int rrx_items_stripe_wise(const rrx_items *it) { return it && it->stripes ? 1 : 0; }
+void rrx_items_free(rrx_items *it) { delete it; }
+
+// An indexed batch on `set` (`t`: its tables on the batch's device): stripe-wise where the index admits it (it said so once: no
+// second attempt), the entry's own conditions hold (stripes_ok) and the set has an items table; else a lane per item.
+static int items_batch(const rrx_regex *re, TableSet &set, const DeviceTables *t, const rrx_items *it, bool stripes_ok, dev::ItemVerdicts out, void *stream) {
+    const ItemsTable tab = it->stripes && stripes_ok ? pick_items_table(re, set, it->device, it->trim) : ItemsTable();
+    if (!tab.items1 && !tab.items2) return extents_lanes(re, set, t, it->d_bytes, it->d_off, it->nitems, it->trim, out, stream);
+    std::lock_guard<std::mutex> lock(it->mu);
+    const int le = tab.items2 ? dev::items_match2(*tab.items2, it->d_bytes + it->first, it->nbytes, it->nitems, it->d_index.p, it->d_result.p, out, stream)
+                              : dev::items_match(*tab.items1, it->d_bytes + it->first, it->nbytes, it->nitems, it->trim, it->d_index.p, it->d_result.p, out, stream);
+    return le ? hip_fail((hipError_t)le, (std::string(set.word) + "_items launch").c_str()) : RRX_OK;
+}
+int rrx_match_items(const rrx_regex *re, const rrx_items *it, uint8_t *d_accept, void *stream) {
+    if (!re || !it || (it->nitems && !d_accept)) return fail(RRX_ERR_ARG, "null argument");
+    if (!it->nitems) return RRX_OK;
+    const DeviceTables *t;
+    int rc = re->tables(it->device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(it->device));
+    return items_batch(re, re->match_set, t, it, match_stripes_ok(re, d_accept), d_accept, stream);
+}
+
+// "Which items contain a match": the same two paths on the contains set - stripe-wise wherever the contains table has an items form,
+// whatever the regex' MATCH engine is and at any alignment of the bitmap (the stripe-wise kernels write into scratch, the caller's
+// bitmap receives a masked copy).  An empty batch still reports a regex without a contains table.
+int rrx_contains_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                         uint32_t *d_bits, void *stream) {
+    if (!re || (nitems && (!d_off || !d_bits))) return fail(RRX_ERR_ARG, "null argument");
+    const DeviceTables *t;
+    int rc = re->contains_tables(device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if (!nitems) return RRX_OK;
+    return extents_batch(re, re->contains_set, t, device, d_bytes, d_off, nitems, trim, /*stripes_ok=*/true, d_bits, stream);
+}
+int rrx_contains_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_bits, void *stream) {
+    if (!re || !it || (it->nitems && !d_bits)) return fail(RRX_ERR_ARG, "null argument");
+    const DeviceTables *t;
+    int rc = re->contains_tables(it->device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(it->device));
+    if (!it->nitems) return RRX_OK;
+    return items_batch(re, re->contains_set, t, it, /*stripes_ok=*/true, d_bits, stream);
+}
+
+// One device-resident string of any length.  Long strings take the chunk-map path when the automaton has a small
+// table (every chunk stepped from every state, maps composed); the rest is one item of the extents kernel.
+// long_string_plan decides which, once per call: the scratch is sized and the string matched by the same plan.
+// `scratch`: caller-provided device memory of plan.scratch_bytes (rrx_match_cstr passes the tail of its own buffer).
+struct LongStringPlan {
+    enum Kind { kOneItem, kLongDfa, kLongNfa } kind = kOneItem;       // one item of the extents kernel, or the chunk maps of a table / NFA engine
+    uint32_t chunk = 0, nchunks = 0;
+    size_t scratch_bytes = 2 * sizeof(uint64_t);                      // (one item: its two offsets)
+};
+static LongStringPlan long_string_plan(const rrx_regex *re, const DeviceTables *t, size_t nbytes) {
+    LongStringPlan p;
+    if (re->engine == RRX_ENGINE_DFA && nbytes >= kLongStringBytesTable && t->dfa.nstates && t->dfa.nstates <= dev::kLongMaxStates) {
+        p.kind = LongStringPlan::kLongDfa;
+        p.scratch_bytes = dev::long_scratch_bytes(t->dfa.nstates, nbytes, &p.chunk);
+    } else if (re->engine == RRX_ENGINE_NFA && nbytes >= kLongStringBytes && t->nfa.nbits <= kLongNfaMaxBits) {
+        p.kind = LongStringPlan::kLongNfa;
+        p.scratch_bytes = dev::long_nfa_scratch_bytes(t->nfa, nbytes, &p.chunk, &p.nchunks);
+    }
+    return p;
+}
+static int match_string_with(const rrx_regex *re, int device, const DeviceTables *t, const LongStringPlan &plan, const uint8_t *d_bytes, size_t nbytes,
+                             uint8_t *d_accept, uint8_t *scratch, hipStream_t st) {
+    if (plan.kind == LongStringPlan::kLongDfa) {
+        return launched(dev::match_long_dfa(t->dfa, d_bytes, nbytes, plan.chunk, scratch, d_accept, st), "match_long launch");
+    }
+    if (plan.kind == LongStringPlan::kLongNfa) {
+        return launched(dev::match_long_nfa(t->nfa, d_bytes, nbytes, plan.chunk, plan.nchunks, scratch, d_accept, st), "match_long_nfa launch");
+    }
+    const uint64_t off[2] = {0, nbytes};
+    uint64_t *d_off = reinterpret_cast<uint64_t *>(scratch);
+    hipError_t e = hipMemcpyAsync(d_off, off, sizeof off, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);                    // `off` leaves scope
+    if (e != hipSuccess) return hip_fail(e, "extent upload");
+    return rrx_match_extents(re, device, d_bytes, d_off, 1, 0, d_accept, st);
+}
+
+int rrx_match_string(const rrx_regex *re, int device, const void *d_bytes, size_t nbytes, uint8_t *d_accept, void *stream) {
+    if (!re || (nbytes && !d_bytes) || !d_accept) return fail(RRX_ERR_ARG, "null argument");
+    const DeviceTables *t;
+    int rc = re->tables(device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    std::lock_guard<std::mutex> lock(re->scratch_mu);
+    void *scratch = nullptr;
+    const LongStringPlan plan = long_string_plan(re, t, nbytes);
+    rc = re->scratch_for(device, plan.scratch_bytes, &scratch);
+    if (rc) return rc;
+    rc = match_string_with(re, device, t, plan, static_cast<const uint8_t *>(d_bytes), nbytes, d_accept, static_cast<uint8_t *>(scratch),
+                           static_cast<hipStream_t>(stream));
+    const hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(stream));      // the scratch is reused by the next call
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "match_string");
+    return rc;
+}
+
+int rrx_match_cstr(const rrx_regex *re, int device, const char *text, int *accepted, size_t *len) {
+    if (!re || !text || !accepted) return fail(RRX_ERR_ARG, "null argument");
+    const size_t n = std::strlen(text);                       // regex.h:157: consume up to the terminator
+    if (len) *len = n;
+    const DeviceTables *t;
+    int rc = re->tables(device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    // one persistent device buffer: [text, padded to 16 | accept byte, padded to 16 | scratch of the match]
+    std::lock_guard<std::mutex> lock(re->scratch_mu);
+    const size_t acc_at = (n + 15) & ~(size_t)15, scratch_at = acc_at + 16;
+    void *buf = nullptr;
+    const LongStringPlan plan = long_string_plan(re, t, n);
+    rc = re->scratch_for(device, scratch_at + plan.scratch_bytes, &buf);
+    if (rc) return rc;
+    uint8_t *d = static_cast<uint8_t *>(buf);
+    hipError_t e = n ? hipMemcpy(d, text, n, hipMemcpyHostToDevice) : hipSuccess;
+    if (e != hipSuccess) return hip_fail(e, "text upload");
+    rc = match_string_with(re, device, t, plan, d, n, d + acc_at, d + scratch_at, nullptr);
+    uint8_t a = 0;
+    if (!rc) { e = hipMemcpy(&a, d + acc_at, 1, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hip_fail(e, "accept readback"); }
+    *accepted = a;
+    return rc;
+}
+
+}  // extern "C"

@@ -1418,6 +1418,7 @@ Dfa2OrderStats order_dfa2(const Dfa2Program &d, const uint8_t *sample, uint32_t 
 }
 
 // ------------------------------------------------------------------------------------------ work beside the caller
+// fn() runs without try / catch - an exception ends the process or leaves kRunning for good; the fix goes here.
 bool OnceTask::start(std::function<void()> job, bool background) {
     std::unique_lock<std::mutex> lock(mu_);        // held from the decision to the thread being in place: wait() sees both or neither
     int expected = kIdle;

@@ -41,6 +41,7 @@ bool ItemsForms::pack2(const LineTables &lt, Image &img, dev::Dfa2Device &t) {
 }
 
 void plan_engines(const std::string &pattern, int engine, Programs &p) {
+    p.requested = engine;
     p.ref = build_reference_automaton(pattern);
     p.trimmed = trim(p.ref);
     const Reduced red = reduce(p.trimmed);

@@ -1,6 +1,6 @@
 // plan.hpp — the decisions between a pattern and its device images (host only: no HIP): which programs are lowered for a
 // requested engine and which engine AUTO ends on, which forms of a DFA table fit the device, how the search tables are planned,
-// and how a program is dumped as words (rrx_program_words).  The fit rules are stated here or nowhere: abi.cpp and the
+// and how a program is dumped as words (rrx_program_words).  The fit rules are stated here or nowhere: the ABI layer (regex.cpp) and the
 // sanitizer driver (tests/cpp/host_pipeline_driver.cpp) both call them.
 #pragma once
 #include <string>
@@ -62,6 +62,7 @@ struct Programs {
     NfaProgram nfa_block;        // up to 65536 positions, exception edges in CSR form (wave-resident engine)
     bool has_block = false;
     LineTables match;
+    int requested = 0;           // the RRX_ENGINE_* asked for (plan_engines)
     int engine = 0;
     const char *engine_name() const;
     bool accepts_empty() const;

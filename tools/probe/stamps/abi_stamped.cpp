@@ -1,5 +1,6 @@
-// PROBE BUILD (not shipped): the C ABI plus one entry that runs the stamped stride-2 kernel on a corpus.
-#include "../../../roaringregex_amd/csrc/abi.cpp"
+// PROBE BUILD (not shipped): the product's objects plus one entry that runs the stamped stride-2 kernel on a corpus.
+#include "../../../roaringregex_amd/csrc/handles.hpp"
+using namespace rrx;
 namespace rrx { namespace dev {
 int match_stripes_dfa2_stamped(const Dfa2Device &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
                                size_t nstripes, uint32_t *accept, uint64_t *stamps, uint64_t *rounds, void *stream);
