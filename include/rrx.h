@@ -274,6 +274,28 @@ int rrx_contains_extents(const rrx_regex *re, int device, const void *d_bytes, c
                          uint32_t *d_bits, void *stream);
 int rrx_contains_items(const rrx_regex *re, const rrx_items *items, uint32_t *d_bits, void *stream);
 
+/* WHERE the first match of every item is: rrx_search_corpus for explicit items (what regexp_extract, find and substring need of a
+ * string column; re-packing the column as '\n'-delimited text is wrong as soon as an item holds a '\n', and costs a copy and an
+ * index pass).  Item i is d_bytes[d_off[i] .. d_off[i+1] - trim), as in rrx_contains_extents; a trim larger than the item's
+ * length leaves the empty item.  [d_start[i], d_end[i]) - offsets relative to the start of item i - is the substring of item i
+ * that the pattern accepts as a whole string (regex.h:156-162) with the smallest end, and among those the smallest start;
+ * 0xFFFFFFFF in both when no substring is accepted.  '\n' is an ordinary byte and may be part of a match; NUL and bytes >= 0x80
+ * are ordinary text that no pattern takes.  A pattern that accepts the empty string gives [0, 0) for every item, an empty item
+ * included (two fills, no table, no kernel); an empty-language pattern 0xFFFFFFFF everywhere.  d_start and d_end hold nitems
+ * words each; every one of them is written on `stream`, whatever it held.  nitems == 0 writes nothing and returns RRX_OK - a
+ * regex without search tables is still reported.  Both calls are FULLY asynchronous on `stream` and can be captured into a graph:
+ * a lane per item on the two plain search tables (RRX_PROGRAM_SEARCH_FWD to the first accepting position, RRX_PROGRAM_SEARCH_REV
+ * back from there to the last accepting one), the kernel reads the offsets itself - no extent bound, no read-back, no scratch, no
+ * event, unlike rrx_match_extents; rrx_search_items uses the handle's bytes, offsets, item count, trim and device only (not its
+ * index).  Both tables sit in LDS when together they fit 64 KiB, else - and for a regex compiled with RRX_ENGINE_DFA_GLOBAL - in
+ * HBM/L2.  RRX_ERR_ARG for null arguments (checked before any device call); RRX_ERR_UNSUPPORTED only where the forward or the
+ * reverse search automaton does not determinise within the state budget (16384 states) - the fit rules of rrx_search_corpus'
+ * kernel play no part.  LONG ITEMS: offsets are 32-bit - only matches that end at or before offset 0xFFFFFFFE of their item are
+ * reported, the forward pass stops there.                                                                                   */
+int rrx_search_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                       uint32_t *d_start, uint32_t *d_end, void *stream);
+int rrx_search_items(const rrx_regex *re, const rrx_items *items, uint32_t *d_start, uint32_t *d_end, void *stream);
+
 /* ONE device-resident string of any length (regex.h:156-159: operator++ consumes the whole string; '\n' and every
  * other byte are ordinary, a NUL or a byte >= 0x80 rejects).  d_accept[0] = 1 iff accepted.  Strings of 32 KiB and
  * more are split into chunks that are stepped in parallel from every table state (automata with <= 254 table

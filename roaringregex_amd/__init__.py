@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "rrx_match_string", "rrx_match_host", "rrx_match_cstr",
     "rrx_contains_corpus", "rrx_contains_engine_name", "rrx_contains_states", "rrx_bitmap_count",
     "rrx_contains_extents", "rrx_contains_items",
+    "rrx_search_extents", "rrx_search_items",
 )
 
 
@@ -120,6 +121,8 @@ def _load():
         "rrx_bitmap_count": (i32, [i32, vp, sz, vp, vp]),
         "rrx_contains_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp]),
         "rrx_contains_items": (i32, [vp, vp, vp, vp]),
+        "rrx_search_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, vp]),
+        "rrx_search_items": (i32, [vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -517,6 +520,33 @@ class RRegex:
             _check(_L.rrx_bitmap_to_bytes(data.device.index, C.c_void_p(bits.data_ptr() if n else 0), n,
                                           C.c_void_p(out.data_ptr() if n else 0), _stream_ptr(stream)))
         return out[:n]
+
+    def search_items(self, items, stream=None):
+        """Per item of an indexed batch (Items) the accepted substring [start, end) with the smallest end, then the smallest start
+        (rrx_search_items), as two int32 tensors of offsets relative to the start of the item; (-1, -1) where nothing is accepted.
+        '\\n', NUL and bytes >= 0x80 are ordinary text inside an item.  Asynchronous on `stream`."""
+        import torch
+        n = items.num_items
+        with _on(items.device, stream):
+            start = torch.empty(n, dtype=torch.int32, device=items.data.device)
+            end = torch.empty(n, dtype=torch.int32, device=items.data.device)
+            _check(_L.rrx_search_items(self._h, items._h, C.c_void_p(start.data_ptr() if n else 0), C.c_void_p(end.data_ptr() if n else 0),
+                                       _stream_ptr(stream)))
+        return start, end
+
+    def search_extents(self, data, offsets, trim=0, stream=None):
+        """The same for a batch nobody has indexed (rrx_search_extents): item i = data[offsets[i] : offsets[i+1] - trim] ->
+        (start, end), int32, (-1, -1) where nothing is accepted.  Nothing is read back: the call can be captured into a graph."""
+        import torch
+        n = offsets.numel() - 1
+        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+        with _on(data.device.index, stream):
+            start = torch.empty(n, dtype=torch.int32, device=data.device)
+            end = torch.empty(n, dtype=torch.int32, device=data.device)
+            _check(_L.rrx_search_extents(self._h, data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0),
+                                         C.c_void_p(offsets.data_ptr()), n, trim, C.c_void_p(start.data_ptr() if n else 0),
+                                         C.c_void_p(end.data_ptr() if n else 0), _stream_ptr(stream)))
+        return start, end
 
     def match_string(self, data, stream=None):
         """ONE device-resident string of any length (regex.h:156-159); '\n' is an ordinary character.  -> bool"""

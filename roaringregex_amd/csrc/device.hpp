@@ -257,6 +257,20 @@ int contains_extents_dfa(const DfaDevice &p, bool in_global, uint32_t found, con
 // the first ceil(nitems / 32) words of a stripe-wise result bitmap into `bits`, the last one masked to nitems
 int copy_result_bits(const uint32_t *result, size_t nitems, uint32_t *bits, void *stream);
 
+// ---- first match per explicit item, a lane per item: kernels_search_items.hip
+// The two search tables in their plain form, one image: fwd = "any bytes, then the pattern" (accepting exactly where a match ends),
+// rev = the pattern right to left (accepting, walking back from a match end, exactly where a match starts; row 0 dead and absorbing:
+// pack_search_items checks it).  '\n', NUL and bytes >= 0x80 are ordinary bytes of their class in both.
+struct SearchItemsDevice {
+    DfaDevice fwd, rev;
+};
+// Item i = bytes[off[i] .. off[i+1] - trim): [match_start[i], match_end[i]) = the accepted substring with the smallest end, then
+// the smallest start, relative to the item; ~0u in both where none is accepted.  Every one of the 2 x nitems words is written
+// with plain stores.  in_global: leave both tables in HBM/L2 whatever their size (they stay there anyway when together they pass
+// kPlainDfaLdsBudget).  Matches that end beyond offset 0xFFFFFFFE of an item are not reported.
+int search_extents_dfa(const SearchItemsDevice &p, bool in_global, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
+                       uint32_t *match_start, uint32_t *match_end, void *stream);
+
 // ---- one long string on the plain DFA: kernels_long.hip
 // One long string (regex.h:156-159 consumes it byte by byte): the string is cut into chunks, every chunk is stepped
 // from EVERY table state at once (lane = (chunk, start state); the lanes of a chunk read the same text), which yields

@@ -164,6 +164,11 @@ struct rrx_regex : rrx::Programs {                       // (plan.hpp: the progr
     int build_search() const;            // host side (call with `mu` held)
     // The stripe-wise kernel's tables on `device` (uploaded once); *out = nullptr for a pattern that accepts the empty string.
     int search_tables(int device, const rrx::dev::SearchChunkDevice **out) const;
+    // The lane-per-item search kernel's tables on `device` (search.fwd and search.rev in their plain form, uploaded once); *out =
+    // nullptr for a pattern that accepts the empty string.  RRX_ERR_UNSUPPORTED only where fwd or rev did not determinise: the fit
+    // rule of the stripe-wise kernel (build_search's return code) plays no part.
+    mutable std::map<int, OnDevice<rrx::dev::SearchItemsDevice>> search_items_on_device;
+    int search_item_tables(int device, const rrx::dev::SearchItemsDevice **out) const;
 
     // ---- the order of the stride-2 table's rows and columns in LDS (empty: as numbered).  The order costs no memory and decides
     // which entries share an LDS bank: bank = (row slot * row words + column slot) mod 32.  State 0 (dead) keeps slot 0.

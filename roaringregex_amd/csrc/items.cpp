@@ -1,4 +1,5 @@
-// items.cpp — explicit items (an offsets array: rrx_match_extents / rrx_contains_extents, and rrx_items, the batch indexed once)
+// items.cpp — explicit items (an offsets array: rrx_match_extents / rrx_contains_extents / rrx_search_extents, and rrx_items, the batch
+// indexed once)
 // and single strings (rrx_match_string, rrx_match_cstr).
 #include <algorithm>
 #include <cstring>
@@ -194,6 +195,34 @@ int rrx_contains_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_bit
     HIP_TRY(hipSetDevice(it->device));
     if (!it->nitems) return RRX_OK;
     return items_batch(re, re->contains_set, t, it, /*stripes_ok=*/true, d_bits, stream);
+}
+
+// WHERE the first match of every item is (rrx_search_corpus for explicit items): a lane per item on the two plain search tables.
+// Nothing is known on the host and nothing read back: the kernel takes every extent from the offsets.  A pattern that accepts the
+// empty string matches [0, 0) in every item: two fills, no table.  An empty batch still reports a regex without search tables.
+static int search_lanes(const rrx_regex *re, int device, const uint8_t *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, uint32_t *d_start,
+                        uint32_t *d_end, void *stream) {
+    const dev::SearchItemsDevice *t;
+    const int rc = re->search_item_tables(device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if (!nitems) return RRX_OK;
+    if (!t) {
+        HIP_TRY(hipMemsetAsync(d_start, 0, nitems * sizeof(uint32_t), (hipStream_t)stream));
+        HIP_TRY(hipMemsetAsync(d_end, 0, nitems * sizeof(uint32_t), (hipStream_t)stream));
+        return RRX_OK;
+    }
+    return launched(dev::search_extents_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, d_bytes, d_off, nitems, trim, d_start, d_end, stream),
+                    "search_extents launch");
+}
+int rrx_search_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                       uint32_t *d_start, uint32_t *d_end, void *stream) {
+    if (!re || (nitems && (!d_off || !d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
+    return search_lanes(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_start, d_end, stream);
+}
+int rrx_search_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_start, uint32_t *d_end, void *stream) {
+    if (!re || !it || (it->nitems && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
+    return search_lanes(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_start, d_end, stream);
 }
 
 // One device-resident string of any length.  Long strings take the chunk-map path when the automaton has a small

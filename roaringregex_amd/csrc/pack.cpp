@@ -116,6 +116,21 @@ bool pack_items(const DfaProgram &dfa, Image &img, dev::LineDfaDevice &d) {
     return true;
 }
 
+bool pack_search_items(const DfaProgram &fwd, const DfaProgram &rev, Image &img, dev::SearchItemsDevice &d) {
+    if (!fwd.nstates || !rev.nstates || rev.accepting[0]) return false;
+    for (uint32_t k = 0; k < rev.ncls; k++)
+        if (rev.next[k] != 0) return false;                      // row 0 of the reverse table must be dead and absorbing
+    auto plain = [&](const DfaProgram &p, dev::DfaDevice &t) {
+        img.put(t.cls, p.cls, 256);
+        img.put(t.next, p.next.data(), p.next.size() * 2);
+        img.put(t.acc, p.accepting.data(), p.accepting.size());
+        t.nstates = p.nstates; t.ncls = p.ncls; t.start = p.start;
+    };
+    plain(fwd, d.fwd);
+    plain(rev, d.rev);
+    return true;
+}
+
 void pack_lane_nfa(const NfaProgram &nfa, Image &img, dev::NfaDevice &d) {
     const uint32_t W = nfa.W, WP = (uint32_t)instantiated_width(W);
     std::vector<uint32_t> B((size_t)256 * WP, 0), X((size_t)nfa.nbits * WP, 0);

@@ -54,5 +54,9 @@ void pack_wave_nfa(const NfaProgram &nfa, const Trimmed &trimmed, uint32_t WL, b
 dev::SearchChunkDevice search_chunk_layout(const SearchLine2Program &s2, const DfaProgram &fwd, const DfaProgram &rev, bool in_global);
 void pack_search(const SearchLine2Program &s2, const DfaProgram &fwd, const DfaProgram &rev, const dev::SearchChunkDevice &layout, Image &img,
                  dev::SearchChunkDevice &d);
+// The lane-per-item search kernel's tables: fwd and rev in the plain form (cls / next / acc each), one image.  false where the
+// reverse table's row 0 is not its dead row - rejecting, every class back to itself (lower_dfa's numbering; the kernel stops a
+// lane there) - or a table is empty.
+bool pack_search_items(const DfaProgram &fwd, const DfaProgram &rev, Image &img, dev::SearchItemsDevice &d);
 
 }  // namespace rrx

@@ -96,6 +96,19 @@ int rrx_regex::search_tables(int device, const dev::SearchChunkDevice **out) con
     return upload_once(search_on_device, device, false, pack, out);
 }
 
+// The lane-per-item search kernel's tables on `device` (uploaded once); *out = nullptr for a pattern that accepts the empty string.
+// Whether the stripe-wise kernel's tables fit (build_search's return code) does not matter here: fwd and rev do.
+int rrx_regex::search_item_tables(int device, const dev::SearchItemsDevice **out) const {
+    std::lock_guard<std::mutex> lock(mu);
+    (void)build_search();
+    if (!search.fwd.nstates || !search.rev.nstates)
+        return fail(RRX_ERR_UNSUPPORTED, "no search tables: the forward or the reverse search automaton does not determinise within the state budget");
+    *out = nullptr;
+    if (search.nullable) return RRX_OK;
+    auto pack = [&](Image &img, dev::SearchItemsDevice &t) { return pack_search_items(search.fwd, search.rev, img, t); };
+    return upload_once(search_items_on_device, device, false, pack, out);
+}
+
 // "Contains a match" (rrx_contains_corpus): the forward search table with its accepting states folded into one absorbing
 // state (lower.hpp: contains_dfa), in the forms of the match path and by its fit rules (plan.hpp: LineTables) - the stride-2
 // form, the wide / classed LDS line table, the global line table; a regex compiled with RRX_ENGINE_DFA / _DFA_GLOBAL keeps it
@@ -357,10 +370,13 @@ size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t ca
         append_words(w, re->nfa_block, /*csr=*/true);
     } else if (kind == RRX_PROGRAM_SEARCH_LINE || kind == RRX_PROGRAM_SEARCH_LINE2 || kind == RRX_PROGRAM_SEARCH_FWD || kind == RRX_PROGRAM_SEARCH_REV) {
         std::lock_guard<std::mutex> lock(re->mu);
-        if (re->build_search()) return 0;
+        // (the two plain tables are dumped wherever they determinise - the lane-per-item search runs on them whether or not the
+        // stripe-wise kernel's tables fit the device; the line tables only where that kernel has them)
+        const bool fits = re->build_search() == RRX_OK;
         const SearchPlan &s = re->search;
-        if (kind == RRX_PROGRAM_SEARCH_FWD) append_words(w, s.fwd);
-        else if (kind == RRX_PROGRAM_SEARCH_REV) append_words(w, s.rev);
+        if (kind == RRX_PROGRAM_SEARCH_FWD) { if (s.fwd.nstates) append_words(w, s.fwd); }
+        else if (kind == RRX_PROGRAM_SEARCH_REV) { if (s.rev.nstates) append_words(w, s.rev); }
+        else if (!fits) return 0;
         else if (kind == RRX_PROGRAM_SEARCH_LINE && s.line.nrows) append_words(w, s.line, s.fwd);
         else if (kind == RRX_PROGRAM_SEARCH_LINE2 && s.line2.nrows) append_words(w, s.line2, s.layout);
     } else if (kind == RRX_PROGRAM_CONTAINS_DFA || kind == RRX_PROGRAM_CONTAINS_DFA2) {
