@@ -296,6 +296,43 @@ int rrx_search_extents(const rrx_regex *re, int device, const void *d_bytes, con
                        uint32_t *d_start, uint32_t *d_end, void *stream);
 int rrx_search_items(const rrx_regex *re, const rrx_items *items, uint32_t *d_start, uint32_t *d_end, void *stream);
 
+/* EVERY match of every item, left to right: rrx_search_all* for explicit items (what regexp_count, regexp_extract_all,
+ * regexp_replace and split need of a string column).  Item i is d_bytes[d_off[i] .. d_off[i+1] - trim), as in rrx_search_extents.
+ * The matches of an item are those of rrx_search_extents applied repeatedly TO THE REST OF THE ITEM behind the previous match:
+ * match k is the accepted substring of item[p_k:] with the smallest end, and among those the smallest start; p_0 = 0, p_{k+1} = the
+ * end of match k, one byte further after an empty match; offsets are relative to the start of the item.  A match never starts
+ * before the end of the previous one, even where a longer substring reaching back across it would be accepted ("ab|bab" on "abab":
+ * [0,2) and [2,4), not [1,4)).  '\n' is an ordinary byte and may be part of a match; NUL and bytes >= 0x80 are ordinary text that
+ * no pattern takes.  A pattern that accepts the empty string has the matches [k, k) for k = 0 ... length of the item - length + 1
+ * of them, 1 for an empty item (no table, no text); an empty-language pattern has none.  LONG ITEMS as rrx_search_extents: only
+ * matches that end at or before offset 0xFFFFFFFE of their item are found.
+ * Two passes: _count writes d_count[i] = matches of item i - every one of the nitems words, whatever it held; the caller turns the
+ * counts into the exclusive prefix d_first[i] (u64); _fill writes match k of item i to slot d_first[i] + k of d_start / d_end and no
+ * other slot.  Both are FULLY asynchronous on `stream` and can be captured into a graph once the tables are uploaded: no read-back,
+ * no scratch, no event, no extent bound.  A lane per item on the two plain search tables (kernels_search_all_items.hip), both in
+ * LDS when together they fit 64 KiB, else - and for a regex compiled with RRX_ENGINE_DFA_GLOBAL - in HBM/L2; _count steps the
+ * forward table alone and resets it at every match end, _fill walks back on the reverse table from every match end to the end of
+ * the previous match.  A wave of 64 consecutive items takes as long as its longest item, and a lane's result stores are scattered.
+ * The one-call form mirrors rrx_search_all: d_first has nitems + 1 entries, d_first[nitems] = *total; the match arrays hold `cap`
+ * entries, matches in slots >= cap are counted, not written - if *total > cap call again with arrays of *total entries (d_first
+ * is complete either way).  Synchronous (returns *total).  It is _count, a device scan and _fill, the counts and the scan's scratch
+ * in device memory the call allocates and frees: calls share nothing and may overlap.  The scan carries 30 bits per count: an item
+ * with 2^30 or more matches needs the two-pass form.  nitems == 0: d_first[0] = 0, *total = 0.
+ * rrx_search_all_items* use the handle's bytes, offsets, item count, trim and device only (not its index).
+ * RRX_ERR_ARG for null arguments, checked before any device call (d_start / d_end may be null where nothing can be written:
+ * cap == 0 or nitems == 0); RRX_ERR_UNSUPPORTED exactly where rrx_search_extents returns it, for an empty batch too.          */
+int rrx_search_all_extents_count(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                 uint32_t *d_count, void *stream);
+int rrx_search_all_extents_fill(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, void *stream);
+int rrx_search_all_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                           uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap, size_t *total, void *stream);
+int rrx_search_all_items_count(const rrx_regex *re, const rrx_items *items, uint32_t *d_count, void *stream);
+int rrx_search_all_items_fill(const rrx_regex *re, const rrx_items *items, const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end,
+                              void *stream);
+int rrx_search_all_items(const rrx_regex *re, const rrx_items *items, uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap,
+                         size_t *total, void *stream);
+
 /* ONE device-resident string of any length (regex.h:156-159: operator++ consumes the whole string; '\n' and every
  * other byte are ordinary, a NUL or a byte >= 0x80 rejects).  d_accept[0] = 1 iff accepted.  Strings of 32 KiB and
  * more are split into chunks that are stepped in parallel from every table state (automata with <= 254 table

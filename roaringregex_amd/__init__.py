@@ -46,6 +46,8 @@ ABI_SYMBOLS = (
     "rrx_contains_corpus", "rrx_contains_engine_name", "rrx_contains_states", "rrx_bitmap_count",
     "rrx_contains_extents", "rrx_contains_items",
     "rrx_search_extents", "rrx_search_items",
+    "rrx_search_all_extents_count", "rrx_search_all_extents_fill", "rrx_search_all_extents",
+    "rrx_search_all_items_count", "rrx_search_all_items_fill", "rrx_search_all_items",
 )
 
 
@@ -123,6 +125,12 @@ def _load():
         "rrx_contains_items": (i32, [vp, vp, vp, vp]),
         "rrx_search_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, vp]),
         "rrx_search_items": (i32, [vp, vp, vp, vp, vp]),
+        "rrx_search_all_extents_count": (i32, [vp, i32, vp, vp, sz, u32, vp, vp]),
+        "rrx_search_all_extents_fill": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, vp, vp]),
+        "rrx_search_all_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, vp, sz, C.POINTER(sz), vp]),
+        "rrx_search_all_items_count": (i32, [vp, vp, vp, vp]),
+        "rrx_search_all_items_fill": (i32, [vp, vp, vp, vp, vp, vp]),
+        "rrx_search_all_items": (i32, [vp, vp, vp, vp, vp, sz, C.POINTER(sz), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -547,6 +555,79 @@ class RRegex:
                                          C.c_void_p(offsets.data_ptr()), n, trim, C.c_void_p(start.data_ptr() if n else 0),
                                          C.c_void_p(end.data_ptr() if n else 0), _stream_ptr(stream)))
         return start, end
+
+    def _search_all_two_pass(self, dev, n, count_call, fill_call):
+        """count, the prefix with torch, fill -> (count, first, start, end), as search_all shapes them."""
+        import torch
+        count = torch.zeros(n, dtype=torch.int32, device=dev)
+        _check(count_call(C.c_void_p(count.data_ptr() if n else 0)))
+        inclusive = torch.cumsum(count, dim=0, dtype=torch.int64)
+        first = inclusive - count
+        total = int(inclusive[-1].item()) if n else 0
+        start = torch.empty(total, dtype=torch.int32, device=dev)
+        end = torch.empty(total, dtype=torch.int32, device=dev)
+        if total:
+            _check(fill_call(C.c_void_p(first.data_ptr()), C.c_void_p(start.data_ptr()), C.c_void_p(end.data_ptr())))
+        return count, first, start, end
+
+    def _search_all_one_call(self, dev, n, cap, call):
+        """The one-call entry, repeated with the exact size if `cap` was too small -> (first[n + 1], start, end)."""
+        import torch
+        first = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        cap = int(cap) if cap is not None else 2 * n + 1024
+        while True:
+            start = torch.empty(cap, dtype=torch.int32, device=dev)
+            end = torch.empty(cap, dtype=torch.int32, device=dev)
+            total = C.c_size_t(0)
+            _check(call(C.c_void_p(first.data_ptr()), C.c_void_p(start.data_ptr() if cap else 0), C.c_void_p(end.data_ptr() if cap else 0), cap,
+                        C.byref(total)))
+            if total.value <= cap:
+                break
+            cap = total.value
+        return first, start[:total.value], end[:total.value]
+
+    def search_all_items(self, items, stream=None):
+        """ALL matches of every item of an indexed batch (Items), left to right (rrx_search_all_items_count / _fill) ->
+        (count[n] int32, first[n] int64, start[total] int32, end[total] int32), shaped as search_all returns them: the matches of
+        item i are start/end[first[i] : first[i] + count[i]], relative to the item.  Match k + 1 is searched in the rest of the item
+        behind match k; '\\n', NUL and bytes >= 0x80 are ordinary text inside an item."""
+        with _on(items.device, stream):
+            s = _stream_ptr(stream)
+            return self._search_all_two_pass(items.data.device, items.num_items,
+                                             lambda c: _L.rrx_search_all_items_count(self._h, items._h, c, s),
+                                             lambda f, st, en: _L.rrx_search_all_items_fill(self._h, items._h, f, st, en, s))
+
+    def search_all_extents(self, data, offsets, trim=0, stream=None):
+        """The same for a batch nobody has indexed (rrx_search_all_extents_count / _fill): item i = data[offsets[i] : offsets[i+1] - trim]."""
+        import torch
+        n = offsets.numel() - 1
+        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+        d, b, o = data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0), C.c_void_p(offsets.data_ptr())
+        with _on(d, stream):
+            s = _stream_ptr(stream)
+            return self._search_all_two_pass(data.device, n,
+                                             lambda c: _L.rrx_search_all_extents_count(self._h, d, b, o, n, trim, c, s),
+                                             lambda f, st, en: _L.rrx_search_all_extents_fill(self._h, d, b, o, n, trim, f, st, en, s))
+
+    def search_all_items_fused(self, items, cap=None, stream=None):
+        """The same result through the one-call entry (rrx_search_all_items) -> (first[n + 1] int64 CSR offsets, start[total] int32,
+        end[total] int32).  cap: entries to provide for at first (default: two per item); the call is repeated with the exact size
+        if there are more."""
+        with _on(items.device, stream):
+            s = _stream_ptr(stream)
+            return self._search_all_one_call(items.data.device, items.num_items, cap,
+                                             lambda f, st, en, cp, tot: _L.rrx_search_all_items(self._h, items._h, f, st, en, cp, tot, s))
+
+    def search_all_extents_fused(self, data, offsets, trim=0, cap=None, stream=None):
+        """The one-call entry for a batch nobody has indexed (rrx_search_all_extents) -> (first[n + 1], start, end)."""
+        import torch
+        n = offsets.numel() - 1
+        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+        d, b, o = data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0), C.c_void_p(offsets.data_ptr())
+        with _on(d, stream):
+            s = _stream_ptr(stream)
+            return self._search_all_one_call(data.device, n, cap,
+                                             lambda f, st, en, cp, tot: _L.rrx_search_all_extents(self._h, d, b, o, n, trim, f, st, en, cp, tot, s))
 
     def match_string(self, data, stream=None):
         """ONE device-resident string of any length (regex.h:156-159); '\n' is an ordinary character.  -> bool"""

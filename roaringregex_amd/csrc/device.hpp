@@ -271,6 +271,19 @@ struct SearchItemsDevice {
 int search_extents_dfa(const SearchItemsDevice &p, bool in_global, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
                        uint32_t *match_start, uint32_t *match_end, void *stream);
 
+// ---- all matches per explicit item, a lane per item: kernels_search_all_items.hip
+// The matches of item i are those of search_extents_dfa applied again and again to the rest of the item behind the previous match
+// (patterns that do not accept the empty string: every match has a byte).  first == nullptr: count[i] = their number, every one of
+// the nitems words written with a plain store - the forward table alone is placed and stepped.  Otherwise (`first`: the caller's
+// exclusive prefix of the counts) match k of item i goes to slot first[i] + k of match_start / match_end, relative to the item;
+// slots >= cap are not written, nor any other slot.  Placement and long items as search_extents_dfa.
+int search_all_extents_dfa(const SearchItemsDevice &p, bool in_global, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
+                           uint32_t *count, const uint64_t *first, uint32_t *match_start, uint32_t *match_end, size_t cap, void *stream);
+// The same for a pattern that accepts the empty string: [k, k) for k = 0 .. the item's trimmed length (empty_matches for an offsets
+// array with a trim) - no table, no text.
+int empty_item_matches(const uint64_t *off, size_t nitems, uint32_t trim, uint32_t *count, const uint64_t *first, uint32_t *match_start,
+                       uint32_t *match_end, size_t cap, void *stream);
+
 // ---- one long string on the plain DFA: kernels_long.hip
 // One long string (regex.h:156-159 consumes it byte by byte): the string is cut into chunks, every chunk is stepped
 // from EVERY table state at once (lane = (chunk, start state); the lanes of a chunk read the same text), which yields

@@ -1,5 +1,5 @@
-// items.cpp — explicit items (an offsets array: rrx_match_extents / rrx_contains_extents / rrx_search_extents, and rrx_items, the batch
-// indexed once)
+// items.cpp — explicit items (an offsets array: rrx_match_extents / rrx_contains_extents / rrx_search_extents / rrx_search_all_extents*,
+// and rrx_items, the batch indexed once)
 // and single strings (rrx_match_string, rrx_match_cstr).
 #include <algorithm>
 #include <cstring>
@@ -223,6 +223,81 @@ int rrx_search_extents(const rrx_regex *re, int device, const void *d_bytes, con
 int rrx_search_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_start, uint32_t *d_end, void *stream) {
     if (!re || !it || (it->nitems && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
     return search_lanes(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_start, d_end, stream);
+}
+
+// EVERY match of every item (rrx_search_all* for explicit items): search_lanes' tables and kernel shape, the search applied again
+// to the rest of the item behind each match.  d_first == nullptr: the counts; otherwise the matches into the slots behind
+// d_first[i], those below `cap`.  Nothing is known on the host and nothing read back.  A pattern that accepts the empty string has
+// the matches [k, k) for k = 0 .. length: no table, no text.  An empty batch still reports a regex without search tables.
+static int search_all_lanes(const rrx_regex *re, int device, const uint8_t *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, uint32_t *d_count,
+                            const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap, void *stream) {
+    const dev::SearchItemsDevice *t;
+    const int rc = re->search_item_tables(device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if (!nitems) return RRX_OK;
+    if (!t) return launched(dev::empty_item_matches(d_off, nitems, trim, d_count, d_first, d_start, d_end, cap, stream), "empty_item_matches launch");
+    return launched(dev::search_all_extents_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, d_bytes, d_off, nitems, trim, d_count, d_first, d_start, d_end,
+                                                cap, stream),
+                    "search_all_extents launch");
+}
+// count + scan + fill in one call, the counts and the scan's scratch in device memory of the call's own (freed when it leaves:
+// hipFree waits for what is queued): calls share nothing.
+static int search_all_one_call(const rrx_regex *re, int device, const uint8_t *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, uint64_t *d_first,
+                               uint32_t *d_start, uint32_t *d_end, size_t cap, size_t *total, void *stream) {
+    *total = 0;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = search_all_lanes(re, device, d_bytes, d_off, 0, trim, nullptr, nullptr, nullptr, nullptr, 0, stream);      // (the tables, the device)
+    if (rc) return rc;
+    if (!nitems) { HIP_TRY(hipMemsetAsync(d_first, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
+    DeviceArray<uint32_t> d_count;
+    DeviceArray<uint64_t> d_sums;
+    hipError_t he = d_count.alloc(device, nitems * sizeof(uint32_t));
+    if (he == hipSuccess) he = d_sums.alloc(device, dev::scan_scratch_words(nitems) * sizeof(uint64_t));
+    if (he != hipSuccess) return hip_fail(he, "hipMalloc(search_all counts)");
+    rc = search_all_lanes(re, device, d_bytes, d_off, nitems, trim, d_count, nullptr, nullptr, nullptr, 0, stream);
+    if (rc) return rc;
+    const int le = dev::scan_counts(d_count, d_first, d_sums, nitems, stream);  // d_first[nitems] = total
+    if (le) return hip_fail((hipError_t)le, "search_all scan launch");
+    he = hipMemsetAsync(d_first, 0, sizeof(uint64_t), st);                      // the scan marks entry 0 as a stripe start: not here
+    uint64_t tot = 0;
+    if (he == hipSuccess) he = hipMemcpyAsync(&tot, d_first + nitems, sizeof tot, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return hip_fail(he, "search_all scan");
+    *total = (size_t)tot;
+    if (tot && cap) {                                                            // matches in slots >= cap are counted, not written
+        rc = search_all_lanes(re, device, d_bytes, d_off, nitems, trim, nullptr, d_first, d_start, d_end, cap, stream);
+        if (!rc) { he = hipStreamSynchronize(st); if (he != hipSuccess) rc = hip_fail(he, "search_all fill"); }
+    }
+    return rc;
+}
+int rrx_search_all_extents_count(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                 uint32_t *d_count, void *stream) {
+    if (!re || (nitems && (!d_off || !d_count))) return fail(RRX_ERR_ARG, "null argument");
+    return search_all_lanes(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_count, nullptr, nullptr, nullptr, 0, stream);
+}
+int rrx_search_all_extents_fill(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, void *stream) {
+    if (!re || (nitems && (!d_off || !d_first || !d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
+    return search_all_lanes(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, nullptr, d_first, d_start, d_end, ~(size_t)0, stream);
+}
+int rrx_search_all_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                           uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap, size_t *total, void *stream) {
+    if (!re || !total || !d_first || (nitems && (!d_off || (cap && (!d_start || !d_end))))) return fail(RRX_ERR_ARG, "null argument");
+    return search_all_one_call(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_first, d_start, d_end, cap, total, stream);
+}
+int rrx_search_all_items_count(const rrx_regex *re, const rrx_items *it, uint32_t *d_count, void *stream) {
+    if (!re || !it || (it->nitems && !d_count)) return fail(RRX_ERR_ARG, "null argument");
+    return search_all_lanes(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_count, nullptr, nullptr, nullptr, 0, stream);
+}
+int rrx_search_all_items_fill(const rrx_regex *re, const rrx_items *it, const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, void *stream) {
+    if (!re || !it || (it->nitems && (!d_first || !d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
+    return search_all_lanes(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, nullptr, d_first, d_start, d_end, ~(size_t)0, stream);
+}
+int rrx_search_all_items(const rrx_regex *re, const rrx_items *it, uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap, size_t *total,
+                         void *stream) {
+    if (!re || !it || !total || !d_first || (it->nitems && cap && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
+    return search_all_one_call(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_first, d_start, d_end, cap, total, stream);
 }
 
 // One device-resident string of any length.  Long strings take the chunk-map path when the automaton has a small
