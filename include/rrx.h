@@ -145,6 +145,11 @@ int         rrx_accepts_empty(const rrx_regex *re); /* Processor::operator*() on
 #define RRX_PROGRAM_CONTAINS_DFA2_ITEMS 18 /* the contains table's stride-2 ITEMS form (rrx_contains_extents / rrx_contains_items, trim 1), in exactly
                                     the RRX_PROGRAM_DFA2_ITEMS layout; 0 words where the contains table has no stride-2 form (RRX_ENGINE_DFA /
                                     _DFA_GLOBAL too) or the items form does not fit.  (The byte-stride forms step RRX_PROGRAM_CONTAINS_DFA.)   */
+#define RRX_PROGRAM_SEARCH_STARTS 19   /* leftmost-longest search (rrx_search_longest_extents): "any bytes, then the pattern right to left",
+                                         DFA layout - stepped from an item's last byte down, accepting where a match starts; no dead row  */
+#define RRX_PROGRAM_SEARCH_ANCHORED 20 /* ... and the pattern's own DFA, DFA layout: state 0 dead and absorbing, class 0 leads there - stepped
+                                         forwards from a match start, accepting where a match from there ends.  Both: 0 words where one
+                                         of the two does not determinise within the state budget                                          */
 size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t cap);
 
 /* ---- batch of strings: the replacement for calling get_acceptance_iter(line)++ per string ------------ *
@@ -291,10 +296,34 @@ int rrx_contains_items(const rrx_regex *re, const rrx_items *items, uint32_t *d_
  * HBM/L2.  RRX_ERR_ARG for null arguments (checked before any device call); RRX_ERR_UNSUPPORTED only where the forward or the
  * reverse search automaton does not determinise within the state budget (16384 states) - the fit rules of rrx_search_corpus'
  * kernel play no part.  LONG ITEMS: offsets are 32-bit - only matches that end at or before offset 0xFFFFFFFE of their item are
- * reported, the forward pass stops there.                                                                                   */
+ * reported, the forward pass stops there.  This is NOT what a regex user calls the first match - [0-9]+ on "abc 12345 x" answers
+ * [4, 5), "1": rrx_search_longest_extents / rrx_search_longest_items below give the leftmost-longest match, [4, 9).              */
 int rrx_search_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                        uint32_t *d_start, uint32_t *d_end, void *stream);
 int rrx_search_items(const rrx_regex *re, const rrx_items *items, uint32_t *d_start, uint32_t *d_end, void *stream);
+
+/* The LEFTMOST-LONGEST match of every item: what regexp_extract, find and substring mean in every SQL engine, in POSIX and in RE2's
+ * longest-match mode.  Item i is d_bytes[d_off[i] .. d_off[i+1] - trim); a trim larger than the item's length leaves the empty
+ * item.  d_start[i] is the smallest s such that some item[s, e) is accepted by the pattern as a whole string (regex.h:156-162);
+ * d_end[i] is the largest e such that item[d_start[i], e) is accepted; offsets relative to the start of item i.  No match gives
+ * 0xFFFFFFFF in both.  '\n' is an ordinary byte and may be part of a match; NUL and bytes >= 0x80 are ordinary text that no pattern
+ * takes.  A pattern that accepts the empty string has d_start[i] = 0 for every item; d_end[i] is the longest accepted prefix, 0 if
+ * none other; an empty item gives [0, 0).  An empty-language pattern gives 0xFFFFFFFF everywhere (two fills, no table).  d_start and
+ * d_end hold nitems words each; every one of the 2 x nitems words is written on `stream`, whatever it held.  nitems == 0 writes
+ * nothing and returns RRX_OK - an unsupported regex is still reported.  Both calls are FULLY asynchronous on `stream` and can be
+ * captured into a graph once the tables are uploaded (the first call on a device uploads them): no read-back, no scratch, no event,
+ * no extent bound; rrx_search_longest_items uses the handle's bytes, offsets, item count, trim and device only (not its index).
+ * A lane per item, two passes over two tables of their own (neither RRX_PROGRAM_SEARCH_FWD nor _REV is used): backwards on
+ * RRX_PROGRAM_SEARCH_STARTS from the item's last byte to its first - that table has no dead row, so the WHOLE item is read, there is
+ * no early exit -, then forwards on RRX_PROGRAM_SEARCH_ANCHORED from the start found to the item's end or the table's dead row.  A
+ * pattern that accepts the empty string runs the second pass alone.  Both tables sit in LDS when together they fit 64 KiB, else -
+ * and for a regex compiled with RRX_ENGINE_DFA_GLOBAL - in HBM/L2.  RRX_ERR_ARG for null arguments (checked before any device
+ * call); RRX_ERR_UNSUPPORTED only where one of the two tables does not determinise within the state budget (16384 states), for an
+ * empty batch too.  LONG ITEMS: offsets are 32-bit - an item longer than 0xFFFFFFFE bytes is searched as if it ended at its offset
+ * 0xFFFFFFFE.                                                                                                                */
+int rrx_search_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                               uint32_t *d_start, uint32_t *d_end, void *stream);
+int rrx_search_longest_items(const rrx_regex *re, const rrx_items *items, uint32_t *d_start, uint32_t *d_end, void *stream);
 
 /* EVERY match of every item, left to right: rrx_search_all* for explicit items (what regexp_count, regexp_extract_all,
  * regexp_replace and split need of a string column).  Item i is d_bytes[d_off[i] .. d_off[i+1] - trim), as in rrx_search_extents.

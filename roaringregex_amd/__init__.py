@@ -24,6 +24,7 @@ PROGRAM_DFA2_ORDER = 11
 PROGRAM_SAMPLED_DFA = 12
 PROGRAM_SAMPLED_DFA2 = 13
 PROGRAM_CONTAINS_DFA, PROGRAM_CONTAINS_DFA2 = 16, 17   # the contains table (rrx_contains_corpus) and its stride-2 form
+PROGRAM_SEARCH_STARTS, PROGRAM_SEARCH_ANCHORED = 19, 20  # the two tables of the leftmost-longest search (rrx_search_longest_extents)
 PROGRAM_CONTAINS_DFA2_ITEMS = 18                       # its stride-2 items form (rrx_contains_extents / rrx_contains_items, trim 1)
 OPT_BACKGROUND_ORDER = 1
 OPT_UNITS_PER_WORKGROUP = 2
@@ -48,6 +49,7 @@ ABI_SYMBOLS = (
     "rrx_search_extents", "rrx_search_items",
     "rrx_search_all_extents_count", "rrx_search_all_extents_fill", "rrx_search_all_extents",
     "rrx_search_all_items_count", "rrx_search_all_items_fill", "rrx_search_all_items",
+    "rrx_search_longest_extents", "rrx_search_longest_items",
 )
 
 
@@ -131,6 +133,8 @@ def _load():
         "rrx_search_all_items_count": (i32, [vp, vp, vp, vp]),
         "rrx_search_all_items_fill": (i32, [vp, vp, vp, vp, vp, vp]),
         "rrx_search_all_items": (i32, [vp, vp, vp, vp, vp, sz, C.POINTER(sz), vp]),
+        "rrx_search_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, vp]),
+        "rrx_search_longest_items": (i32, [vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -628,6 +632,33 @@ class RRegex:
             s = _stream_ptr(stream)
             return self._search_all_one_call(data.device, n, cap,
                                              lambda f, st, en, cp, tot: _L.rrx_search_all_extents(self._h, d, b, o, n, trim, f, st, en, cp, tot, s))
+
+    def search_longest_items(self, items, stream=None):
+        """Per item of an indexed batch (Items) the LEFTMOST-LONGEST match [start, end) (rrx_search_longest_items): the smallest start
+        of any accepted substring, then the largest end from there, as two int32 tensors of offsets relative to the start of the item;
+        (-1, -1) where nothing is accepted.  '\\n', NUL and bytes >= 0x80 are ordinary text inside an item.  Asynchronous on `stream`."""
+        import torch
+        n = items.num_items
+        with _on(items.device, stream):
+            start = torch.empty(n, dtype=torch.int32, device=items.data.device)
+            end = torch.empty(n, dtype=torch.int32, device=items.data.device)
+            _check(_L.rrx_search_longest_items(self._h, items._h, C.c_void_p(start.data_ptr() if n else 0), C.c_void_p(end.data_ptr() if n else 0),
+                                               _stream_ptr(stream)))
+        return start, end
+
+    def search_longest_extents(self, data, offsets, trim=0, stream=None):
+        """The same for a batch nobody has indexed (rrx_search_longest_extents): item i = data[offsets[i] : offsets[i+1] - trim] ->
+        (start, end), int32, (-1, -1) where nothing is accepted.  Nothing is read back: the call can be captured into a graph."""
+        import torch
+        n = offsets.numel() - 1
+        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+        with _on(data.device.index, stream):
+            start = torch.empty(n, dtype=torch.int32, device=data.device)
+            end = torch.empty(n, dtype=torch.int32, device=data.device)
+            _check(_L.rrx_search_longest_extents(self._h, data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0),
+                                                 C.c_void_p(offsets.data_ptr()), n, trim, C.c_void_p(start.data_ptr() if n else 0),
+                                                 C.c_void_p(end.data_ptr() if n else 0), _stream_ptr(stream)))
+        return start, end
 
     def match_string(self, data, stream=None):
         """ONE device-resident string of any length (regex.h:156-159); '\n' is an ordinary character.  -> bool"""

@@ -284,6 +284,22 @@ int search_all_extents_dfa(const SearchItemsDevice &p, bool in_global, const uin
 int empty_item_matches(const uint64_t *off, size_t nitems, uint32_t trim, uint32_t *count, const uint64_t *first, uint32_t *match_start,
                        uint32_t *match_end, size_t cap, void *stream);
 
+// ---- leftmost-longest match per explicit item, a lane per item: kernels_search_longest_items.hip
+// Two plain tables, one image: starts = "any bytes, then the pattern right to left" (never dies; stepped from the item's last byte
+// down, accepting after the byte at offset s exactly when some match starts at s), anchored = the pattern's own DFA (stepped
+// forwards from a match start, accepting exactly where a match from there ends; row 0 dead and absorbing: pack_search_longest
+// checks it).  '\n', NUL and bytes >= 0x80 are ordinary bytes of their class in both.
+struct SearchLongestDevice {
+    DfaDevice starts, anchored;
+};
+// Item i = bytes[off[i] .. off[i+1] - trim): match_start[i] = the smallest s at which an accepted substring starts, match_end[i] =
+// the largest e with item[s, e) accepted, relative to the item; ~0u in both where none is accepted.  nullable (the pattern accepts
+// the empty string): the starts table is not stepped, start = 0 and end = the longest accepted prefix (0 if none other).  Every
+// one of the 2 x nitems words is written with plain stores.  in_global as for search_extents_dfa.  An item is searched as if it
+// ended at its offset 0xFFFFFFFE.
+int search_longest_extents_dfa(const SearchLongestDevice &p, bool in_global, bool nullable, const uint8_t *bytes, const uint64_t *off, size_t nitems,
+                               uint32_t trim, uint32_t *match_start, uint32_t *match_end, void *stream);
+
 // ---- one long string on the plain DFA: kernels_long.hip
 // One long string (regex.h:156-159 consumes it byte by byte): the string is cut into chunks, every chunk is stepped
 // from EVERY table state at once (lane = (chunk, start state); the lanes of a chunk read the same text), which yields

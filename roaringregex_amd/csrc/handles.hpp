@@ -169,6 +169,14 @@ struct rrx_regex : rrx::Programs {                       // (plan.hpp: the progr
     // rule of the stripe-wise kernel (build_search's return code) plays no part.
     mutable std::map<int, OnDevice<rrx::dev::SearchItemsDevice>> search_items_on_device;
     int search_item_tables(int device, const rrx::dev::SearchItemsDevice **out) const;
+    // The leftmost-longest search's two tables (plan.hpp: plan_search_longest), built at their first use beside `search`; they take
+    // no part in build_search's fit rules.  search_longest_tables: on `device` (uploaded once); *out = nullptr for the empty language
+    // (no table: nothing matches).  RRX_ERR_UNSUPPORTED only where one of the two does not determinise.
+    mutable int search_longest_state = 0;        // 0 = not built, 1 = built, -1 = does not determinise
+    mutable rrx::SearchLongestPlan search_longest;
+    mutable std::map<int, OnDevice<rrx::dev::SearchLongestDevice>> search_longest_on_device;
+    int build_search_longest() const;    // host side (call with `mu` held)
+    int search_longest_tables(int device, const rrx::dev::SearchLongestDevice **out) const;
 
     // ---- the order of the stride-2 table's rows and columns in LDS (empty: as numbered).  The order costs no memory and decides
     // which entries share an LDS bank: bank = (row slot * row words + column slot) mod 32.  State 0 (dead) keeps slot 0.

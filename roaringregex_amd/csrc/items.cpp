@@ -225,6 +225,36 @@ int rrx_search_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_start
     return search_lanes(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_start, d_end, stream);
 }
 
+// The LEFTMOST-LONGEST match of every item: a lane per item on the starts table (backwards over the whole item: the smallest start)
+// and the anchored table (forwards from there: the largest end).  Nothing is known on the host and nothing read back.  The empty
+// language matches nowhere: two fills, no table.  A pattern that accepts the empty string starts at 0 everywhere and runs the
+// forward pass alone.  An empty batch still reports a regex whose tables do not determinise.
+static int search_longest_lanes(const rrx_regex *re, int device, const uint8_t *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                uint32_t *d_start, uint32_t *d_end, void *stream) {
+    const dev::SearchLongestDevice *t;
+    const int rc = re->search_longest_tables(device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if (!nitems) return RRX_OK;
+    if (!t) {
+        HIP_TRY(hipMemsetAsync(d_start, 0xff, nitems * sizeof(uint32_t), (hipStream_t)stream));
+        HIP_TRY(hipMemsetAsync(d_end, 0xff, nitems * sizeof(uint32_t), (hipStream_t)stream));
+        return RRX_OK;
+    }
+    return launched(dev::search_longest_extents_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, re->search_longest.nullable, d_bytes, d_off, nitems, trim,
+                                                    d_start, d_end, stream),
+                    "search_longest_extents launch");
+}
+int rrx_search_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                               uint32_t *d_start, uint32_t *d_end, void *stream) {
+    if (!re || (nitems && (!d_off || !d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
+    return search_longest_lanes(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_start, d_end, stream);
+}
+int rrx_search_longest_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_start, uint32_t *d_end, void *stream) {
+    if (!re || !it || (it->nitems && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
+    return search_longest_lanes(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_start, d_end, stream);
+}
+
 // EVERY match of every item (rrx_search_all* for explicit items): search_lanes' tables and kernel shape, the search applied again
 // to the rest of the item behind each match.  d_first == nullptr: the counts; otherwise the matches into the slots behind
 // d_first[i], those below `cap`.  Nothing is known on the host and nothing read back.  A pattern that accepts the empty string has

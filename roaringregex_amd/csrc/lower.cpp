@@ -1123,6 +1123,12 @@ static Reduced reversed(const Reduced &r) {
 bool search_dfas(const Reduced &r, uint32_t max_states, DfaProgram &fwd, DfaProgram &rev) {
     return subset_construct(r, max_states, true, fwd) && subset_construct(reversed(r), max_states, false, rev);
 }
+bool search_longest_dfas(const Reduced &r, uint32_t max_states, DfaProgram &starts, DfaProgram &anchored) {
+    if (subset_construct(reversed(r), max_states, true, starts) && subset_construct(r, max_states, false, anchored)) return true;
+    starts = DfaProgram();
+    anchored = DfaProgram();
+    return false;
+}
 
 // "Does the line contain a match": the forward search table with every accepting state folded into one absorbing accepting
 // state FOUND (the line's verdict is in, it waits for the '\n'), minimised again.  Row 0 of the forward table - the empty set,

@@ -166,6 +166,13 @@ bool lower_dfa_sampled(const Reduced &r, const uint8_t *sample, uint32_t pieces,
 // byte kills it, it is accepting exactly at the positions where some match ends.  rev: the DFA of the pattern read
 // right to left - walked backwards from a match end it is accepting exactly at the positions where a match starts.
 bool search_dfas(const Reduced &r, uint32_t max_states, DfaProgram &fwd, DfaProgram &rev);
+// Leftmost-longest search (rrx_search_longest_extents): the other two of the four combinations {pattern, pattern reversed} x
+// {anchored, "any bytes first"}.  starts: the DFA of "any bytes, then the pattern right to left" - no byte kills it (no dead row
+// is ever reached: a pass over it has no early exit); stepped from an item's last byte down to its first it is accepting after the
+// byte at offset s exactly when some match starts at s.  anchored: the pattern's own DFA (lower_dfa: class 0 leads to the dead
+// row 0) - stepped forwards from a match start it is accepting exactly where a match from there ends.  false where one of them
+// does not determinise within max_states; both are empty then.
+bool search_longest_dfas(const Reduced &r, uint32_t max_states, DfaProgram &starts, DfaProgram &anchored);
 // "Contains a match" (rrx_contains_corpus): `fwd` with its accepting states folded into one absorbing accepting state, minimised;
 // state 0 = the SKIP row (absorbing, rejecting, reached from nowhere), never more states than `fwd` has.  Class 0 (NUL, bytes
 // >= 0x80, bytes the pattern does not mention) is a live column: it leads where `fwd` says.  Steps like any DfaProgram in line

@@ -131,6 +131,21 @@ bool pack_search_items(const DfaProgram &fwd, const DfaProgram &rev, Image &img,
     return true;
 }
 
+bool pack_search_longest(const DfaProgram &starts, const DfaProgram &anchored, Image &img, dev::SearchLongestDevice &d) {
+    if (!starts.nstates || !anchored.nstates || anchored.accepting[0]) return false;
+    for (uint32_t k = 0; k < anchored.ncls; k++)
+        if (anchored.next[k] != 0) return false;                 // row 0 of the anchored table must be dead and absorbing
+    auto plain = [&](const DfaProgram &p, dev::DfaDevice &t) {
+        img.put(t.cls, p.cls, 256);
+        img.put(t.next, p.next.data(), p.next.size() * 2);
+        img.put(t.acc, p.accepting.data(), p.accepting.size());
+        t.nstates = p.nstates; t.ncls = p.ncls; t.start = p.start;
+    };
+    plain(starts, d.starts);
+    plain(anchored, d.anchored);
+    return true;
+}
+
 void pack_lane_nfa(const NfaProgram &nfa, Image &img, dev::NfaDevice &d) {
     const uint32_t W = nfa.W, WP = (uint32_t)instantiated_width(W);
     std::vector<uint32_t> B((size_t)256 * WP, 0), X((size_t)nfa.nbits * WP, 0);

@@ -58,5 +58,8 @@ void pack_search(const SearchLine2Program &s2, const DfaProgram &fwd, const DfaP
 // reverse table's row 0 is not its dead row - rejecting, every class back to itself (lower_dfa's numbering; the kernel stops a
 // lane there) - or a table is empty.
 bool pack_search_items(const DfaProgram &fwd, const DfaProgram &rev, Image &img, dev::SearchItemsDevice &d);
+// The leftmost-longest kernel's tables: starts and anchored in the plain form, one image.  false where the anchored table's row 0
+// is not its dead row - rejecting, every class back to itself (the kernel stops a lane there) - or a table is empty.
+bool pack_search_longest(const DfaProgram &starts, const DfaProgram &anchored, Image &img, dev::SearchLongestDevice &d);
 
 }  // namespace rrx

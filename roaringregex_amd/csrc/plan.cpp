@@ -108,6 +108,15 @@ bool plan_search(const Reduced &red, bool use_anchored, bool accepts_empty, Sear
     return ok && (s.nullable || s.layout.nrows);
 }
 
+bool plan_search_longest(const Reduced &red, bool accepts_empty, SearchLongestPlan &s) {
+    s = SearchLongestPlan();
+    if (!search_longest_dfas(red, kMaxSubsetStates, s.starts, s.anchored)) return false;
+    s.nullable = accepts_empty;
+    s.empty = true;
+    for (uint8_t a : s.anchored.accepting) s.empty = s.empty && !a;
+    return true;
+}
+
 void append_words(std::vector<uint32_t> &w, const NfaProgram &p, bool csr) {
     w.insert(w.end(), {p.W, p.nbits, p.n_exc, p.accepts_empty ? 1u : 0u});
     for (auto *v : {&p.init, &p.fin, &p.chain, &p.self, &p.excm, &p.cgrp, &p.ctgt, &p.B}) w.insert(w.end(), v->begin(), v->end());

@@ -84,6 +84,16 @@ struct SearchPlan {
 using SearchLdsBytes = size_t (*)(const dev::SearchChunkDevice &);
 bool plan_search(const Reduced &red, bool use_anchored, bool accepts_empty, SearchLdsBytes lds_bytes, SearchPlan &out);
 
+// The tables of the leftmost-longest search per item (lower.hpp: search_longest_dfas).  No fit rule: the lane-per-item kernel takes
+// plain tables of any size (LDS or HBM/L2).
+struct SearchLongestPlan {
+    DfaProgram starts, anchored;
+    bool nullable = false;       // the pattern accepts the empty string: start = 0 everywhere, the starts table is not stepped
+    bool empty = false;          // the empty language (no accepting state in `anchored`): no match anywhere, no table
+};
+// false: one of the two tables does not determinise within kMaxSubsetStates (both stay empty).
+bool plan_search_longest(const Reduced &red, bool accepts_empty, SearchLongestPlan &out);
+
 // rrx_program_words: the word layouts that tests/program_replay.py reads.
 void append_words(std::vector<uint32_t> &w, const NfaProgram &p, bool csr);                   // csr: xoff / xtgt in the place of X
 void append_words(std::vector<uint32_t> &w, const DfaProgram &d, bool escaped = false);       // escaped: then the escaped flag per state

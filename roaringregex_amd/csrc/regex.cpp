@@ -109,6 +109,25 @@ int rrx_regex::search_item_tables(int device, const dev::SearchItemsDevice **out
     return upload_once(search_items_on_device, device, false, pack, out);
 }
 
+// Host side of the leftmost-longest search's tables (call with `mu` held): the starts table and the anchored table, built once.
+int rrx_regex::build_search_longest() const {
+    if (search_longest_state == 0) search_longest_state = plan_search_longest(reduce(trimmed), accepts_empty(), search_longest) ? 1 : -1;
+    return search_longest_state == 1 ? RRX_OK
+                                     : fail(RRX_ERR_UNSUPPORTED, "no leftmost-longest search tables: the starts automaton or the anchored automaton "
+                                                                  "does not determinise within the state budget");
+}
+// Those tables on `device` (uploaded once); *out = nullptr for the empty language.  A nullable pattern has them too: its anchored
+// table finds the longest accepted prefix.
+int rrx_regex::search_longest_tables(int device, const dev::SearchLongestDevice **out) const {
+    std::lock_guard<std::mutex> lock(mu);
+    const int rc = build_search_longest();
+    if (rc) return rc;
+    *out = nullptr;
+    if (search_longest.empty) return RRX_OK;
+    auto pack = [&](Image &img, dev::SearchLongestDevice &t) { return pack_search_longest(search_longest.starts, search_longest.anchored, img, t); };
+    return upload_once(search_longest_on_device, device, false, pack, out);
+}
+
 // "Contains a match" (rrx_contains_corpus): the forward search table with its accepting states folded into one absorbing
 // state (lower.hpp: contains_dfa), in the forms of the match path and by its fit rules (plan.hpp: LineTables) - the stride-2
 // form, the wide / classed LDS line table, the global line table; a regex compiled with RRX_ENGINE_DFA / _DFA_GLOBAL keeps it
@@ -379,6 +398,10 @@ size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t ca
         else if (!fits) return 0;
         else if (kind == RRX_PROGRAM_SEARCH_LINE && s.line.nrows) append_words(w, s.line, s.fwd);
         else if (kind == RRX_PROGRAM_SEARCH_LINE2 && s.line2.nrows) append_words(w, s.line2, s.layout);
+    } else if (kind == RRX_PROGRAM_SEARCH_STARTS || kind == RRX_PROGRAM_SEARCH_ANCHORED) {
+        std::lock_guard<std::mutex> lock(re->mu);
+        if (re->build_search_longest()) return 0;
+        append_words(w, kind == RRX_PROGRAM_SEARCH_STARTS ? re->search_longest.starts : re->search_longest.anchored);
     } else if (kind == RRX_PROGRAM_CONTAINS_DFA || kind == RRX_PROGRAM_CONTAINS_DFA2) {
         std::lock_guard<std::mutex> lock(re->mu);
         if (re->build_contains()) return 0;
