@@ -365,7 +365,8 @@ int rrx_search_all_items(const rrx_regex *re, const rrx_items *items, uint64_t *
 /* ONE device-resident string of any length (regex.h:156-159: operator++ consumes the whole string; '\n' and every
  * other byte are ordinary, a NUL or a byte >= 0x80 rejects).  d_accept[0] = 1 iff accepted.  Strings of 32 KiB and
  * more are split into chunks that are stepped in parallel from every table state (automata with <= 254 table
- * states); synchronous with respect to `stream`.                                                                */
+ * states); synchronous with respect to `stream`.  d_bytes needs no alignment: a string may start at any address
+ * (a chunk that does not start on a 16-byte boundary is read byte by byte instead of sixteen bytes per load).    */
 int rrx_match_string(const rrx_regex *re, int device, const void *d_bytes, size_t nbytes, uint8_t *d_accept, void *stream);
 
 /* ---- host-buffer conveniences (PCIe inclusive; synchronous) ------------------------------------------ */

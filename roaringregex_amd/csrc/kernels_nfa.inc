@@ -262,13 +262,17 @@ __global__ __launch_bounds__(256) void long_rows_nfa_kernel(NfaDevice prog, cons
     for (int i = 0; i < W; i++) st.s[i] = (uint32_t)i == (p >> 5) ? 1u << (p & 31) : 0u;
     auto alive = [&]() { uint32_t o = 0; for (int i = 0; i < W; i++) o |= st.s[i]; return o != 0; };
     size_t pos = a;
-    for (; pos + 16 <= b && alive(); pos += 16) {                     // chunk starts are multiples of 16, the base is 16-byte aligned
-        const uint4 v = *reinterpret_cast<const uint4 *>(bytes + pos);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    // chunk starts are multiples of 16 from the base, and the base may sit at any address (rrx.h asks for no alignment):
+    // sixteen bytes per load only where the chunk starts on a 16-byte boundary, as long_walk does; else byte by byte
+    if ((reinterpret_cast<uintptr_t>(bytes + pos) & 15) == 0) {
+        for (; pos + 16 <= b && alive(); pos += 16) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(bytes + pos);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const uint32_t c = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
-            if (c == 0 || c >= 0x80) eng.kill(st); else eng.step(st, c);
+            for (int i = 0; i < 16; i++) {
+                const uint32_t c = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
+                if (c == 0 || c >= 0x80) eng.kill(st); else eng.step(st, c);
+            }
         }
     }
     for (; pos < b && alive(); pos++) { const uint32_t c = bytes[pos]; if (c == 0 || c >= 0x80) eng.kill(st); else eng.step(st, c); }
