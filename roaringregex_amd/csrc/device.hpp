@@ -248,6 +248,7 @@ int items_match(const LineDfaDevice &p, const uint8_t *bytes, size_t nbytes, siz
                 ItemVerdicts out, void *stream, const uint64_t *resolve_off = nullptr, const uint32_t *skip_if = nullptr);
 
 // ---- contains for explicit items, a lane per item: kernels_contains_items.hip
+// (What the five lane-per-item kernels - this one, match_extents_kernel, the three searches below - share, their walk included: item_lanes.hpp.)
 // `p`: the contains table in its plain form ('\n', NUL and bytes >= 0x80 are ordinary bytes of their class; nothing kills).
 // found: its one accepting state if that state is absorbing - a lane stops reading there -, ~0u: none.  in_global: leave the
 // table in HBM/L2 whatever its size.  Whole words of `bits` are written with plain stores (ceil(nitems / 32) of them, the bits

@@ -19,6 +19,10 @@ extern "C" {
 // below these a batch stays on the lane-per-item kernel (the index costs more than it saves)
 static constexpr size_t kItemsStripesMin = (size_t)1 << 16;
 static constexpr size_t kItemsStripesMinBytes = (size_t)8 << 20;
+// A batch of items as the lane-per-item paths take it: the raw arguments of an _extents entry, or an rrx_items without its index.
+struct ItemBatch { int device; const uint8_t *bytes; const uint64_t *off; size_t nitems; uint32_t trim; };
+static ItemBatch batch_of(int device, const void *d_bytes, const uint64_t *d_off, size_t n, uint32_t trim) { return {device, static_cast<const uint8_t *>(d_bytes), d_off, n, trim}; }
+static ItemBatch batch_of(const rrx_items *it) { return {it->device, it->d_bytes, it->d_off, it->nitems, it->trim}; }
 // A lane (lane group, workgroup) per item: the match set on the regex' engine, one byte per item; the contains set on the plain
 // arrays of its table, the bitmap itself.
 static int extents_lanes(const rrx_regex *re, const TableSet &set, const DeviceTables *t, const uint8_t *b, const uint64_t *d_off, size_t nitems,
@@ -200,8 +204,8 @@ int rrx_contains_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_bit
 // WHERE the first match of every item is (rrx_search_corpus for explicit items): a lane per item on the two plain search tables.
 // Nothing is known on the host and nothing read back: the kernel takes every extent from the offsets.  A pattern that accepts the
 // empty string matches [0, 0) in every item: two fills, no table.  An empty batch still reports a regex without search tables.
-static int search_lanes(const rrx_regex *re, int device, const uint8_t *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, uint32_t *d_start,
-                        uint32_t *d_end, void *stream) {
+static int search_lanes(const rrx_regex *re, const ItemBatch &b, uint32_t *d_start, uint32_t *d_end, void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
     const dev::SearchItemsDevice *t;
     const int rc = re->search_item_tables(device, &t);
     if (rc) return rc;
@@ -212,25 +216,24 @@ static int search_lanes(const rrx_regex *re, int device, const uint8_t *d_bytes,
         HIP_TRY(hipMemsetAsync(d_end, 0, nitems * sizeof(uint32_t), (hipStream_t)stream));
         return RRX_OK;
     }
-    return launched(dev::search_extents_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, d_bytes, d_off, nitems, trim, d_start, d_end, stream),
+    return launched(dev::search_extents_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, bytes, off, nitems, trim, d_start, d_end, stream),
                     "search_extents launch");
 }
 int rrx_search_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                        uint32_t *d_start, uint32_t *d_end, void *stream) {
     if (!re || (nitems && (!d_off || !d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
-    return search_lanes(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_start, d_end, stream);
+    return search_lanes(re, batch_of(device, d_bytes, d_off, nitems, trim), d_start, d_end, stream);
 }
 int rrx_search_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_start, uint32_t *d_end, void *stream) {
     if (!re || !it || (it->nitems && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
-    return search_lanes(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_start, d_end, stream);
+    return search_lanes(re, batch_of(it), d_start, d_end, stream);
 }
 
-// The LEFTMOST-LONGEST match of every item: a lane per item on the starts table (backwards over the whole item: the smallest start)
-// and the anchored table (forwards from there: the largest end).  Nothing is known on the host and nothing read back.  The empty
-// language matches nowhere: two fills, no table.  A pattern that accepts the empty string starts at 0 everywhere and runs the
-// forward pass alone.  An empty batch still reports a regex whose tables do not determinise.
-static int search_longest_lanes(const rrx_regex *re, int device, const uint8_t *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
-                                uint32_t *d_start, uint32_t *d_end, void *stream) {
+// The LEFTMOST-LONGEST match of every item, on the starts table (backwards over the whole item: the smallest start) and the
+// anchored table (forwards from there: the largest end).  The empty language matches nowhere: two fills, no table.  A pattern that
+// accepts the empty string starts at 0 everywhere and runs the forward pass alone.  (No tables: they do not determinise.)
+static int search_longest_lanes(const rrx_regex *re, const ItemBatch &b, uint32_t *d_start, uint32_t *d_end, void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
     const dev::SearchLongestDevice *t;
     const int rc = re->search_longest_tables(device, &t);
     if (rc) return rc;
@@ -241,43 +244,45 @@ static int search_longest_lanes(const rrx_regex *re, int device, const uint8_t *
         HIP_TRY(hipMemsetAsync(d_end, 0xff, nitems * sizeof(uint32_t), (hipStream_t)stream));
         return RRX_OK;
     }
-    return launched(dev::search_longest_extents_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, re->search_longest.nullable, d_bytes, d_off, nitems, trim,
+    return launched(dev::search_longest_extents_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, re->search_longest.nullable, bytes, off, nitems, trim,
                                                     d_start, d_end, stream),
                     "search_longest_extents launch");
 }
 int rrx_search_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                                uint32_t *d_start, uint32_t *d_end, void *stream) {
     if (!re || (nitems && (!d_off || !d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
-    return search_longest_lanes(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_start, d_end, stream);
+    return search_longest_lanes(re, batch_of(device, d_bytes, d_off, nitems, trim), d_start, d_end, stream);
 }
 int rrx_search_longest_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_start, uint32_t *d_end, void *stream) {
     if (!re || !it || (it->nitems && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
-    return search_longest_lanes(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_start, d_end, stream);
+    return search_longest_lanes(re, batch_of(it), d_start, d_end, stream);
 }
 
 // EVERY match of every item (rrx_search_all* for explicit items): search_lanes' tables and kernel shape, the search applied again
 // to the rest of the item behind each match.  d_first == nullptr: the counts; otherwise the matches into the slots behind
-// d_first[i], those below `cap`.  Nothing is known on the host and nothing read back.  A pattern that accepts the empty string has
-// the matches [k, k) for k = 0 .. length: no table, no text.  An empty batch still reports a regex without search tables.
-static int search_all_lanes(const rrx_regex *re, int device, const uint8_t *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, uint32_t *d_count,
-                            const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap, void *stream) {
+// d_first[i], those below `cap`.  A pattern that accepts the empty string has the matches [k, k) for k = 0 .. length: no table, no
+// text.
+static int search_all_lanes(const rrx_regex *re, const ItemBatch &b, uint32_t *d_count, const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap,
+                            void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
     const dev::SearchItemsDevice *t;
     const int rc = re->search_item_tables(device, &t);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(device));
     if (!nitems) return RRX_OK;
-    if (!t) return launched(dev::empty_item_matches(d_off, nitems, trim, d_count, d_first, d_start, d_end, cap, stream), "empty_item_matches launch");
-    return launched(dev::search_all_extents_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, d_bytes, d_off, nitems, trim, d_count, d_first, d_start, d_end,
+    if (!t) return launched(dev::empty_item_matches(off, nitems, trim, d_count, d_first, d_start, d_end, cap, stream), "empty_item_matches launch");
+    return launched(dev::search_all_extents_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, bytes, off, nitems, trim, d_count, d_first, d_start, d_end,
                                                 cap, stream),
                     "search_all_extents launch");
 }
 // count + scan + fill in one call, the counts and the scan's scratch in device memory of the call's own (freed when it leaves:
 // hipFree waits for what is queued): calls share nothing.
-static int search_all_one_call(const rrx_regex *re, int device, const uint8_t *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, uint64_t *d_first,
-                               uint32_t *d_start, uint32_t *d_end, size_t cap, size_t *total, void *stream) {
+static int search_all_one_call(const rrx_regex *re, const ItemBatch &b, uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap, size_t *total,
+                               void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
     *total = 0;
     hipStream_t st = (hipStream_t)stream;
-    int rc = search_all_lanes(re, device, d_bytes, d_off, 0, trim, nullptr, nullptr, nullptr, nullptr, 0, stream);      // (the tables, the device)
+    int rc = search_all_lanes(re, batch_of(device, bytes, off, 0, trim), nullptr, nullptr, nullptr, nullptr, 0, stream);      // (the tables, the device)
     if (rc) return rc;
     if (!nitems) { HIP_TRY(hipMemsetAsync(d_first, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
     DeviceArray<uint32_t> d_count;
@@ -285,7 +290,7 @@ static int search_all_one_call(const rrx_regex *re, int device, const uint8_t *d
     hipError_t he = d_count.alloc(device, nitems * sizeof(uint32_t));
     if (he == hipSuccess) he = d_sums.alloc(device, dev::scan_scratch_words(nitems) * sizeof(uint64_t));
     if (he != hipSuccess) return hip_fail(he, "hipMalloc(search_all counts)");
-    rc = search_all_lanes(re, device, d_bytes, d_off, nitems, trim, d_count, nullptr, nullptr, nullptr, 0, stream);
+    rc = search_all_lanes(re, b, d_count, nullptr, nullptr, nullptr, 0, stream);
     if (rc) return rc;
     const int le = dev::scan_counts(d_count, d_first, d_sums, nitems, stream);  // d_first[nitems] = total
     if (le) return hip_fail((hipError_t)le, "search_all scan launch");
@@ -296,7 +301,7 @@ static int search_all_one_call(const rrx_regex *re, int device, const uint8_t *d
     if (he != hipSuccess) return hip_fail(he, "search_all scan");
     *total = (size_t)tot;
     if (tot && cap) {                                                            // matches in slots >= cap are counted, not written
-        rc = search_all_lanes(re, device, d_bytes, d_off, nitems, trim, nullptr, d_first, d_start, d_end, cap, stream);
+        rc = search_all_lanes(re, b, nullptr, d_first, d_start, d_end, cap, stream);
         if (!rc) { he = hipStreamSynchronize(st); if (he != hipSuccess) rc = hip_fail(he, "search_all fill"); }
     }
     return rc;
@@ -304,30 +309,30 @@ static int search_all_one_call(const rrx_regex *re, int device, const uint8_t *d
 int rrx_search_all_extents_count(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                                  uint32_t *d_count, void *stream) {
     if (!re || (nitems && (!d_off || !d_count))) return fail(RRX_ERR_ARG, "null argument");
-    return search_all_lanes(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_count, nullptr, nullptr, nullptr, 0, stream);
+    return search_all_lanes(re, batch_of(device, d_bytes, d_off, nitems, trim), d_count, nullptr, nullptr, nullptr, 0, stream);
+}
+int rrx_search_all_items_count(const rrx_regex *re, const rrx_items *it, uint32_t *d_count, void *stream) {
+    if (!re || !it || (it->nitems && !d_count)) return fail(RRX_ERR_ARG, "null argument");
+    return search_all_lanes(re, batch_of(it), d_count, nullptr, nullptr, nullptr, 0, stream);
 }
 int rrx_search_all_extents_fill(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                                 const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, void *stream) {
     if (!re || (nitems && (!d_off || !d_first || !d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
-    return search_all_lanes(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, nullptr, d_first, d_start, d_end, ~(size_t)0, stream);
+    return search_all_lanes(re, batch_of(device, d_bytes, d_off, nitems, trim), nullptr, d_first, d_start, d_end, ~(size_t)0, stream);
+}
+int rrx_search_all_items_fill(const rrx_regex *re, const rrx_items *it, const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, void *stream) {
+    if (!re || !it || (it->nitems && (!d_first || !d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
+    return search_all_lanes(re, batch_of(it), nullptr, d_first, d_start, d_end, ~(size_t)0, stream);
 }
 int rrx_search_all_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                            uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap, size_t *total, void *stream) {
     if (!re || !total || !d_first || (nitems && (!d_off || (cap && (!d_start || !d_end))))) return fail(RRX_ERR_ARG, "null argument");
-    return search_all_one_call(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_first, d_start, d_end, cap, total, stream);
-}
-int rrx_search_all_items_count(const rrx_regex *re, const rrx_items *it, uint32_t *d_count, void *stream) {
-    if (!re || !it || (it->nitems && !d_count)) return fail(RRX_ERR_ARG, "null argument");
-    return search_all_lanes(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_count, nullptr, nullptr, nullptr, 0, stream);
-}
-int rrx_search_all_items_fill(const rrx_regex *re, const rrx_items *it, const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, void *stream) {
-    if (!re || !it || (it->nitems && (!d_first || !d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
-    return search_all_lanes(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, nullptr, d_first, d_start, d_end, ~(size_t)0, stream);
+    return search_all_one_call(re, batch_of(device, d_bytes, d_off, nitems, trim), d_first, d_start, d_end, cap, total, stream);
 }
 int rrx_search_all_items(const rrx_regex *re, const rrx_items *it, uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap, size_t *total,
                          void *stream) {
     if (!re || !it || !total || !d_first || (it->nitems && cap && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
-    return search_all_one_call(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_first, d_start, d_end, cap, total, stream);
+    return search_all_one_call(re, batch_of(it), d_first, d_start, d_end, cap, total, stream);
 }
 
 // One device-resident string of any length.  Long strings take the chunk-map path when the automaton has a small

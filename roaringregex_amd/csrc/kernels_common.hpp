@@ -1,5 +1,5 @@
 // kernels_common.hpp — shared device code of every kernel translation unit (kernels_table, _index, _items, _long, _search,
-// _coop, _wave .hip and kernels_nfa.inc; the table engines on top of it: table_engines.hpp).  Originally one file:
+// _coop, _wave .hip and kernels_nfa.inc; the table engines on top of it: table_engines.hpp; the lane-per-item kernels: item_lanes.hpp).  Originally one file:
 // hand-written CDNA4 (gfx950) kernels for the RoaringRegex hot path.
 //
 // Replaces, for a whole batch of '\n'-delimited strings at once:
@@ -303,10 +303,8 @@ __device__ __forceinline__ void match_stripes_body(const Program &prog, const ui
     }
 }
 
-// ============================================================================================ extents kernel
-// One lane per item; bytes come straight from HBM/L2.  Used for explicit (offset,len) batches, for the
-// iterator facade's single strings, and wherever '\n' is an ordinary character.
-// Two entry points for one body.  The table engines run best as the compiler allocates them (66 VGPRs; capping them at 64
+// ============================================================================================ batch kernel entry points
+// Two kernels for one body.  The table engines run best as the compiler allocates them (66 VGPRs; capping them at 64
 // for a second workgroup per CU measured -6 %); the register-resident NFA engines gain from the cap (+2 ... +13 %,
 // W >= 2 spills a little to scratch).
 template <class Engine, class Program>
@@ -328,40 +326,6 @@ __global__ __launch_bounds__(kThreads) void match_stripes_onepass_kernel(Program
                                                                           uint32_t *__restrict__ counts, uint32_t *__restrict__ slabs) {
     match_stripes_body<Engine, Program, true>(prog, bytes, nbytes, stripe, nullptr, nullptr, 0, 0, counts, slabs);
 }
-template <class Engine, class Program>
-__global__ __launch_bounds__(kThreads) void match_extents_kernel(Program prog, const uint8_t *__restrict__ bytes,
-                                                                  const uint64_t *__restrict__ off, size_t nitems, uint32_t trim,
-                                                                  uint8_t *__restrict__ accept, const uint32_t *__restrict__ only_if) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    if (only_if && !*only_if) return;            // queued behind the stripe-wise kernel as its fallback: the batch was fit, nothing to do
-    Engine eng;
-    eng.load(prog, smem);
-    __syncthreads();
-    // (one item per lane when the grid covers the batch; the predicated fallback is launched with a bounded grid and strides)
-    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < nitems; i += (size_t)gridDim.x * kThreads) {
-    size_t b = off[i], e = off[i + 1];
-    e = e - b >= trim ? e - trim : b;
-    typename Engine::State st;
-    eng.reset(st);
-    bool dead = false;
-    size_t p = b;
-    auto one = [&](uint32_t c) {
-        if (c == 0 || c >= 0x80) { eng.kill(st); dead = true; }
-        else eng.step(st, c);
-    };
-    for (; p < e && (p & 15) && !dead; p++) one(bytes[p]);                 // up to 16-byte alignment
-    for (; p + 16 <= e && !dead; p += 16) {                                // 16 bytes per load
-        const uint4 v = *reinterpret_cast<const uint4 *>(bytes + p);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-            if (!dead) one((w[k >> 2] >> (8 * (k & 3))) & 0xffu);
-    }
-    for (; p < e && !dead; p++) one(bytes[p]);
-    accept[i] = eng.accepting(st) ? 1 : 0;
-    }
-}
-
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel, device and size increase, not once per launch.
 // (One slot array per kernel: `slots` is a function-local static of the calling template instantiation.)
 constexpr int kMaxDevices = 64;
@@ -406,20 +370,6 @@ int launch_stripes(const Program &p, size_t table_bytes, const uint8_t *bytes, s
     if (e != hipSuccess) return (int)e;
     size_t blocks = (nstripes + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(kThreads), lds, (hipStream_t)stream, p, bytes, nbytes, stripe, stripe_base, accept, stage_off, stage_words);
-    return (int)hipGetLastError();
-}
-
-template <class Engine, class Program>
-int launch_extents(const Program &p, size_t table_bytes, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
-                   uint8_t *accept, void *stream, const uint32_t *only_if = nullptr) {
-    if (!nitems) return 0;
-    auto k = match_extents_kernel<Engine, Program>;
-    static LdsAttr attr;
-    hipError_t e = ensure_dynamic_lds(attr, reinterpret_cast<const void *>(k), table_bytes);
-    if (e != hipSuccess) return (int)e;
-    size_t blocks = (nitems + kThreads - 1) / kThreads;
-    if (only_if && blocks > 1024) blocks = 1024;      // the fallback behind the stripe-wise kernel mostly has nothing to do: a grid that ends at once (86 k workgroups: 33 us)
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(kThreads), table_bytes, (hipStream_t)stream, p, bytes, off, nitems, trim, accept, only_if);
     return (int)hipGetLastError();
 }
 

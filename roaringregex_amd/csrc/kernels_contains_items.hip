@@ -1,21 +1,20 @@
 // kernels_contains_items.hip — "which items contain a match" (rrx_contains_extents / rrx_contains_items): the lane-per-item
 // kernel on the plain contains table and the copy of a stripe-wise result out of its scratch bitmap.  The stripe-wise forms are
 // the items kernels themselves on the contains items tables (kernels_items.hip: items_match / items_match2).
-#include "table_engines.hpp"
+#include "item_lanes.hpp"
 
 namespace rrx {
 namespace dev {
 namespace {
 
-// One lane per item on the contains table (lower.hpp: contains_dfa) in its plain form.  match_extents_kernel's walk - head up to
-// 16-byte alignment, 16 bytes per load, tail - with three differences:
+// One lane per item on the contains table (lower.hpp: contains_dfa) in its plain form: the walk of item_lanes.hpp, aligned on the
+// offset as in match_extents_kernel, with three differences from that kernel:
 //  * no byte kills: NUL and bytes >= 0x80 are class 0 in the table's own byte -> class map, and class 0 is a live column here;
 //  * a lane stops reading once its state cannot change any more: `found`, the one accepting state, is absorbing, and so is row 0
 //    (SKIP - the start row of the empty language, unreachable otherwise).  found = ~0u: the host found no such state, no early exit;
-//  * the result is a bitmap.  A pass of the grid-stride loop gives every wave 64 CONSECUTIVE items starting at a multiple of 64:
-//    one ballot gathers their verdicts, lane 0 writes them as two plain 32-bit stores.  The wave owns both words - no atomics, and
-//    nothing to clear beforehand; lanes behind the last item vote 0, a second word wholly behind the last item is not written.
-//    The loop runs on the wave's first item, so every lane of a wave makes the same number of turns and the ballot sees them all.
+//  * the result is a bitmap.  One ballot gathers the verdicts of a pass' 64 consecutive items, lane 0 writes them as two plain 32-bit
+//    stores.  The wave owns both words - no atomics, and nothing to clear beforehand; lanes behind the last item vote 0, a second
+//    word wholly behind the last item is not written.
 template <class Engine, class Program>
 __global__ __launch_bounds__(kThreads) void contains_extents_kernel(Program prog, uint32_t found, const uint8_t *__restrict__ bytes,
                                                                      const uint64_t *__restrict__ off, size_t nitems, uint32_t trim,
@@ -25,14 +24,11 @@ __global__ __launch_bounds__(kThreads) void contains_extents_kernel(Program prog
     Engine eng;
     eng.load(prog, smem);
     __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    const size_t per_pass = (size_t)gridDim.x * kThreads;
-    for (size_t first = (size_t)blockIdx.x * kThreads + (threadIdx.x - lane); first < nitems; first += per_pass) {
+    for_each_wave_pass(nitems, [&](size_t first, uint32_t lane) {
         const size_t i = first + lane;
         bool hit = false;
         if (i < nitems) {
-            size_t b = off[i], e = off[i + 1];
-            e = e - b >= trim ? e - trim : b;
+            const auto [b, e] = item_span(off, i, trim);
             typename Engine::State st;
             eng.reset(st);
             bool done = st.s == found || st.s == 0;
@@ -57,7 +53,7 @@ __global__ __launch_bounds__(kThreads) void contains_extents_kernel(Program prog
             bits[first >> 5] = (uint32_t)verdicts;
             if (first + 32 < nitems) bits[(first >> 5) + 1] = (uint32_t)(verdicts >> 32);
         }
-    }
+    });
 }
 
 // The first `words` words of a stripe-wise result (scratch: padded, and bit nitems may be set by the batch's closing end) into the
@@ -68,30 +64,19 @@ __global__ __launch_bounds__(256) void copy_result_bits_kernel(const uint32_t *_
         dst[w] = w + 1 == words ? src[w] & last_mask : src[w];
 }
 
-template <class Engine>
-int launch_contains_extents(const DfaDevice &p, uint32_t found, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
-                            uint32_t *bits, void *stream, const uint32_t *only_if) {
-    auto k = contains_extents_kernel<Engine, DfaDevice>;
-    const size_t table_bytes = Engine::lds_bytes(p);
-    static LdsAttr attr;
-    hipError_t e = ensure_dynamic_lds(attr, reinterpret_cast<const void *>(k), table_bytes);
-    if (e != hipSuccess) return (int)e;
-    size_t blocks = (nitems + kThreads - 1) / kThreads;
-    if (only_if && blocks > 1024) blocks = 1024;      // (the fallback mostly has nothing to do: see launch_extents)
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(kThreads), table_bytes, (hipStream_t)stream, p, found, bytes, off, nitems, trim, bits, only_if);
-    return (int)hipGetLastError();
-}
-
 }  // namespace
 
 int contains_extents_dfa(const DfaDevice &p, bool in_global, uint32_t found, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
                          uint32_t *bits, void *stream, const uint32_t *only_if) {
     if (!nitems) return 0;
-    if (!p.nstates || !p.next || !p.cls || !p.acc) return (int)hipErrorInvalidValue;
+    if (!plain_table_ok(p)) return (int)hipErrorInvalidValue;
+    const size_t max_blocks = only_if ? kItemLanesMaxBlocks : 0;      // (the fallback mostly has nothing to do: see launch_extents)
     // tables beyond the LDS budget, and the tables of a regex that asked for the global form, stay in HBM/L2
     if (in_global || PlainDfaEngine::lds_bytes(p) > kPlainDfaLdsBudget)
-        return launch_contains_extents<PlainDfaGlobalEngine>(p, found, bytes, off, nitems, trim, bits, stream, only_if);
-    return launch_contains_extents<PlainDfaEngine>(p, found, bytes, off, nitems, trim, bits, stream, only_if);
+        return launch_item_lanes<contains_extents_kernel<PlainDfaGlobalEngine, DfaDevice>>(PlainDfaGlobalEngine::lds_bytes(p), nitems, max_blocks, stream, p, found,
+                                                                                          bytes, off, nitems, trim, bits, only_if);
+    return launch_item_lanes<contains_extents_kernel<PlainDfaEngine, DfaDevice>>(PlainDfaEngine::lds_bytes(p), nitems, max_blocks, stream, p, found, bytes, off,
+                                                                                nitems, trim, bits, only_if);
 }
 
 int copy_result_bits(const uint32_t *result, size_t nitems, uint32_t *bits, void *stream) {

@@ -1,7 +1,7 @@
 // kernels_nfa.inc — the shift-and NFA lane engines (state set in registers, bitmaps in LDS).  Shared device code:
 // kernels_common.hpp.  Compiled four times, once per group of widths (kernels_nfa_w1.hip ... _w16.hip define
 // RRX_NFA_PART): the instantiations of one group are a minute of hipcc, the groups build in parallel.
-#include "kernels_common.hpp"
+#include "item_lanes.hpp"
 
 namespace rrx {
 namespace dev {

@@ -2,14 +2,11 @@
 // item on the two plain search tables (lower.hpp: search_dfas), search_extents_kernel's grid shape.  The matches of an item are
 // those of rrx_search_extents applied again and again to the rest of the item behind the previous match.  The stripe-wise
 // all-matches kernels (kernels_search.hip) are tied to '\n'; here '\n' is a byte like any other.
-#include "table_engines.hpp"
+#include "item_lanes.hpp"
 
 namespace rrx {
 namespace dev {
 namespace {
-
-constexpr size_t kMaxMatchEnd = 0xfffffffeu;             // offsets are 32-bit (rrx_search_extents' rule): the forward pass stops here
-constexpr size_t kSearchAllItemsMaxBlocks = 1024;        // workgroups per launch: beyond 2^20 items the grid strides
 
 // One lane per item, a pass gives every wave 64 CONSECUTIVE items.  One body, two modes, for patterns that do NOT accept the empty
 // string (every match then has at least one byte, and the next search begins at the match end wherever the match starts):
@@ -20,9 +17,8 @@ constexpr size_t kSearchAllItemsMaxBlocks = 1024;        // workgroups per launc
 //    the state is reset and the stream goes on with the next byte of the vector already in registers (`k`: the first byte of `v`
 //    not yet consumed).  After each hit the lane walks back on rev (the pattern right to left) from the hit end down to the FLOOR -
 //    the end of the previous match, the item's first byte for the first one - as search_extents_kernel does down to the item's
-//    first byte: a tail down to 16-byte alignment, aligned 16-byte loads consumed high byte first, a head; it stops in dead row 0;
-//    the last accepting position is the start.  A hit guarantees an accepting position at or above the floor: fwd was reset there.
-//    Match n of item i goes to slot first[i] + n if that slot is below `cap`.
+//    first byte; it stops in dead row 0; the last accepting position is the start.  A hit guarantees an accepting position at or
+//    above the floor: fwd was reset there.  Match n of item i goes to slot first[i] + n if that slot is below `cap`.
 // No byte outside the item is ever read: a wide load is used only where all its 16 bytes lie inside [item start, item end), and,
 // walking back, inside [floor, hit end).  Alignment is that of the ADDRESS (d_bytes itself may sit anywhere).
 // A wave takes as long as its longest item, and a lane's result stores are scattered (one slot run per item).
@@ -36,16 +32,14 @@ __global__ __launch_bounds__(kThreads) void search_all_extents_kernel(SearchItem
     fwd.load(prog.fwd, smem);
     if constexpr (FILL) rev.load(prog.rev, smem + rev_lds_off);
     __syncthreads();
+    const size_t skew = reinterpret_cast<uintptr_t>(bytes) & 15;      // (p + skew) & 15 == 0: bytes + p is 16-byte aligned
+    // (for_each_wave_pass, written out: through the helper's lambda the compiler lays the FILL body out differently)
     const uint32_t lane = threadIdx.x & 63u;
     const size_t per_pass = (size_t)gridDim.x * kThreads;
-    const size_t skew = reinterpret_cast<uintptr_t>(bytes) & 15;      // (p + skew) & 15 == 0: bytes + p is 16-byte aligned
     for (size_t first_item = (size_t)blockIdx.x * kThreads + (threadIdx.x - lane); first_item < nitems; first_item += per_pass) {
         const size_t i = first_item + lane;
         if (i >= nitems) continue;
-        const size_t b = off[i];
-        size_t e = off[i + 1];
-        e = e - b >= trim ? e - trim : b;
-        if (e - b > kMaxMatchEnd) e = b + kMaxMatchEnd;
+        const auto [b, e] = item_span(off, i, trim, kMaxItemOffset);
         uint64_t slot = 0;                               // FILL: where this item's next match goes
         if constexpr (FILL) slot = first[i];
         uint32_t n = 0;                                  // matches so far
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(256) void empty_item_matches_kernel(const uint64_t 
     if (i >= nitems) return;
     const uint64_t b = off[i], e = off[i + 1];
     uint64_t len = e - b >= trim ? e - b - trim : 0;
-    if (len > kMaxMatchEnd) len = kMaxMatchEnd;          // (matches that end beyond offset 0xFFFFFFFE are not reported)
+    if (len > kMaxItemOffset) len = kMaxItemOffset;         // (matches that end beyond offset 0xFFFFFFFE are not reported)
     if constexpr (!FILL) { count[i] = (uint32_t)(len + 1); return; }
     const uint64_t slot = first[i];
     for (uint64_t k = 0; k <= len && slot + k < cap; k++) { match_start[slot + k] = (uint32_t)k; match_end[slot + k] = (uint32_t)k; }
@@ -130,17 +124,10 @@ __global__ __launch_bounds__(256) void empty_item_matches_kernel(const uint64_t 
 template <class Engine, bool FILL>
 int launch_search_all_extents(const SearchItemsDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim, uint32_t *count,
                               const uint64_t *first, uint32_t *match_start, uint32_t *match_end, size_t cap, void *stream) {
-    auto k = search_all_extents_kernel<Engine, FILL>;
     // COUNT places the forward table only
     const size_t rev_off = (Engine::lds_bytes(p.fwd) + 15) & ~(size_t)15, lds = FILL ? rev_off + Engine::lds_bytes(p.rev) : Engine::lds_bytes(p.fwd);
-    static LdsAttr attr;
-    hipError_t e = ensure_dynamic_lds(attr, reinterpret_cast<const void *>(k), lds);
-    if (e != hipSuccess) return (int)e;
-    size_t blocks = (nitems + kThreads - 1) / kThreads;
-    if (blocks > kSearchAllItemsMaxBlocks) blocks = kSearchAllItemsMaxBlocks;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(kThreads), lds, (hipStream_t)stream, p, (uint32_t)rev_off, bytes, off, nitems, trim, count, first,
-                       match_start, match_end, (uint64_t)cap);
-    return (int)hipGetLastError();
+    return launch_item_lanes<search_all_extents_kernel<Engine, FILL>>(lds, nitems, kItemLanesMaxBlocks, stream, p, (uint32_t)rev_off, bytes, off, nitems, trim,
+                                                                      count, first, match_start, match_end, (uint64_t)cap);
 }
 
 }  // namespace
@@ -148,10 +135,9 @@ int launch_search_all_extents(const SearchItemsDevice &p, const uint8_t *bytes, 
 int search_all_extents_dfa(const SearchItemsDevice &p, bool in_global, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
                            uint32_t *count, const uint64_t *first, uint32_t *match_start, uint32_t *match_end, size_t cap, void *stream) {
     if (!nitems) return 0;
-    for (const DfaDevice *t : {&p.fwd, &p.rev})
-        if (!t->nstates || !t->next || !t->cls || !t->acc) return (int)hipErrorInvalidValue;
-    // search_extents_dfa's placement rule, for both modes: LDS while the two tables together fit the budget
-    const bool global = in_global || PlainDfaEngine::lds_bytes(p.fwd) + PlainDfaEngine::lds_bytes(p.rev) > kPlainDfaLdsBudget;
+    if (!plain_table_ok(p.fwd) || !plain_table_ok(p.rev)) return (int)hipErrorInvalidValue;
+    // search_extents_dfa's placement rule, for both modes
+    const bool global = !two_tables_in_lds(p.fwd, p.rev, in_global);
     if (!first)
         return global ? launch_search_all_extents<PlainDfaGlobalEngine, false>(p, bytes, off, nitems, trim, count, first, match_start, match_end, cap, stream)
                       : launch_search_all_extents<PlainDfaEngine, false>(p, bytes, off, nitems, trim, count, first, match_start, match_end, cap, stream);

@@ -1,27 +1,21 @@
 // kernels_search_items.hip — "where is the first match of every item" (rrx_search_extents / rrx_search_items): a lane per item on
 // the two plain search tables (lower.hpp: search_dfas).  The stripe-wise search kernel (kernels_search.hip) is tied to '\n' through
 // its product table's columns and its chunk index; this one knows items only, and '\n' is a byte like any other.
-#include "table_engines.hpp"
+#include "item_lanes.hpp"
 
 namespace rrx {
 namespace dev {
 namespace {
 
-constexpr uint32_t kNoMatch = 0xffffffffu;
-constexpr size_t kMaxMatchEnd = 0xfffffffeu;             // offsets are 32-bit and ~0u says "none": the forward pass stops here
-constexpr size_t kSearchItemsMaxBlocks = 1024;           // workgroups per launch: beyond 2^20 items the grid strides
-
-// One lane per item, contains_extents_kernel's grid-stride shape: a pass gives every wave 64 CONSECUTIVE items, so the two result
-// stores of a wave are contiguous 256-byte rows.  Two phases per pass, each run by all lanes of the wave before the next begins
-// (a lane without a hit idles through the second one once per pass, not once per byte):
+// One lane per item, a pass of the grid-stride loop per 64 consecutive items (item_lanes.hpp: the loop, the item's span, the
+// walks).  Two phases per pass, each run by all lanes of the wave before the next begins (a lane without a hit idles through the
+// second one once per pass, not once per byte):
 //  * forward on fwd ("any bytes, then the pattern": never dies, accepting exactly where a match ends) from the item's first
-//    byte - a head up to 16-byte alignment, 16 bytes per load, a tail - until the first byte after which the state accepts: that
-//    byte's offset + 1 is `end`.  No state ever accepts: no match.
-//  * backward on rev (the pattern right to left) from the byte at end - 1 down to the item's first byte - a tail down to 16-byte
-//    alignment, aligned 16-byte loads consumed high byte first, a head.  Accepting after the byte at offset s: item[s, end) is
-//    accepted; `start` is the last such s seen, i.e. the smallest.  Row 0 of rev is dead and absorbing (pack_search_items checks
-//    it): a lane stops reading there.  A hit guarantees at least one accepting position (the CPU replay test asserts it).
-// No byte outside the item is ever read: a wide load is used only where all its 16 bytes lie inside [item start, item end).
+//    byte until the first byte after which the state accepts: that byte's offset + 1 is `end`.  No state ever accepts: no match.
+//  * backward on rev (the pattern right to left) from the byte at end - 1 down to the item's first byte.  Accepting after the byte
+//    at offset s: item[s, end) is accepted; `start` is the last such s seen, i.e. the smallest.  Row 0 of rev is dead and absorbing
+//    (pack_search_items checks it): a lane stops reading there.  A hit guarantees at least one accepting position (the CPU replay
+//    test asserts it).
 // Alignment is that of the ADDRESS (d_bytes itself may sit anywhere).  NUL and bytes >= 0x80 go through the tables' own byte ->
 // class maps like every other byte.
 template <class FwdEngine, class RevEngine>
@@ -34,16 +28,11 @@ __global__ __launch_bounds__(kThreads) void search_extents_kernel(SearchItemsDev
     fwd.load(prog.fwd, smem);
     rev.load(prog.rev, smem + rev_lds_off);
     __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    const size_t per_pass = (size_t)gridDim.x * kThreads;
     const size_t skew = reinterpret_cast<uintptr_t>(bytes) & 15;      // (p + skew) & 15 == 0: bytes + p is 16-byte aligned
-    for (size_t first = (size_t)blockIdx.x * kThreads + (threadIdx.x - lane); first < nitems; first += per_pass) {
+    for_each_wave_pass(nitems, [&](size_t first, uint32_t lane) {
         const size_t i = first + lane;
-        if (i >= nitems) continue;
-        const size_t b = off[i];
-        size_t e = off[i + 1];
-        e = e - b >= trim ? e - trim : b;
-        if (e - b > kMaxMatchEnd) e = b + kMaxMatchEnd;
+        if (i >= nitems) return;
+        const auto [b, e] = item_span(off, i, trim, kMaxItemOffset);
         // ---- forward: the smallest end
         size_t hit_end = 0;                              // one past the byte that made fwd accept
         bool hit = false;
@@ -91,23 +80,15 @@ __global__ __launch_bounds__(kThreads) void search_extents_kernel(SearchItemsDev
         }
         match_start[i] = s_out;
         match_end[i] = e_out;
-    }
+    });
 }
 
 template <class FwdEngine, class RevEngine>
 int launch_search_extents(const SearchItemsDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim, uint32_t *match_start,
                           uint32_t *match_end, void *stream) {
-    auto k = search_extents_kernel<FwdEngine, RevEngine>;
     const size_t rev_off = (FwdEngine::lds_bytes(p.fwd) + 15) & ~(size_t)15, lds = rev_off + RevEngine::lds_bytes(p.rev);
-    static LdsAttr attr;
-    hipError_t e = ensure_dynamic_lds(attr, reinterpret_cast<const void *>(k), lds);
-    if (e != hipSuccess) return (int)e;
-    // at most 1024 workgroups (two generations on the 256 CUs at two workgroups each): a workgroup copies its tables once and
-    // strides over the batch
-    size_t blocks = (nitems + kThreads - 1) / kThreads;
-    if (blocks > kSearchItemsMaxBlocks) blocks = kSearchItemsMaxBlocks;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(kThreads), lds, (hipStream_t)stream, p, (uint32_t)rev_off, bytes, off, nitems, trim, match_start, match_end);
-    return (int)hipGetLastError();
+    return launch_item_lanes<search_extents_kernel<FwdEngine, RevEngine>>(lds, nitems, kItemLanesMaxBlocks, stream, p, (uint32_t)rev_off, bytes, off, nitems, trim,
+                                                                          match_start, match_end);
 }
 
 }  // namespace
@@ -115,11 +96,8 @@ int launch_search_extents(const SearchItemsDevice &p, const uint8_t *bytes, cons
 int search_extents_dfa(const SearchItemsDevice &p, bool in_global, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
                        uint32_t *match_start, uint32_t *match_end, void *stream) {
     if (!nitems) return 0;
-    for (const DfaDevice *t : {&p.fwd, &p.rev})
-        if (!t->nstates || !t->next || !t->cls || !t->acc) return (int)hipErrorInvalidValue;
-    // both tables in LDS, one behind the other, while together they fit the budget; else - and for a regex that asked for the global
-    // form - both stay in HBM/L2 (their class maps in LDS)
-    if (in_global || PlainDfaEngine::lds_bytes(p.fwd) + PlainDfaEngine::lds_bytes(p.rev) > kPlainDfaLdsBudget)
+    if (!plain_table_ok(p.fwd) || !plain_table_ok(p.rev)) return (int)hipErrorInvalidValue;
+    if (!two_tables_in_lds(p.fwd, p.rev, in_global))
         return launch_search_extents<PlainDfaGlobalEngine, PlainDfaGlobalEngine>(p, bytes, off, nitems, trim, match_start, match_end, stream);
     return launch_search_extents<PlainDfaEngine, PlainDfaEngine>(p, bytes, off, nitems, trim, match_start, match_end, stream);
 }

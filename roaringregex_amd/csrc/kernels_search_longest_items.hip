@@ -1,27 +1,21 @@
 // kernels_search_longest_items.hip — "where is the LEFTMOST-LONGEST match of every item" (rrx_search_longest_extents /
 // rrx_search_longest_items): a lane per item on the starts table and the anchored table (lower.hpp: search_longest_dfas),
-// search_extents_kernel's grid shape and walks.  '\n' is a byte like any other.
-#include "table_engines.hpp"
+// search_extents_kernel's grid shape.  '\n' is a byte like any other.
+#include "item_lanes.hpp"
 
 namespace rrx {
 namespace dev {
 namespace {
 
-constexpr uint32_t kNoMatch = 0xffffffffu;
-constexpr size_t kMaxItemEnd = 0xfffffffeu;              // offsets are 32-bit and ~0u says "none": an item is searched as if it ended here
-constexpr size_t kSearchLongestMaxBlocks = 1024;         // workgroups per launch: beyond 2^20 items the grid strides
-
-// One lane per item in a grid-stride loop: a pass gives every wave 64 CONSECUTIVE items, so the two result stores of a wave are
-// contiguous 256-byte rows.  Two phases per pass, each run by all lanes of the wave before the next begins:
+// One lane per item, a pass of the grid-stride loop per 64 consecutive items (item_lanes.hpp: the loop, the item's span, the
+// walks).  Two phases per pass, each run by all lanes of the wave before the next begins:
 //  * backward on starts ("any bytes, then the pattern right to left": never dies, so the WHOLE item is read - there is no early
-//    exit) from the item's last byte down to its first - a tail down to 16-byte alignment, aligned 16-byte loads consumed high byte
-//    first, a head.  Accepting after the byte at offset s: some match starts at s; `start` is the last such s seen, i.e. the
-//    smallest.  No state ever accepts: no match.  Skipped where `nullable` (launch-uniform): start = 0.
-//  * forward on anchored (the pattern's own DFA) from the byte at `start` - a head up to 16-byte alignment, 16 bytes per load, a
-//    tail - to the item's end or to row 0, which is dead and absorbing (pack_search_longest checks it).  Accepting after the byte
-//    at offset p: item[start, p + 1) is accepted; `end` is the last such p + 1 seen, i.e. the largest.  A hit of the first phase
-//    guarantees one (the CPU replay test asserts it); a nullable pattern begins with end = start = 0.
-// No byte outside the item is ever read: a wide load is used only where all its 16 bytes lie inside [item start, item end).
+//    exit) from the item's last byte down to its first.  Accepting after the byte at offset s: some match starts at s; `start` is
+//    the last such s seen, i.e. the smallest.  No state ever accepts: no match.  Skipped where `nullable` (launch-uniform): start = 0.
+//  * forward on anchored (the pattern's own DFA) from the byte at `start` to the item's end or to row 0, which is dead and absorbing
+//    (pack_search_longest checks it).  Accepting after the byte at offset p: item[start, p + 1) is accepted; `end` is the last such
+//    p + 1 seen, i.e. the largest.  A hit of the first phase guarantees one (the CPU replay test asserts it); a nullable pattern
+//    begins with end = start = 0.
 // Alignment is that of the ADDRESS (d_bytes itself may sit anywhere).  NUL and bytes >= 0x80 go through the tables' own byte ->
 // class maps like every other byte.
 // (8 waves per SIMD asked for: the backward loop has no exit inside its 16 bytes, and without the bound the compiler spreads the
@@ -37,16 +31,11 @@ __global__ __launch_bounds__(kThreads, 8) void search_longest_extents_kernel(Sea
     starts.load(prog.starts, smem);
     anchored.load(prog.anchored, smem + anchored_lds_off);
     __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    const size_t per_pass = (size_t)gridDim.x * kThreads;
     const size_t skew = reinterpret_cast<uintptr_t>(bytes) & 15;      // (p + skew) & 15 == 0: bytes + p is 16-byte aligned
-    for (size_t first = (size_t)blockIdx.x * kThreads + (threadIdx.x - lane); first < nitems; first += per_pass) {
+    for_each_wave_pass(nitems, [&](size_t first, uint32_t lane) {
         const size_t i = first + lane;
-        if (i >= nitems) continue;
-        const size_t b = off[i];
-        size_t e = off[i + 1];
-        e = e - b >= trim ? e - trim : b;
-        if (e - b > kMaxItemEnd) e = b + kMaxItemEnd;
+        if (i >= nitems) return;
+        const auto [b, e] = item_span(off, i, trim, kMaxItemOffset);
         // ---- backward over the whole item: the smallest start
         size_t start = b;
         bool hit = nullable != 0;
@@ -93,24 +82,15 @@ __global__ __launch_bounds__(kThreads, 8) void search_longest_extents_kernel(Sea
         }
         match_start[i] = s_out;
         match_end[i] = e_out;
-    }
+    });
 }
 
 template <class StartsEngine, class AnchoredEngine>
 int launch_search_longest(const SearchLongestDevice &p, bool nullable, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
                           uint32_t *match_start, uint32_t *match_end, void *stream) {
-    auto k = search_longest_extents_kernel<StartsEngine, AnchoredEngine>;
     const size_t anchored_off = (StartsEngine::lds_bytes(p.starts) + 15) & ~(size_t)15, lds = anchored_off + AnchoredEngine::lds_bytes(p.anchored);
-    static LdsAttr attr;
-    hipError_t e = ensure_dynamic_lds(attr, reinterpret_cast<const void *>(k), lds);
-    if (e != hipSuccess) return (int)e;
-    // at most 1024 workgroups (two generations on the 256 CUs at two workgroups each): a workgroup copies its tables once and
-    // strides over the batch
-    size_t blocks = (nitems + kThreads - 1) / kThreads;
-    if (blocks > kSearchLongestMaxBlocks) blocks = kSearchLongestMaxBlocks;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(kThreads), lds, (hipStream_t)stream, p, (uint32_t)anchored_off, nullable ? 1u : 0u, bytes, off, nitems,
-                       trim, match_start, match_end);
-    return (int)hipGetLastError();
+    return launch_item_lanes<search_longest_extents_kernel<StartsEngine, AnchoredEngine>>(lds, nitems, kItemLanesMaxBlocks, stream, p, (uint32_t)anchored_off,
+                                                                                          nullable ? 1u : 0u, bytes, off, nitems, trim, match_start, match_end);
 }
 
 }  // namespace
@@ -118,11 +98,8 @@ int launch_search_longest(const SearchLongestDevice &p, bool nullable, const uin
 int search_longest_extents_dfa(const SearchLongestDevice &p, bool in_global, bool nullable, const uint8_t *bytes, const uint64_t *off, size_t nitems,
                                uint32_t trim, uint32_t *match_start, uint32_t *match_end, void *stream) {
     if (!nitems) return 0;
-    for (const DfaDevice *t : {&p.starts, &p.anchored})
-        if (!t->nstates || !t->next || !t->cls || !t->acc) return (int)hipErrorInvalidValue;
-    // both tables in LDS, one behind the other, while together they fit the budget; else - and for a regex that asked for the global
-    // form - both stay in HBM/L2 (their class maps in LDS)
-    if (in_global || PlainDfaEngine::lds_bytes(p.starts) + PlainDfaEngine::lds_bytes(p.anchored) > kPlainDfaLdsBudget)
+    if (!plain_table_ok(p.starts) || !plain_table_ok(p.anchored)) return (int)hipErrorInvalidValue;
+    if (!two_tables_in_lds(p.starts, p.anchored, in_global))
         return launch_search_longest<PlainDfaGlobalEngine, PlainDfaGlobalEngine>(p, nullable, bytes, off, nitems, trim, match_start, match_end, stream);
     return launch_search_longest<PlainDfaEngine, PlainDfaEngine>(p, nullable, bytes, off, nitems, trim, match_start, match_end, stream);
 }

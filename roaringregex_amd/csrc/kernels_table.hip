@@ -1,7 +1,7 @@
 // kernels_table.hip — the batch match path of the table engines: the stride-2 stripe kernels, the launchers of the byte-stride
 // ones, the stream compaction of the one-shot entry and the two-bit split of the sampled-table engine.  Engines:
 // table_engines.hpp; shared device code: kernels_common.hpp.
-#include "table_engines.hpp"
+#include "item_lanes.hpp"
 
 namespace rrx {
 namespace dev {

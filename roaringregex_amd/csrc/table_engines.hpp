@@ -1,6 +1,6 @@
 // table_engines.hpp — the table engine structs: the byte-stride line and plain DFA engines (tables in LDS or in HBM/L2)
-// and the stride-2 engine Dfa2.  No kernels and no launchers.  Included by kernels_table.hip, kernels_items.hip,
-// kernels_contains_items.hip, kernels_search_items.hip, kernels_search_all_items.hip and kernels_search_longest_items.hip only.
+// and the stride-2 engine Dfa2.  No kernels and no launchers.  Included by kernels_items.hip and, through item_lanes.hpp (what the
+// lane-per-item kernels share), by the units that hold such a kernel.
 #pragma once
 #include "kernels_common.hpp"
 

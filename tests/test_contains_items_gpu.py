@@ -330,3 +330,55 @@ def test_degenerate_inputs():
     assert rr._L.rrx_contains_extents(None, 0, None, None, 0, 0, None, None) == 2
     assert rr._L.rrx_contains_extents(r._h, 0, dev.data_ptr(), doff.data_ptr(), 5, 0, None, None) == 2     # RRX_ERR_ARG: no bitmap for a batch with items
     assert rr._L.rrx_contains_items(r._h, None, None, None) == 2
+
+
+MATCH_GLOBAL = "[ab]*a[ab]{12}c"                    # 8194 states of 4 classes: its plain match table passes 64 KiB and stays in HBM/L2
+
+
+def test_every_alignment_of_item_start_on_the_lane_kernels():
+    """match_extents_kernel and contains_extents_kernel: items of every length 0 ... 40, each placed at all 16 alignments of its first
+    byte, trim 1 - on a 16-byte aligned buffer and on the same buffer sliced by one byte (both kernels align on the OFFSET, so on the
+    slice every wide load is an unaligned one), tables in LDS and in HBM/L2.  One round of the 41 lengths takes 861 bytes, 13 mod 16:
+    16 rounds carry every length through the 16 residues.  656 items: far below the stripe-wise thresholds, a lane per item.
+    Expected: the oracle's whole-string acceptance (match) and its brute-force search (contains)."""
+    from contains_cases import brute_force
+    from pyoracle import OracleRegex
+    from test_search_items_lowering import plain_table_bytes
+    rng = random.Random(31)
+    small = ("ab+c", "abcz", 3, lambda n: b"a" + b"b" * (n - 2) + b"c")
+    large = (MATCH_GLOBAL, "abc", 14, lambda n: b"b" * (n - 14) + b"a" + b"b" * 12 + b"c")
+    # (pattern ..., engine, match on the lane kernel's LDS / global form, contains on its LDS / global form or None)
+    for (p, alphabet, shortest, witness), engine, match_form, contains_form in ((small, rr.ENGINE_AUTO, "lds", "lds"), (small, rr.ENGINE_DFA_GLOBAL, "lds", "global"),
+                                                                                (large, rr.ENGINE_DFA_GLOBAL, "global", None)):
+        items = []
+        for _ in range(16):
+            for n in range(41):
+                it = "".join(rng.choice(alphabet) for _ in range(n)).encode()
+                k = rng.randrange(4)
+                if k == 0 and n >= shortest:
+                    it = witness(n)                                                         # the whole item matches
+                elif k == 1 and n >= shortest:
+                    at = rng.randrange(n - shortest + 1)
+                    it = it[:at] + witness(shortest) + it[at + shortest:]                  # a match somewhere inside
+                items.append(it)
+        o = OracleRegex(p)
+        want_match = np.array([1 if o.accepts(it) else 0 for it in items], dtype=np.uint8)
+        assert len(items) == 656 and 50 < want_match.sum() < 400
+        text, offs = pack(items, 1, rng)
+        assert len({(int(at) % 16, len(it)) for at, it in zip(offs[:-1], items)}) == 16 * 41
+        dev, doff = to_dev(text, offs)
+        sliced = torch.cat([torch.zeros(1, dtype=torch.uint8, device="cuda"), dev])[1:]
+        assert dev.data_ptr() % 16 == 0 and sliced.data_ptr() % 16 == 1
+        r = rr.RRegex(p, engine)
+        assert r.engine_name.startswith("dfa"), r.engine_name                               # (match_extents on the plain table)
+        assert (plain_table_bytes(r.program(rr.ENGINE_DFA)) > 65536) == (match_form == "global")
+        for buf, what in ((dev, "aligned"), (sliced, "sliced by one byte")):
+            got = r.match_extents(buf, doff, trim=1).cpu().numpy()
+            bad = np.nonzero(got != want_match)[0]
+            assert bad.size == 0, ("match", p, match_form, what, int(bad[0]), items[bad[0]], int(offs[bad[0]]) % 16)
+        if contains_form:
+            want_contains = brute_force(p, b"\n".join(items) + b"\n")
+            assert want_match.sum() < want_contains.sum() < len(items)
+            assert plain_table_bytes(r.program(rr.PROGRAM_CONTAINS_DFA)) <= 65536           # (global only because the regex asked for it)
+            for buf, what in ((dev, "aligned"), (sliced, "sliced by one byte")):
+                check_bits(r, r.contains_extents_bits(buf, doff, trim=1), len(items), want_contains, ("contains", p, contains_form, what))

@@ -1,0 +1,119 @@
+"""The rate of ONE lane-per-item entry in this tree beside the SAME entry of the parent commit - the probe for a change that is
+meant to leave these kernels as fast as they were (item_lanes.hpp).  On the URL, email and keyword-log texts of bench.py viewed as
+items (offsets = the line starts, trim 1: the '\\n' is the separator):
+
+  match           rrx_match_extents       in slices of 65535 items, below the stripe-wise threshold: every slice runs a lane per item
+  contains        rrx_contains_extents    in the same slices
+  search          rrx_search_extents      on the whole batch
+  search_all      rrx_search_all_extents_count + _fill on the whole batch
+  search_longest  rrx_search_longest_extents on the whole batch
+
+The parent's side runs from a second checkout under .oldtree/ (git archive <commit> | tar -x -C .oldtree; build there): per text
+four children - parent, tree, parent, tree -, a fresh process each; device events around every launch (every sweep of slices),
+median and spread of `--launches` launches (at least twelve) after warm-up.  A child that fails ends the run: nothing more is
+started on the device.  The last line per text gives the margin - what the parent differs from itself: the larger of the distance
+between its two medians and its own spread - and whether each of the tree's medians is within it of the slower parent median.
+
+    python tools/probe/item_lanes_rate.py --entry search [--old .oldtree] [--launches 15] [--scale 1.0]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+CONFIGS = (("url", "U2", 1 << 30), ("email", "EMAIL", 1 << 30), ("kwlog", "K1000C", 1 << 30))
+ENTRIES = ("match", "contains", "search", "search_all", "search_longest")
+SLICE = 65535                                  # items per call of match / contains: one below kItemsStripesMin
+
+
+def child(tree, entry, kind, pkey, nbytes, launches):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))    # synth and bench.patterns(): the same text and patterns for both sides
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from bench import patterns
+    import synth
+    sys.path.remove(ROOT)
+    sys.path.insert(0, tree)
+    import roaringregex_amd as rr
+    assert os.path.dirname(os.path.abspath(rr.__file__)).startswith(os.path.abspath(tree)), rr.__file__
+    r = rr.RRegex(patterns()[pkey])
+    host = synth.corpus(kind, 1, nbytes, threads=min(len(os.sched_getaffinity(0)), 16))
+    host = host[:int(np.nonzero(host == 10)[0][-1]) + 1]
+    dev = torch.from_numpy(host).cuda()
+    off = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.nonzero(dev == 10).flatten() + 1]).contiguous()
+    n = off.numel() - 1
+
+    if entry in ("match", "contains"):
+        slices = [off[k:k + SLICE + 1] for k in range(0, n, SLICE)]
+        if entry == "match":
+            out = torch.empty(SLICE, dtype=torch.uint8, device="cuda")
+            one = lambda s: r.match_extents(dev, s, trim=1, out=out)
+            found = sum(int(one(s).sum()) for s in slices)
+        else:
+            out = torch.empty((SLICE + 31) // 32, dtype=torch.int32, device="cuda")
+            one = lambda s: r.contains_extents_bits(dev, s, trim=1, out=out)
+            found = sum(rr.bitmap_count(one(s), s.numel() - 1) for s in slices)
+
+        def call():
+            for s in slices:
+                one(s)
+    elif entry == "search_all":
+        call = lambda: r.search_all_extents(dev, off, trim=1)
+        found = int(call()[1].numel())
+    else:
+        call = (lambda: r.search_extents(dev, off, trim=1)) if entry == "search" else (lambda: r.search_longest_extents(dev, off, trim=1))
+        found = int((call()[1] >= 0).sum())
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(launches):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); call(); b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    ms.sort()
+    med = statistics.median(ms)
+    print(json.dumps({"config": kind, "tree": os.path.relpath(tree, ROOT), "entry": entry, "bytes": int(dev.numel()), "items": n, "found": found,
+                      "ms": round(med, 4), "TB/s": round(dev.numel() / med / 1e9, 3), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4),
+                      "spread": round((ms[-1] - ms[0]) / med, 4)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--entry", choices=ENTRIES, required=True)
+    ap.add_argument("--old", default=os.path.join(ROOT, ".oldtree"))
+    ap.add_argument("--launches", type=int, default=15)
+    ap.add_argument("--scale", type=float, default=1.0, help="corpus sizes times this (a quick run)")
+    ap.add_argument("--child", nargs=4, default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        tree, kind, pkey, nbytes = a.child
+        return child(tree, a.entry, kind, pkey, int(nbytes), max(a.launches, 12))
+    assert os.path.exists(os.path.join(a.old, "roaringregex_amd", "librrx.so")), "build the parent commit under %s first" % a.old
+    for kind, pkey, nbytes in CONFIGS:
+        n = int(nbytes * a.scale) // 4096 * 4096
+        runs = {"parent": [], "tree": []}
+        for side, tree in (("parent", a.old), ("tree", ROOT)) * 2:
+            env = dict(os.environ)
+            env.pop("RRX_LIB", None)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", a.entry, "--launches", str(a.launches), "--child", tree, kind, pkey, str(n)],
+                               env=env, timeout=600, stdout=subprocess.PIPE, text=True)
+            sys.stdout.write(p.stdout)
+            sys.stdout.flush()
+            if p.returncode:                   # a fault or a time limit: nothing more is started on the device
+                raise SystemExit("child failed with %d: %s %s %s" % (p.returncode, tree, a.entry, kind))
+            runs[side].append(json.loads(p.stdout.strip().splitlines()[-1]))
+        assert len({x["found"] for x in runs["parent"] + runs["tree"]}) == 1, "the two trees do not find the same"
+        slower = max(x["ms"] for x in runs["parent"])
+        margin = max(abs(runs["parent"][0]["ms"] - runs["parent"][1]["ms"]), max(x["spread"] * x["ms"] for x in runs["parent"]))
+        print(json.dumps({"config": kind, "entry": a.entry, "parent_ms": [x["ms"] for x in runs["parent"]], "tree_ms": [x["ms"] for x in runs["tree"]],
+                          "margin_ms": round(margin, 4), "within_margin": all(x["ms"] <= slower + margin for x in runs["tree"])}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
