@@ -26,11 +26,14 @@ class NfaReplay:
         else:
             self.X = [big(w[o + b * W:o + (b + 1) * W]) for b in range(self.nbits)]
         self.mask = (1 << (32 * W)) - 1
+        # an empty set stays empty: (0 + CGRP) & CTGT, the one term of a step that needs no live position, yields nothing, and the 1 that
+        # line mode injects into position 0 survives no B row
+        self.empty_stays_empty = (self.cgrp & self.ctgt) == 0 and not any(b & 1 for b in self.B)
 
     def accepts(self, s):
         S = self.init
         for c in s:
-            if c == 0 or c >= 0x80:
+            if c == 0 or c >= 0x80 or (not S and self.empty_stays_empty):
                 return False
             t = ((S << 1) & self.mask & self.chain) | (S & self.self_)
             t |= ((S & self.cgrp) + self.cgrp) & self.ctgt
@@ -54,6 +57,8 @@ class NfaReplay:
         for c in seq:
             if c == 10:
                 out.append(1 if S & self.fin else 0)
+            elif not S and self.empty_stays_empty:            # (until the '\n': position 0 is in no other B row)
+                continue
             t = ((S << 1) & self.mask) | 1 | (S & self.self_)
             t |= ((S & self.cgrp) + self.cgrp) & self.ctgt
             e = S & self.excm

@@ -956,8 +956,10 @@ def test_small_automata_forced_onto_the_cooperative_engines():
 
 
 def test_nfa_lane_engine_sixteen_words():
-    """LineNfaEngine<16, ...> (385-512 positions in one lane's registers), all four builds: bare chain, + self loops and
-    add-carry groups, + exception rows - never launched before round 3.  Batch, one-shot, extents, facade vs the oracle."""
+    """LineNfaEngine<16, ...> (385-512 positions in one lane's registers), three of its four builds: bare chain (a{1,450}), add-carry
+    groups (the two patterns with a star: their programs have self loops AND carry groups), exception rows - never launched before
+    round 3.  Batch, one-shot, extents, facade vs the oracle.  The fourth build, self loops without carry groups, and every other
+    width and build: test_nfa_widths_gpu.py."""
     cases = [("a{1,450}", (0, 1, 2, 449, 450, 451, 452, 700), "a"),
              ("(a|b)*a(a|b){400}", (0, 1, 400, 401, 402, 403, 500, 900, 1700), "ab"),
              ("(ab|ba){1,120}", (0, 2, 3, 100, 238, 240, 242, 480), "ab"),
