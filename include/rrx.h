@@ -362,6 +362,58 @@ int rrx_search_all_items_fill(const rrx_regex *re, const rrx_items *items, const
 int rrx_search_all_items(const rrx_regex *re, const rrx_items *items, uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap,
                          size_t *total, void *stream);
 
+/* EVERY LEFTMOST-LONGEST match of every item, left to right: what regexp_count, regexp_extract_all, regexp_replace and split mean
+ * in every SQL engine, in POSIX and in RE2's longest-match mode ([0-9]+ on "a1 22 333": [1,2) [3,5) [6,9), where
+ * rrx_search_all_extents reports six one-digit matches).  Item i is d_bytes[d_off[i] .. d_off[i+1] - trim), as in
+ * rrx_search_longest_extents.  Match k of an item is the leftmost-longest match of item[p_k:] - the smallest start s >= p_k such
+ * that some item[s, e) is accepted as a whole string, then the largest such e; p_0 = 0, p_{k+1} = the end of match k, one byte
+ * further after an empty match; the search goes on while p_k <= length and stops at the first p_k without a match.  Offsets are
+ * relative to the start of the item.  '\n', NUL and bytes >= 0x80 are ordinary text, as in rrx_search_longest_extents.  A pattern
+ * that accepts the empty string matches at every position that no non-empty match covers: a* on "baab" gives [0,0) [1,3) [3,3)
+ * [4,4) (Python's findall).  An empty-language pattern has no matches: the counts are 0 (a fill: no table, no text pass).  LONG
+ * ITEMS: an item is searched as if it ended at its offset 0xFFFFFFFE.
+ * Two phases per item, a lane per item (kernels_search_all_longest_items.hip) on the two tables of rrx_search_longest_extents,
+ * placed as there: backwards on RRX_PROGRAM_SEARCH_STARTS over the WHOLE item, recording a MARK bit for every offset at which some
+ * match starts; then forwards - the next mark at or behind p, RRX_PROGRAM_SEARCH_ANCHORED from there to the item's end or the
+ * table's dead row, the last accepting position is the end, p = that end, and again.  The marks make this linear in the item.
+ * The marks live in d_marks, a buffer of the caller's: rrx_search_all_longest_marks_words(extent_bytes, nitems) 32-bit words
+ * (extent_bytes / 32 + nitems + 1) for any extent_bytes >= d_off[nitems] - d_off[0] - the size of the byte buffer will do.  Host
+ * only, pure.  The bit of byte g of item i is bit (g - d_off[0]) & 31 of word ((g - d_off[0]) >> 5) + i: no two items share a word,
+ * nothing has to be cleared, words outside the items' ranges are left as they were.
+ * Two passes: _count writes the marks and d_count[i] = matches of item i - every one of the nitems count words, whatever it held;
+ * the caller turns the counts into the exclusive prefix d_first[i] (u64); _fill, given the marks that _count left for the same
+ * regex, batch and trim, writes match k of item i to slot d_first[i] + k of d_start / d_end - exactly the slots d_first[i] ..
+ * d_first[i] + count[i] and nothing else.  Both are FULLY asynchronous on `stream` and can be captured into a graph once the
+ * tables are uploaded: no read-back, no scratch of their own, no event, no extent bound.  _count reads an item about twice and
+ * writes an eighth of it; _fill reads the marks and the matched bytes.  A d_marks shorter than
+ * rrx_search_all_longest_marks_words(extent, nitems) is the caller's error, as a short d_start is; a marks_words below nitems + 1
+ * is rejected (RRX_ERR_ARG: that bound needs no extent).  A pattern that accepts the empty string never touches d_marks.
+ * KNOWN COST of such a pattern: the anchored walk restarts at every offset that no non-empty match covers, and each restart
+ * runs to the dead row - (a*b)? on a long run of 'a' without a 'b' is quadratic in the run.
+ * The one-call form mirrors rrx_search_all_extents: d_first has nitems + 1 entries, d_first[nitems] = *total; the match arrays
+ * hold `cap` entries, matches in slots >= cap are counted, not written - if *total > cap call again with arrays of *total entries
+ * (d_first is complete either way).  Synchronous (returns *total).  It reads d_off[0] and d_off[nitems] back to size the marks,
+ * then runs _count, a device scan and _fill, the counts, the marks and the scan's scratch in device memory the call allocates and
+ * frees.  The scan carries 30 bits per count.  nitems == 0: d_first[0] = 0, *total = 0.
+ * rrx_search_all_longest_items* use the handle's bytes, offsets, item count, trim and device only (not its index).
+ * RRX_ERR_ARG for null arguments, checked before any device call (d_marks is required when nitems > 0; d_start / d_end may be
+ * null where nothing can be written: the one-call form with cap == 0 or nitems == 0); RRX_ERR_UNSUPPORTED exactly where
+ * rrx_search_longest_extents returns it, for an empty batch too - nothing is written then.                                       */
+size_t rrx_search_all_longest_marks_words(size_t extent_bytes, size_t nitems);
+int rrx_search_all_longest_extents_count(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                         uint32_t *d_marks, size_t marks_words, uint32_t *d_count, void *stream);
+int rrx_search_all_longest_extents_fill(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                        const uint32_t *d_marks, size_t marks_words, const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end,
+                                        void *stream);
+int rrx_search_all_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                   uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap, size_t *total, void *stream);
+int rrx_search_all_longest_items_count(const rrx_regex *re, const rrx_items *items, uint32_t *d_marks, size_t marks_words, uint32_t *d_count,
+                                       void *stream);
+int rrx_search_all_longest_items_fill(const rrx_regex *re, const rrx_items *items, const uint32_t *d_marks, size_t marks_words,
+                                      const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, void *stream);
+int rrx_search_all_longest_items(const rrx_regex *re, const rrx_items *items, uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap,
+                                 size_t *total, void *stream);
+
 /* ONE device-resident string of any length (regex.h:156-159: operator++ consumes the whole string; '\n' and every
  * other byte are ordinary, a NUL or a byte >= 0x80 rejects).  d_accept[0] = 1 iff accepted.  Strings of 32 KiB and
  * more are split into chunks that are stepped in parallel from every table state (automata with <= 254 table

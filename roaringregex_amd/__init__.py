@@ -50,6 +50,9 @@ ABI_SYMBOLS = (
     "rrx_search_all_extents_count", "rrx_search_all_extents_fill", "rrx_search_all_extents",
     "rrx_search_all_items_count", "rrx_search_all_items_fill", "rrx_search_all_items",
     "rrx_search_longest_extents", "rrx_search_longest_items",
+    "rrx_search_all_longest_marks_words",
+    "rrx_search_all_longest_extents_count", "rrx_search_all_longest_extents_fill", "rrx_search_all_longest_extents",
+    "rrx_search_all_longest_items_count", "rrx_search_all_longest_items_fill", "rrx_search_all_longest_items",
 )
 
 
@@ -135,6 +138,13 @@ def _load():
         "rrx_search_all_items": (i32, [vp, vp, vp, vp, vp, sz, C.POINTER(sz), vp]),
         "rrx_search_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, vp]),
         "rrx_search_longest_items": (i32, [vp, vp, vp, vp, vp]),
+        "rrx_search_all_longest_marks_words": (sz, [sz, sz]),
+        "rrx_search_all_longest_extents_count": (i32, [vp, i32, vp, vp, sz, u32, vp, sz, vp, vp]),
+        "rrx_search_all_longest_extents_fill": (i32, [vp, i32, vp, vp, sz, u32, vp, sz, vp, vp, vp, vp]),
+        "rrx_search_all_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, vp, sz, C.POINTER(sz), vp]),
+        "rrx_search_all_longest_items_count": (i32, [vp, vp, vp, sz, vp, vp]),
+        "rrx_search_all_longest_items_fill": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
+        "rrx_search_all_longest_items": (i32, [vp, vp, vp, vp, vp, sz, C.POINTER(sz), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -659,6 +669,61 @@ class RRegex:
                                                  C.c_void_p(offsets.data_ptr()), n, trim, C.c_void_p(start.data_ptr() if n else 0),
                                                  C.c_void_p(end.data_ptr() if n else 0), _stream_ptr(stream)))
         return start, end
+
+    @staticmethod
+    def _search_all_longest_marks(data, n):
+        """The marks buffer of the two-pass leftmost-longest entries for a batch of n items inside `data`: int32, sized from
+        data.numel() (rrx_search_all_longest_marks_words), uninitialised - the count pass stores every word that the fill pass reads."""
+        import torch
+        words = _L.rrx_search_all_longest_marks_words(data.numel(), n)
+        return torch.empty(words, dtype=torch.int32, device=data.device), words
+
+    def search_all_longest_items(self, items, stream=None):
+        """ALL LEFTMOST-LONGEST matches of every item of an indexed batch (Items), left to right (rrx_search_all_longest_items_count /
+        _fill) -> (count[n] int32, first[n] int64, start[total] int32, end[total] int32), shaped as search_all_items returns them.
+        Match k + 1 is the leftmost-longest match of the rest of the item behind match k (one byte further after an empty match):
+        [0-9]+ on b"a1 22 333" gives [1,2) [3,5) [6,9).  '\\n', NUL and bytes >= 0x80 are ordinary text inside an item."""
+        with _on(items.device, stream):
+            s = _stream_ptr(stream)
+            marks, words = self._search_all_longest_marks(items.data, items.num_items)
+            m = C.c_void_p(marks.data_ptr())
+            return self._search_all_two_pass(items.data.device, items.num_items,
+                                             lambda c: _L.rrx_search_all_longest_items_count(self._h, items._h, m, words, c, s),
+                                             lambda f, st, en: _L.rrx_search_all_longest_items_fill(self._h, items._h, m, words, f, st, en, s))
+
+    def search_all_longest_extents(self, data, offsets, trim=0, stream=None):
+        """The same for a batch nobody has indexed (rrx_search_all_longest_extents_count / _fill): item i = data[offsets[i] : offsets[i+1] - trim]."""
+        import torch
+        n = offsets.numel() - 1
+        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+        d, b, o = data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0), C.c_void_p(offsets.data_ptr())
+        with _on(d, stream):
+            s = _stream_ptr(stream)
+            marks, words = self._search_all_longest_marks(data, n)
+            m = C.c_void_p(marks.data_ptr())
+            return self._search_all_two_pass(data.device, n,
+                                             lambda c: _L.rrx_search_all_longest_extents_count(self._h, d, b, o, n, trim, m, words, c, s),
+                                             lambda f, st, en: _L.rrx_search_all_longest_extents_fill(self._h, d, b, o, n, trim, m, words, f, st, en, s))
+
+    def search_all_longest_items_fused(self, items, cap=None, stream=None):
+        """The same result through the one-call entry (rrx_search_all_longest_items) -> (first[n + 1] int64 CSR offsets, start[total]
+        int32, end[total] int32).  cap: entries to provide for at first (default: two per item); the call is repeated with the exact
+        size if there are more."""
+        with _on(items.device, stream):
+            s = _stream_ptr(stream)
+            return self._search_all_one_call(items.data.device, items.num_items, cap,
+                                             lambda f, st, en, cp, tot: _L.rrx_search_all_longest_items(self._h, items._h, f, st, en, cp, tot, s))
+
+    def search_all_longest_extents_fused(self, data, offsets, trim=0, cap=None, stream=None):
+        """The one-call entry for a batch nobody has indexed (rrx_search_all_longest_extents) -> (first[n + 1], start, end)."""
+        import torch
+        n = offsets.numel() - 1
+        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+        d, b, o = data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0), C.c_void_p(offsets.data_ptr())
+        with _on(d, stream):
+            s = _stream_ptr(stream)
+            return self._search_all_one_call(data.device, n, cap,
+                                             lambda f, st, en, cp, tot: _L.rrx_search_all_longest_extents(self._h, d, b, o, n, trim, f, st, en, cp, tot, s))
 
     def match_string(self, data, stream=None):
         """ONE device-resident string of any length (regex.h:156-159); '\n' is an ordinary character.  -> bool"""

@@ -301,6 +301,21 @@ struct SearchLongestDevice {
 int search_longest_extents_dfa(const SearchLongestDevice &p, bool in_global, bool nullable, const uint8_t *bytes, const uint64_t *off, size_t nitems,
                                uint32_t trim, uint32_t *match_start, uint32_t *match_end, void *stream);
 
+// ---- all leftmost-longest matches per explicit item, a lane per item: kernels_search_all_longest_items.hip
+// The matches of item i are those of search_longest_extents_dfa applied again and again to the rest of the item behind the previous
+// match (one byte further after an empty match).  first == nullptr (COUNT): the backward walk on starts leaves a MARK bit in `marks`
+// for every offset at which some match starts - the bit of byte g of item i is bit (g - off[0]) & 31 of word ((g - off[0]) >> 5) + i,
+// every word of an item's range stored, no other - and the forward phase on the marks counts: count[i], every one of the nitems
+// words written with a plain store.  Otherwise (`first`: the caller's exclusive prefix of the counts) the forward phase alone, on
+// the marks a COUNT launch on the same batch left: match k of item i goes to slot first[i] + k of match_start / match_end, relative
+// to the item; slots >= cap are not written, nor any other slot.  marks holds marks_words words, at least
+// search_all_longest_marks_words(extent, nitems) for extent >= off[nitems] - off[0]; words at or beyond marks_words are not touched.
+// nullable: every offset 0 .. length is a start, marks is not touched.  Placement and long items as search_longest_extents_dfa.
+size_t search_all_longest_marks_words(size_t extent_bytes, size_t nitems);
+int search_all_longest_extents_dfa(const SearchLongestDevice &p, bool in_global, bool nullable, const uint8_t *bytes, const uint64_t *off, size_t nitems,
+                                   uint32_t trim, uint32_t *marks, size_t marks_words, uint32_t *count, const uint64_t *first, uint32_t *match_start,
+                                   uint32_t *match_end, size_t cap, void *stream);
+
 // ---- one long string on the plain DFA: kernels_long.hip
 // One long string (regex.h:156-159 consumes it byte by byte): the string is cut into chunks, every chunk is stepped
 // from EVERY table state at once (lane = (chunk, start state); the lanes of a chunk read the same text), which yields

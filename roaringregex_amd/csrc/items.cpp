@@ -1,5 +1,5 @@
-// items.cpp — explicit items (an offsets array: rrx_match_extents / rrx_contains_extents / rrx_search_extents / rrx_search_all_extents*,
-// and rrx_items, the batch indexed once)
+// items.cpp — explicit items (an offsets array: rrx_match_extents / rrx_contains_extents / rrx_search_extents / rrx_search_all_extents* /
+// rrx_search_longest_extents / rrx_search_all_longest_extents*, and rrx_items, the batch indexed once)
 // and single strings (rrx_match_string, rrx_match_cstr).
 #include <algorithm>
 #include <cstring>
@@ -333,6 +333,102 @@ int rrx_search_all_items(const rrx_regex *re, const rrx_items *it, uint64_t *d_f
                          void *stream) {
     if (!re || !it || !total || !d_first || (it->nitems && cap && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
     return search_all_one_call(re, batch_of(it), d_first, d_start, d_end, cap, total, stream);
+}
+
+// EVERY LEFTMOST-LONGEST match of every item: search_longest_lanes' tables, the search applied again to the rest of the item behind
+// each match.  d_first == nullptr: the marks and the counts; otherwise the matches into the slots behind d_first[i], those below
+// `cap`, on the marks the count pass left.  The empty language matches nowhere: the counts are a fill, there is no table and no
+// text pass.  (No tables: they do not determinise.)
+struct ItemMarks { uint32_t *words; size_t nwords; };
+static int search_all_longest_lanes(const rrx_regex *re, const ItemBatch &b, ItemMarks marks, uint32_t *d_count, const uint64_t *d_first, uint32_t *d_start,
+                                    uint32_t *d_end, size_t cap, void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
+    const dev::SearchLongestDevice *t;
+    const int rc = re->search_longest_tables(device, &t);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if (!nitems) return RRX_OK;
+    if (!t) {
+        if (!d_first) HIP_TRY(hipMemsetAsync(d_count, 0, nitems * sizeof(uint32_t), (hipStream_t)stream));
+        return RRX_OK;
+    }
+    return launched(dev::search_all_longest_extents_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, re->search_longest.nullable, bytes, off, nitems, trim,
+                                                        marks.words, marks.nwords, d_count, d_first, d_start, d_end, cap, stream),
+                    "search_all_longest_extents launch");
+}
+// The marks of a batch of nitems items take a word per item at the very least, whatever the extent: a shorter buffer cannot be meant
+static bool marks_ok(size_t nitems, const uint32_t *d_marks, size_t marks_words) { return !nitems || (d_marks && marks_words >= nitems + 1); }
+static const char *const kMarksError = "null argument, or marks_words below nitems + 1";
+// count + scan + fill in one call (search_all_one_call), the marks too in device memory of the call's own, sized from the batch's
+// real extent: off[0] and off[nitems] are read back.
+static int search_all_longest_one_call(const rrx_regex *re, const ItemBatch &b, uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap,
+                                       size_t *total, void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
+    *total = 0;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = search_all_longest_lanes(re, batch_of(device, bytes, off, 0, trim), {}, nullptr, nullptr, nullptr, nullptr, 0, stream);   // (the tables, the device)
+    if (rc) return rc;
+    if (!nitems) { HIP_TRY(hipMemsetAsync(d_first, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
+    uint64_t lo = 0, hi = 0;
+    HIP_TRY(hipMemcpyAsync(&lo, off, sizeof lo, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&hi, off + nitems, sizeof hi, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const size_t nwords = rrx_search_all_longest_marks_words(hi > lo ? (size_t)(hi - lo) : 0, nitems);
+    DeviceArray<uint32_t> d_count, d_marks;
+    DeviceArray<uint64_t> d_sums;
+    hipError_t he = d_count.alloc(device, nitems * sizeof(uint32_t));
+    if (he == hipSuccess) he = d_marks.alloc(device, nwords * sizeof(uint32_t));
+    if (he == hipSuccess) he = d_sums.alloc(device, dev::scan_scratch_words(nitems) * sizeof(uint64_t));
+    if (he != hipSuccess) return hip_fail(he, "hipMalloc(search_all_longest counts and marks)");
+    const ItemMarks marks{d_marks, nwords};
+    rc = search_all_longest_lanes(re, b, marks, d_count, nullptr, nullptr, nullptr, 0, stream);
+    if (rc) return rc;
+    const int le = dev::scan_counts(d_count, d_first, d_sums, nitems, stream);  // d_first[nitems] = total
+    if (le) return hip_fail((hipError_t)le, "search_all_longest scan launch");
+    he = hipMemsetAsync(d_first, 0, sizeof(uint64_t), st);                      // the scan marks entry 0 as a stripe start: not here
+    uint64_t tot = 0;
+    if (he == hipSuccess) he = hipMemcpyAsync(&tot, d_first + nitems, sizeof tot, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return hip_fail(he, "search_all_longest scan");
+    *total = (size_t)tot;
+    if (tot && cap) {                                                            // matches in slots >= cap are counted, not written
+        rc = search_all_longest_lanes(re, b, marks, nullptr, d_first, d_start, d_end, cap, stream);
+        if (!rc) { he = hipStreamSynchronize(st); if (he != hipSuccess) rc = hip_fail(he, "search_all_longest fill"); }
+    }
+    return rc;
+}
+size_t rrx_search_all_longest_marks_words(size_t extent_bytes, size_t nitems) { return dev::search_all_longest_marks_words(extent_bytes, nitems); }
+int rrx_search_all_longest_extents_count(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                         uint32_t *d_marks, size_t marks_words, uint32_t *d_count, void *stream) {
+    if (!re || (nitems && (!d_off || !d_count)) || !marks_ok(nitems, d_marks, marks_words)) return fail(RRX_ERR_ARG, kMarksError);
+    return search_all_longest_lanes(re, batch_of(device, d_bytes, d_off, nitems, trim), {d_marks, marks_words}, d_count, nullptr, nullptr, nullptr, 0, stream);
+}
+int rrx_search_all_longest_items_count(const rrx_regex *re, const rrx_items *it, uint32_t *d_marks, size_t marks_words, uint32_t *d_count, void *stream) {
+    if (!re || !it || (it->nitems && !d_count) || !marks_ok(it->nitems, d_marks, marks_words)) return fail(RRX_ERR_ARG, kMarksError);
+    return search_all_longest_lanes(re, batch_of(it), {d_marks, marks_words}, d_count, nullptr, nullptr, nullptr, 0, stream);
+}
+int rrx_search_all_longest_extents_fill(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                        const uint32_t *d_marks, size_t marks_words, const uint64_t *d_first, uint32_t *d_start, uint32_t *d_end,
+                                        void *stream) {
+    if (!re || (nitems && (!d_off || !d_first || !d_start || !d_end)) || !marks_ok(nitems, d_marks, marks_words)) return fail(RRX_ERR_ARG, kMarksError);
+    return search_all_longest_lanes(re, batch_of(device, d_bytes, d_off, nitems, trim), {const_cast<uint32_t *>(d_marks), marks_words}, nullptr, d_first,
+                                    d_start, d_end, ~(size_t)0, stream);       // (the fill kernel only reads the marks)
+}
+int rrx_search_all_longest_items_fill(const rrx_regex *re, const rrx_items *it, const uint32_t *d_marks, size_t marks_words, const uint64_t *d_first,
+                                      uint32_t *d_start, uint32_t *d_end, void *stream) {
+    if (!re || !it || (it->nitems && (!d_first || !d_start || !d_end)) || !marks_ok(it->nitems, d_marks, marks_words))
+        return fail(RRX_ERR_ARG, kMarksError);
+    return search_all_longest_lanes(re, batch_of(it), {const_cast<uint32_t *>(d_marks), marks_words}, nullptr, d_first, d_start, d_end, ~(size_t)0, stream);
+}
+int rrx_search_all_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                   uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap, size_t *total, void *stream) {
+    if (!re || !total || !d_first || (nitems && (!d_off || (cap && (!d_start || !d_end))))) return fail(RRX_ERR_ARG, "null argument");
+    return search_all_longest_one_call(re, batch_of(device, d_bytes, d_off, nitems, trim), d_first, d_start, d_end, cap, total, stream);
+}
+int rrx_search_all_longest_items(const rrx_regex *re, const rrx_items *it, uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap,
+                                 size_t *total, void *stream) {
+    if (!re || !it || !total || !d_first || (it->nitems && cap && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
+    return search_all_longest_one_call(re, batch_of(it), d_first, d_start, d_end, cap, total, stream);
 }
 
 // One device-resident string of any length.  Long strings take the chunk-map path when the automaton has a small
