@@ -414,6 +414,55 @@ int rrx_search_all_longest_items_fill(const rrx_regex *re, const rrx_items *item
 int rrx_search_all_longest_items(const rrx_regex *re, const rrx_items *items, uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap,
                                  size_t *total, void *stream);
 
+/* regexp_replace on a string column, WRITTEN on the device: from a column, a match list per item and a literal replacement to the
+ * new column (d_out_off[nitems + 1], d_out).  Item i is t = d_bytes[d_off[i] .. d_off[i+1] - trim), empty where trim exceeds its
+ * length.  Its matches (s_0,e_0) ... (s_{m-1},e_{m-1}) are in order, s_0 >= 0, e_k >= s_k, s_{k+1} >= e_k, e_{m-1} <= length; the
+ * output item is t[0:s_0] + R + t[e_0:s_1] + R + ... + R + t[e_{m-1}:], R the replacement: rep_len >= 0 literal bytes, no group
+ * references (the engine has no captures).  An empty match inserts R at its position (a* on "baab" with "<>": "<>b<><>b<>"), an
+ * item without matches is copied verbatim, the `trim` separator bytes are never copied: the output column has no separators.  This
+ * is Python's re.sub(p, lambda m: R, t) for the list re.finditer names.
+ * THE MATCH LIST is the shape every rrx_search_all* one-call form returns (and the two-pass forms once the caller's prefix has one
+ * more entry): d_first has nitems + 1 entries, match k of item i is slot d_first[i] + k of d_start / d_end, offsets relative to the
+ * item; d_pos[slot] belongs to the same slot (the arrays are indexed by the slot itself, d_first[0] need not be 0).  The two generic
+ * entries take a list and no regex - they do not know where it came from: the lists of rrx_search_all_extents* (earliest end first)
+ * work as well as the leftmost-longest ones.
+ * rrx_replace_matches_sizes (pass 1, a lane per item walking its matches): d_len[i] = length of output item i - every one of the
+ * nitems words, whatever it held; a length beyond 32 bits saturates at 0xFFFFFFFF - and d_pos[slot] = the offset inside the OUTPUT
+ * item at which that match's R begins, s_k - sum_{j<k} (e_j - s_j) + k * rep_len (32 bits), for exactly the slots d_first[0] ..
+ * d_first[nitems].  The caller turns d_len into the prefix d_out_off (u64, nitems + 1 entries); d_out_off[0] may be any value: a
+ * running offset into a larger buffer.
+ * rrx_replace_matches_fill (pass 2, the bytes): writes exactly d_out[d_out_off[0] .. d_out_off[nitems]) and, for every item, nothing
+ * outside [d_out_off[i], d_out_off[i+1]) whatever the lists hold; it reads no input byte outside an item - a source offset at or
+ * beyond the item's end yields a 0 byte.  d_rep is a DEVICE pointer (may be null when rep_len == 0); d_out may be null when nothing
+ * can be written; d_bytes, d_rep and d_out may sit at any address.  The kernel is driven by OUTPUT bytes (kernels_replace_items.hip):
+ * a wave takes 64 consecutive items and sweeps their output range 256 contiguous bytes per turn, whole dwords aligned by address;
+ * per byte the item is found among the wave's 64 staged output offsets and the segment among the item's d_pos entries.  One long
+ * item is one wave's work.
+ * Both generic entries are FULLY asynchronous on `stream` and can be captured into a graph: no read-back, no scratch, no event, no
+ * extent bound.  nitems == 0 writes nothing and returns RRX_OK.  RRX_ERR_ARG for null arguments, checked before any device call
+ * (d_start / d_end / d_pos are required when nitems > 0 even where the lists are empty).
+ * The one-call forms replace EVERY LEFTMOST-LONGEST match of `re` (rrx_search_all_longest_extents' list) and mirror that entry:
+ * synchronous; everything temporary - marks, counts, the match arrays, d_pos, d_len, the scans' scratch, a copy of `rep`, which is
+ * a HOST pointer here - lives in device memory the call allocates and frees.  d_out_off has nitems + 1 entries, d_out_off[0] = 0,
+ * complete either way, *total = d_out_off[nitems]; d_out holds `cap` bytes: if *total > cap NO byte of d_out is written - call
+ * again with *total bytes.  The scan carries 30 bits per count: a call that meets an item whose OUTPUT has 2^30 bytes or more
+ * returns RRX_ERR_UNSUPPORTED instead of a wrong column (use the search entries and the two generic passes, with a prefix of the
+ * caller's own).  An empty-language pattern copies the items; a pattern that accepts the empty string follows the rule above.
+ * nitems == 0: d_out_off[0] = 0, *total = 0.  RRX_ERR_ARG for null arguments, checked before any device call (rep may be null when
+ * rep_len == 0, d_out when cap == 0); RRX_ERR_UNSUPPORTED exactly where rrx_search_longest_extents returns it, for an empty batch
+ * too.  rrx_replace_all_longest_items uses the handle's bytes, offsets, item count, trim and device only (not its index).
+ * LONG ITEMS: matches end at or before offset 0xFFFFFFFE of their item, the rest of a longer item is copied verbatim (not tested:
+ * no test of a few seconds reaches it); d_pos is 32-bit, so the generic passes need every R to begin below 2^32 in its output item. */
+int rrx_replace_matches_sizes(int device, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint64_t *d_first, const uint32_t *d_start,
+                              const uint32_t *d_end, uint32_t rep_len, uint32_t *d_len, uint32_t *d_pos, void *stream);
+int rrx_replace_matches_fill(int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint64_t *d_first,
+                             const uint32_t *d_end, const uint32_t *d_pos, const void *d_rep, uint32_t rep_len, const uint64_t *d_out_off, void *d_out,
+                             void *stream);
+int rrx_replace_all_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                    const void *rep, uint32_t rep_len, uint64_t *d_out_off, void *d_out, size_t cap, size_t *total, void *stream);
+int rrx_replace_all_longest_items(const rrx_regex *re, const rrx_items *items, const void *rep, uint32_t rep_len, uint64_t *d_out_off, void *d_out,
+                                  size_t cap, size_t *total, void *stream);
+
 /* ONE device-resident string of any length (regex.h:156-159: operator++ consumes the whole string; '\n' and every
  * other byte are ordinary, a NUL or a byte >= 0x80 rejects).  d_accept[0] = 1 iff accepted.  Strings of 32 KiB and
  * more are split into chunks that are stepped in parallel from every table state (automata with <= 254 table

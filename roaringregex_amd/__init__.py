@@ -53,6 +53,7 @@ ABI_SYMBOLS = (
     "rrx_search_all_longest_marks_words",
     "rrx_search_all_longest_extents_count", "rrx_search_all_longest_extents_fill", "rrx_search_all_longest_extents",
     "rrx_search_all_longest_items_count", "rrx_search_all_longest_items_fill", "rrx_search_all_longest_items",
+    "rrx_replace_matches_sizes", "rrx_replace_matches_fill", "rrx_replace_all_longest_extents", "rrx_replace_all_longest_items",
 )
 
 
@@ -145,6 +146,10 @@ def _load():
         "rrx_search_all_longest_items_count": (i32, [vp, vp, vp, sz, vp, vp]),
         "rrx_search_all_longest_items_fill": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
         "rrx_search_all_longest_items": (i32, [vp, vp, vp, vp, vp, sz, C.POINTER(sz), vp]),
+        "rrx_replace_matches_sizes": (i32, [i32, vp, sz, u32, vp, vp, vp, u32, vp, vp, vp]),
+        "rrx_replace_matches_fill": (i32, [i32, vp, vp, sz, u32, vp, vp, vp, vp, u32, vp, vp, vp]),
+        "rrx_replace_all_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, u32, vp, vp, sz, C.POINTER(sz), vp]),
+        "rrx_replace_all_longest_items": (i32, [vp, vp, vp, u32, vp, vp, sz, C.POINTER(sz), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -198,6 +203,41 @@ def bitmap_count(bits, nlines, stream=None):
         _check(_L.rrx_bitmap_count(bits.device.index, C.c_void_p(bits.data_ptr() if nlines else 0), nlines, C.c_void_p(count.data_ptr()),
                                    _stream_ptr(stream)))
         return int(count.item())
+
+
+def _ptr(t):
+    """The address of a tensor's first element, or null for an empty one."""
+    return C.c_void_p(t.data_ptr() if t.numel() else 0)
+
+
+def replace_matches(data, offsets, first, start, end, repl, trim=0, stream=None):
+    """regexp_replace from a match list, written on the device (rrx_replace_matches_sizes, a torch.cumsum, rrx_replace_matches_fill):
+    item i = data[offsets[i] : offsets[i + 1] - trim]; its matches are start/end[first[i] : first[i + 1]], relative to the item, as
+    every search_all*_fused method returns them (`first` has n + 1 entries); `repl` is bytes, a literal.  -> (out uint8,
+    out_off int64[n + 1]): output item i = out[out_off[i] : out_off[i + 1]], the item with every match replaced by `repl`; the
+    separators are not copied.  The lists need not come from a regex of this library.  Waits for the output's size."""
+    import torch
+    n = offsets.numel() - 1
+    assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+    assert first.is_cuda and first.dtype in (torch.int64, torch.uint64) and first.is_contiguous() and first.numel() == n + 1
+    assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() for t in (start, end)) and start.numel() == end.numel()
+    assert isinstance(repl, (bytes, bytearray))
+    d = data.device.index
+    with _on(d, stream):
+        s = _stream_ptr(stream)
+        if not start.numel():                      # (the entries take no null array, even where the lists are empty)
+            start = end = torch.zeros(1, dtype=torch.int32, device=data.device)
+        length = torch.empty(n, dtype=torch.int32, device=data.device)
+        pos = torch.empty(start.numel(), dtype=torch.int32, device=data.device)
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
+        _check(_L.rrx_replace_matches_sizes(d, _ptr(offsets), n, trim, _ptr(first), _ptr(start), _ptr(end), len(repl), _ptr(length), _ptr(pos), s))
+        torch.cumsum(length.to(torch.int64) & 0xFFFFFFFF, dim=0, out=out_off[1:])
+        total = int(out_off[-1].item())
+        out = torch.empty(total, dtype=torch.uint8, device=data.device)
+        rep = torch.frombuffer(bytearray(repl), dtype=torch.uint8).to(data.device) if repl else torch.empty(0, dtype=torch.uint8, device=data.device)
+        _check(_L.rrx_replace_matches_fill(d, _ptr(data), _ptr(offsets), n, trim, _ptr(first), _ptr(end), _ptr(pos), _ptr(rep), len(repl), _ptr(out_off),
+                                           _ptr(out), s))
+    return out, out_off
 
 
 class Match:
@@ -724,6 +764,43 @@ class RRegex:
             s = _stream_ptr(stream)
             return self._search_all_one_call(data.device, n, cap,
                                              lambda f, st, en, cp, tot: _L.rrx_search_all_longest_extents(self._h, d, b, o, n, trim, f, st, en, cp, tot, s))
+
+    def _replace_one_call(self, dev, n, cap, call):
+        """The one-call replace entry, repeated with the exact size if `cap` was too small -> (out uint8, out_off int64[n + 1])."""
+        import torch
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        while True:
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            total = C.c_size_t(0)
+            _check(call(_ptr(out_off), _ptr(out), cap, C.byref(total)))
+            if total.value <= cap:
+                break
+            cap = total.value
+        return out[:total.value], out_off
+
+    def replace_all_longest_extents(self, data, offsets, repl, trim=0, cap=None, stream=None):
+        """regexp_replace on a string column (rrx_replace_all_longest_extents): item i = data[offsets[i] : offsets[i+1] - trim] with
+        EVERY LEFTMOST-LONGEST match replaced by the literal `repl` (bytes; no group references) -> (out uint8, out_off int64[n + 1]),
+        output item i = out[out_off[i] : out_off[i + 1]] - re.sub(p, lambda m: repl, item); the separators are not copied.  cap: bytes
+        to provide for at first (default: the size of `data`); the call is repeated with the exact size if the column is larger."""
+        import torch
+        n = offsets.numel() - 1
+        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+        assert isinstance(repl, (bytes, bytearray))
+        d, b, o, rep = data.device.index, _ptr(data), C.c_void_p(offsets.data_ptr()), bytes(repl)
+        with _on(d, stream):
+            s = _stream_ptr(stream)
+            return self._replace_one_call(data.device, n, int(cap) if cap is not None else data.numel(),
+                                          lambda f, out, cp, tot: _L.rrx_replace_all_longest_extents(self._h, d, b, o, n, trim, rep, len(rep), f, out, cp, tot, s))
+
+    def replace_all_longest_items(self, items, repl, cap=None, stream=None):
+        """The same for an indexed batch (rrx_replace_all_longest_items) -> (out uint8, out_off int64[n + 1])."""
+        assert isinstance(repl, (bytes, bytearray))
+        rep = bytes(repl)
+        with _on(items.device, stream):
+            s = _stream_ptr(stream)
+            return self._replace_one_call(items.data.device, items.num_items, int(cap) if cap is not None else items.data.numel(),
+                                          lambda f, out, cp, tot: _L.rrx_replace_all_longest_items(self._h, items._h, rep, len(rep), f, out, cp, tot, s))
 
     def match_string(self, data, stream=None):
         """ONE device-resident string of any length (regex.h:156-159); '\n' is an ordinary character.  -> bool"""

@@ -316,6 +316,23 @@ int search_all_longest_extents_dfa(const SearchLongestDevice &p, bool in_global,
                                    uint32_t trim, uint32_t *marks, size_t marks_words, uint32_t *count, const uint64_t *first, uint32_t *match_start,
                                    uint32_t *match_end, size_t cap, void *stream);
 
+// ---- regexp_replace on explicit items, from a match list: kernels_replace_items.hip
+// Item i = bytes[off[i] .. off[i+1] - trim); its matches are the slots first[i] .. first[i + 1] of match_start / match_end (relative
+// to the item, in order, not overlapping: what every search_all* launcher above leaves); R = `rep_len` literal bytes.  The output
+// item is the item with every match replaced by R.  No table: the kernels do not know which search made the list.
+// replace_sizes (a lane per item): len[i] = the output item's length, saturated at ~0u, every one of the nitems words written;
+// pos[slot] = the offset inside the output item at which that match's R begins, exactly the slots first[0] .. first[nitems].
+// too_long != nullptr: *too_long = 1 (a plain store) if some output item has 2^30 bytes or more - what scan_counts cannot carry.
+// replace_fill (a wave per 64 items, driven by output bytes): exactly the bytes out[out_off[0] .. out_off[nitems]), for item i
+// nothing outside [out_off[i], out_off[i + 1]) whatever the lists hold; no byte outside an item is read (a source offset at or
+// beyond the item's end gives 0).  rep (device memory) may be null when rep_len == 0, out when nothing can be written; both and
+// `bytes` may sit at any address.  Both launch at most kReplaceMaxBlocks workgroups of kThreads lanes, then the grid strides.
+constexpr size_t kReplaceMaxBlocks = 512;        // one generation on the 256 CUs at two workgroups each
+int replace_sizes(const uint64_t *off, size_t nitems, uint32_t trim, const uint64_t *first, const uint32_t *match_start, const uint32_t *match_end,
+                  uint32_t rep_len, uint32_t *len, uint32_t *pos, uint32_t *too_long, void *stream);
+int replace_fill(const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim, const uint64_t *first, const uint32_t *match_end,
+                 const uint32_t *pos, const uint8_t *rep, uint32_t rep_len, const uint64_t *out_off, uint8_t *out, void *stream);
+
 // ---- one long string on the plain DFA: kernels_long.hip
 // One long string (regex.h:156-159 consumes it byte by byte): the string is cut into chunks, every chunk is stepped
 // from EVERY table state at once (lane = (chunk, start state); the lanes of a chunk read the same text), which yields

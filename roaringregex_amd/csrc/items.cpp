@@ -1,5 +1,5 @@
 // items.cpp — explicit items (an offsets array: rrx_match_extents / rrx_contains_extents / rrx_search_extents / rrx_search_all_extents* /
-// rrx_search_longest_extents / rrx_search_all_longest_extents*, and rrx_items, the batch indexed once)
+// rrx_search_longest_extents / rrx_search_all_longest_extents* / rrx_replace_*, and rrx_items, the batch indexed once)
 // and single strings (rrx_match_string, rrx_match_cstr).
 #include <algorithm>
 #include <cstring>
@@ -359,8 +359,39 @@ static int search_all_longest_lanes(const rrx_regex *re, const ItemBatch &b, Ite
 // The marks of a batch of nitems items take a word per item at the very least, whatever the extent: a shorter buffer cannot be meant
 static bool marks_ok(size_t nitems, const uint32_t *d_marks, size_t marks_words) { return !nitems || (d_marks && marks_words >= nitems + 1); }
 static const char *const kMarksError = "null argument, or marks_words below nitems + 1";
-// count + scan + fill in one call (search_all_one_call), the marks too in device memory of the call's own, sized from the batch's
-// real extent: off[0] and off[nitems] are read back.
+// count + scan of one call (search_all_one_call's first half), the counts, the marks and the scan's scratch in device memory of the
+// call's own, the marks sized from the batch's real extent: off[0] and off[nitems] are read back.  Leaves d_first complete
+// (nitems + 1 entries, entry 0 = 0) and *total = d_first[nitems]; nitems > 0, the tables checked by the caller.
+struct LongestCounts {
+    DeviceArray<uint32_t> count, marks;
+    DeviceArray<uint64_t> sums;                  // scan_scratch_words(nitems): free again once the call has synchronised
+    size_t nwords = 0;
+};
+static int search_all_longest_count_scan(const rrx_regex *re, const ItemBatch &b, LongestCounts &c, uint64_t *d_first, size_t *total, void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t lo = 0, hi = 0;
+    HIP_TRY(hipMemcpyAsync(&lo, off, sizeof lo, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&hi, off + nitems, sizeof hi, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c.nwords = rrx_search_all_longest_marks_words(hi > lo ? (size_t)(hi - lo) : 0, nitems);
+    hipError_t he = c.count.alloc(device, nitems * sizeof(uint32_t));
+    if (he == hipSuccess) he = c.marks.alloc(device, c.nwords * sizeof(uint32_t));
+    if (he == hipSuccess) he = c.sums.alloc(device, dev::scan_scratch_words(nitems) * sizeof(uint64_t));
+    if (he != hipSuccess) return hip_fail(he, "hipMalloc(search_all_longest counts and marks)");
+    const int rc = search_all_longest_lanes(re, b, {c.marks, c.nwords}, c.count, nullptr, nullptr, nullptr, 0, stream);
+    if (rc) return rc;
+    const int le = dev::scan_counts(c.count, d_first, c.sums, nitems, stream);  // d_first[nitems] = total
+    if (le) return hip_fail((hipError_t)le, "search_all_longest scan launch");
+    he = hipMemsetAsync(d_first, 0, sizeof(uint64_t), st);                      // the scan marks entry 0 as a stripe start: not here
+    uint64_t tot = 0;
+    if (he == hipSuccess) he = hipMemcpyAsync(&tot, d_first + nitems, sizeof tot, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return hip_fail(he, "search_all_longest scan");
+    *total = (size_t)tot;
+    return RRX_OK;
+}
+// count + scan + fill in one call (search_all_one_call)
 static int search_all_longest_one_call(const rrx_regex *re, const ItemBatch &b, uint64_t *d_first, uint32_t *d_start, uint32_t *d_end, size_t cap,
                                        size_t *total, void *stream) {
     const auto &[device, bytes, off, nitems, trim] = b;
@@ -369,31 +400,12 @@ static int search_all_longest_one_call(const rrx_regex *re, const ItemBatch &b, 
     int rc = search_all_longest_lanes(re, batch_of(device, bytes, off, 0, trim), {}, nullptr, nullptr, nullptr, nullptr, 0, stream);   // (the tables, the device)
     if (rc) return rc;
     if (!nitems) { HIP_TRY(hipMemsetAsync(d_first, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
-    uint64_t lo = 0, hi = 0;
-    HIP_TRY(hipMemcpyAsync(&lo, off, sizeof lo, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&hi, off + nitems, sizeof hi, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const size_t nwords = rrx_search_all_longest_marks_words(hi > lo ? (size_t)(hi - lo) : 0, nitems);
-    DeviceArray<uint32_t> d_count, d_marks;
-    DeviceArray<uint64_t> d_sums;
-    hipError_t he = d_count.alloc(device, nitems * sizeof(uint32_t));
-    if (he == hipSuccess) he = d_marks.alloc(device, nwords * sizeof(uint32_t));
-    if (he == hipSuccess) he = d_sums.alloc(device, dev::scan_scratch_words(nitems) * sizeof(uint64_t));
-    if (he != hipSuccess) return hip_fail(he, "hipMalloc(search_all_longest counts and marks)");
-    const ItemMarks marks{d_marks, nwords};
-    rc = search_all_longest_lanes(re, b, marks, d_count, nullptr, nullptr, nullptr, 0, stream);
+    LongestCounts c;
+    rc = search_all_longest_count_scan(re, b, c, d_first, total, stream);
     if (rc) return rc;
-    const int le = dev::scan_counts(d_count, d_first, d_sums, nitems, stream);  // d_first[nitems] = total
-    if (le) return hip_fail((hipError_t)le, "search_all_longest scan launch");
-    he = hipMemsetAsync(d_first, 0, sizeof(uint64_t), st);                      // the scan marks entry 0 as a stripe start: not here
-    uint64_t tot = 0;
-    if (he == hipSuccess) he = hipMemcpyAsync(&tot, d_first + nitems, sizeof tot, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return hip_fail(he, "search_all_longest scan");
-    *total = (size_t)tot;
-    if (tot && cap) {                                                            // matches in slots >= cap are counted, not written
-        rc = search_all_longest_lanes(re, b, marks, nullptr, d_first, d_start, d_end, cap, stream);
-        if (!rc) { he = hipStreamSynchronize(st); if (he != hipSuccess) rc = hip_fail(he, "search_all_longest fill"); }
+    if (*total && cap) {                                                         // matches in slots >= cap are counted, not written
+        rc = search_all_longest_lanes(re, b, {c.marks, c.nwords}, nullptr, d_first, d_start, d_end, cap, stream);
+        if (!rc) { const hipError_t he = hipStreamSynchronize(st); if (he != hipSuccess) rc = hip_fail(he, "search_all_longest fill"); }
     }
     return rc;
 }
@@ -429,6 +441,91 @@ int rrx_search_all_longest_items(const rrx_regex *re, const rrx_items *it, uint6
                                  size_t *total, void *stream) {
     if (!re || !it || !total || !d_first || (it->nitems && cap && (!d_start || !d_end))) return fail(RRX_ERR_ARG, "null argument");
     return search_all_longest_one_call(re, batch_of(it), d_first, d_start, d_end, cap, total, stream);
+}
+
+// regexp_replace from a match list (kernels_replace_items.hip): the two passes of every CSR result.  No regex, no table, nothing
+// known on the host and nothing read back.
+int rrx_replace_matches_sizes(int device, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint64_t *d_first, const uint32_t *d_start,
+                              const uint32_t *d_end, uint32_t rep_len, uint32_t *d_len, uint32_t *d_pos, void *stream) {
+    if (nitems && (!d_off || !d_first || !d_start || !d_end || !d_len || !d_pos)) return fail(RRX_ERR_ARG, "null argument");
+    if (!nitems) return RRX_OK;
+    HIP_TRY(hipSetDevice(device));
+    return launched(dev::replace_sizes(d_off, nitems, trim, d_first, d_start, d_end, rep_len, d_len, d_pos, nullptr, stream), "replace_sizes launch");
+}
+int rrx_replace_matches_fill(int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint64_t *d_first,
+                             const uint32_t *d_end, const uint32_t *d_pos, const void *d_rep, uint32_t rep_len, const uint64_t *d_out_off, void *d_out,
+                             void *stream) {
+    if (nitems && (!d_off || !d_first || !d_end || !d_pos || !d_out_off || (rep_len && !d_rep))) return fail(RRX_ERR_ARG, "null argument");
+    if (!nitems) return RRX_OK;
+    HIP_TRY(hipSetDevice(device));
+    return launched(dev::replace_fill(static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_first, d_end, d_pos, static_cast<const uint8_t *>(d_rep),
+                                      rep_len, d_out_off, static_cast<uint8_t *>(d_out), stream),
+                    "replace_fill launch");
+}
+// Every leftmost-longest match replaced, in one call: search_all_longest_one_call's count + scan and fill into match arrays of the
+// call's own, then sizes, a second scan (the lengths into d_out_off) and - if the column fits `cap` - the bytes.  The sizes kernel
+// raises a device word where an output item has 2^30 bytes or more (the scan carries 30 bits); it is read back with the total.
+static int replace_all_longest_one_call(const rrx_regex *re, const ItemBatch &b, const void *rep, uint32_t rep_len, uint64_t *d_out_off, void *d_out,
+                                        size_t cap, size_t *total, void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
+    *total = 0;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = search_all_longest_lanes(re, batch_of(device, bytes, off, 0, trim), {}, nullptr, nullptr, nullptr, nullptr, 0, stream);   // (the tables, the device)
+    if (rc) return rc;
+    if (!nitems) { HIP_TRY(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
+    LongestCounts c;
+    DeviceArray<uint64_t> d_first;
+    hipError_t he = d_first.alloc(device, (nitems + 1) * sizeof(uint64_t));
+    if (he != hipSuccess) return hip_fail(he, "hipMalloc(replace prefix)");
+    size_t nmatches = 0;
+    rc = search_all_longest_count_scan(re, b, c, d_first, &nmatches, stream);
+    if (rc) return rc;
+    // (one word more than the lists need: the generic kernels are never handed a null array; the last word of d_len is the flag)
+    DeviceArray<uint32_t> d_start, d_end, d_pos, d_len;
+    DeviceArray<uint8_t> d_rep;
+    const size_t list_bytes = (nmatches + 1) * sizeof(uint32_t);
+    he = d_start.alloc(device, list_bytes);
+    if (he == hipSuccess) he = d_end.alloc(device, list_bytes);
+    if (he == hipSuccess) he = d_pos.alloc(device, list_bytes);
+    if (he == hipSuccess) he = d_len.alloc(device, (nitems + 1) * sizeof(uint32_t));
+    if (he == hipSuccess && rep_len) he = d_rep.alloc(device, rep_len);
+    if (he != hipSuccess) return hip_fail(he, "hipMalloc(replace lists)");
+    if (rep_len) HIP_TRY(hipMemcpyAsync(d_rep, rep, rep_len, hipMemcpyHostToDevice, st));      // (the call does not return before a synchronise: `rep` stays valid)
+    if (nmatches) {
+        rc = search_all_longest_lanes(re, b, {c.marks, c.nwords}, nullptr, d_first, d_start, d_end, nmatches, stream);
+        if (rc) return rc;
+    }
+    uint32_t *d_flag = d_len + nitems;
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st));
+    int le = dev::replace_sizes(off, nitems, trim, d_first, d_start, d_end, rep_len, d_len, d_pos, d_flag, stream);
+    if (!le) le = dev::scan_counts(d_len, d_out_off, c.sums, nitems, stream);   // d_out_off[nitems] = total (the first scan's scratch: the stream orders them)
+    if (le) return hip_fail((hipError_t)le, "replace sizes and scan launch");
+    he = hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), st);                     // the scan marks entry 0 as a stripe start: not here
+    uint64_t tot = 0;
+    uint32_t flag = 0;
+    if (he == hipSuccess) he = hipMemcpyAsync(&tot, d_out_off + nitems, sizeof tot, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return hip_fail(he, "replace scan");
+    if (flag) return fail(RRX_ERR_UNSUPPORTED, "an output item of 2^30 bytes or more: use rrx_search_all_longest_extents and the two passes rrx_replace_matches_sizes / _fill");
+    *total = (size_t)tot;
+    if (tot && tot <= cap) {                                                     // a column beyond cap: not a byte of it is written
+        le = dev::replace_fill(bytes, off, nitems, trim, d_first, d_end, d_pos, d_rep, rep_len, d_out_off, static_cast<uint8_t *>(d_out), stream);
+        if (le) return hip_fail((hipError_t)le, "replace_fill launch");
+        he = hipStreamSynchronize(st);
+        if (he != hipSuccess) return hip_fail(he, "replace fill");
+    }
+    return RRX_OK;
+}
+int rrx_replace_all_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                    const void *rep, uint32_t rep_len, uint64_t *d_out_off, void *d_out, size_t cap, size_t *total, void *stream) {
+    if (!re || !total || !d_out_off || (rep_len && !rep) || (nitems && (!d_off || (cap && !d_out)))) return fail(RRX_ERR_ARG, "null argument");
+    return replace_all_longest_one_call(re, batch_of(device, d_bytes, d_off, nitems, trim), rep, rep_len, d_out_off, d_out, cap, total, stream);
+}
+int rrx_replace_all_longest_items(const rrx_regex *re, const rrx_items *it, const void *rep, uint32_t rep_len, uint64_t *d_out_off, void *d_out,
+                                  size_t cap, size_t *total, void *stream) {
+    if (!re || !it || !total || !d_out_off || (rep_len && !rep) || (it->nitems && cap && !d_out)) return fail(RRX_ERR_ARG, "null argument");
+    return replace_all_longest_one_call(re, batch_of(it), rep, rep_len, d_out_off, d_out, cap, total, stream);
 }
 
 // One device-resident string of any length.  Long strings take the chunk-map path when the automaton has a small

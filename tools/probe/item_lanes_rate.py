@@ -13,6 +13,13 @@ items (offsets = the line starts, trim 1: the '\\n' is the separator):
                   sides do not find the same and "within_margin" says how far the new entry is from that yardstick, not whether
                   anything got slower.
 
+  replace         the column with every leftmost-longest match replaced (kernels_replace_items.hip), rep_len 1 and 16: per launch
+                  rrx_replace_matches_sizes, rrx_replace_matches_fill (the lists found once, outside the timed window) and the
+                  one-call rrx_replace_all_longest_extents (search, scans, sizes and fill, its allocations included), and as the
+                  yardstick a device-to-device copy of the column's bytes - the least any writer of a column can cost -, the four
+                  alternating inside one process.  The parent has no such entry and plays no part: one child per text, this tree
+                  alone; the lines and a summary (fill as a share of the copy's rate) go to `--out` as well.
+
 The parent's side runs from a second checkout under .oldtree/ (git archive <commit> | tar -x -C .oldtree; build there): per text
 four children - parent, tree, parent, tree -, a fresh process each; device events around every launch (every sweep of slices),
 median and spread of `--launches` launches (at least twelve) after warm-up.  A child that fails ends the run: nothing more is
@@ -20,6 +27,7 @@ started on the device.  The last line per text gives the margin - what the paren
 between its two medians and its own spread - and whether each of the tree's medians is within it of the slower parent median.
 
     python tools/probe/item_lanes_rate.py --entry search [--old .oldtree] [--launches 15] [--scale 1.0]
+    python tools/probe/item_lanes_rate.py --entry replace [--launches 15] [--scale 1.0] [--out profiles/replace_items_rate.txt]
 """
 import argparse
 import json
@@ -30,7 +38,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CONFIGS = (("url", "U2", 1 << 30), ("email", "EMAIL", 1 << 30), ("kwlog", "K1000C", 1 << 30))
-ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest")
+ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "replace")
 YARDSTICK = {"search_all_longest": "search_all"}   # entries the parent lacks: what its side runs instead
 SLICE = 65535                                  # items per call of match / contains: one below kItemsStripesMin
 
@@ -52,6 +60,8 @@ def child(tree, entry, kind, pkey, nbytes, launches):
     dev = torch.from_numpy(host).cuda()
     off = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.nonzero(dev == 10).flatten() + 1]).contiguous()
     n = off.numel() - 1
+    if entry == "replace":
+        return replace_child(rr, r, kind, dev, off, n, launches)
 
     if entry in ("match", "contains"):
         slices = [off[k:k + SLICE + 1] for k in range(0, n, SLICE)]
@@ -89,17 +99,94 @@ def child(tree, entry, kind, pkey, nbytes, launches):
                       "spread": round((ms[-1] - ms[0]) / med, 4)}), flush=True)
 
 
+def replace_child(rr, r, kind, dev, off, n, launches):
+    """sizes, fill, the one-call form and a device-to-device copy of the column, alternating, per rep_len one JSON line."""
+    import ctypes as C
+    import torch
+    L, s, nbytes = rr._L, rr._stream_ptr(None), int(dev.numel())
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    first, start, end = r.search_all_longest_extents_fused(dev, off, trim=1)
+    copy_to = torch.empty_like(dev)
+    for rep_len in (1, 16):
+        rep = bytes(range(65, 65 + rep_len))
+        d_rep = torch.frombuffer(bytearray(rep), dtype=torch.uint8).cuda()
+        length = torch.empty(n, dtype=torch.int32, device="cuda")
+        pos = torch.empty(max(int(start.numel()), 1), dtype=torch.int32, device="cuda")
+        sizes = lambda: rr._check(L.rrx_replace_matches_sizes(0, ptr(off), n, 1, ptr(first), ptr(start), ptr(end), rep_len, ptr(length), ptr(pos), s))
+        sizes()
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+        torch.cumsum(length.to(torch.int64), dim=0, out=out_off[1:])
+        total = int(out_off[-1])
+        out = torch.empty(total, dtype=torch.uint8, device="cuda")
+        fill = lambda: rr._check(L.rrx_replace_matches_fill(0, ptr(dev), ptr(off), n, 1, ptr(first), ptr(end), ptr(pos), ptr(d_rep), rep_len, ptr(out_off),
+                                                            ptr(out), s))
+        one_off, one_out, tot = torch.empty(n + 1, dtype=torch.int64, device="cuda"), torch.empty(total, dtype=torch.uint8, device="cuda"), C.c_size_t(0)
+        one = lambda: rr._check(L.rrx_replace_all_longest_extents(r._h, 0, ptr(dev), ptr(off), n, 1, rep, rep_len, ptr(one_off), ptr(one_out), total,
+                                                                  C.byref(tot), s))
+        calls = {"copy": lambda: copy_to.copy_(dev), "sizes": sizes, "fill": fill, "one_call": one}
+        for _ in range(3):
+            for call in calls.values():
+                call()
+        torch.cuda.synchronize()
+        assert tot.value == total and torch.equal(one_out, out) and torch.equal(one_off, out_off), "the one-call form and the two passes differ"
+        ms = {k: [] for k in calls}
+        for _ in range(launches):
+            for k, call in calls.items():                   # alternating: every launch of a kernel has a copy right beside it
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(); call(); b.record()
+                b.synchronize()
+                ms[k].append(a.elapsed_time(b))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        line = {"config": kind, "entry": "replace", "rep_len": rep_len, "bytes": nbytes, "items": n, "matches": int(start.numel()), "out_bytes": total}
+        for k in calls:
+            line[k + "_ms"] = round(med[k], 4)
+            line[k + "_spread"] = round((max(ms[k]) - min(ms[k])) / med[k], 4)
+        line["copy_GB/s"] = round(nbytes / med["copy"] / 1e6, 1)                    # bytes copied (read and written once each)
+        line["fill_GB/s"] = round(total / med["fill"] / 1e6, 1)                     # bytes of the new column written
+        line["fill_share_of_copy"] = round((total / med["fill"]) / (nbytes / med["copy"]), 4)
+        print(json.dumps(line), flush=True)
+
+
+def replace_main(a):
+    """One child per text, this tree alone; the lines and a summary to a.out."""
+    lines = []
+    for kind, pkey, nbytes in CONFIGS:
+        n = int(nbytes * a.scale) // 4096 * 4096
+        env = dict(os.environ)
+        env.pop("RRX_LIB", None)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", "replace", "--launches", str(a.launches), "--child", ROOT, kind, pkey, str(n)],
+                           env=env, timeout=600, stdout=subprocess.PIPE, text=True)
+        sys.stdout.write(p.stdout)
+        sys.stdout.flush()
+        if p.returncode:                       # a fault or a time limit: nothing more is started on the device
+            raise SystemExit("child failed with %d: replace %s" % (p.returncode, kind))
+        lines += [json.loads(x) for x in p.stdout.strip().splitlines()]
+    shares = [x["fill_share_of_copy"] for x in lines]
+    summary = {"entry": "replace", "launches": max(a.launches, 12), "scale": a.scale, "fill_share_of_copy_min": min(shares), "fill_share_of_copy_max": max(shares),
+               "fill_under_a_quarter_of_the_copy": min(shares) < 0.25}
+    print(json.dumps(summary), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("tools/probe/item_lanes_rate.py --entry replace --launches %d --scale %g: medians of device-event times per launch, the four calls\n"
+                "alternating in one process per text; GB/s = bytes of the column written (fill) or copied (copy) per second.\n" % (a.launches, a.scale))
+        for x in lines + [summary]:
+            f.write(json.dumps(x) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entry", choices=ENTRIES, required=True)
     ap.add_argument("--old", default=os.path.join(ROOT, ".oldtree"))
     ap.add_argument("--launches", type=int, default=15)
     ap.add_argument("--scale", type=float, default=1.0, help="corpus sizes times this (a quick run)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "replace_items_rate.txt"), help="--entry replace: where the lines and the summary go")
     ap.add_argument("--child", nargs=4, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
         tree, kind, pkey, nbytes = a.child
         return child(tree, a.entry, kind, pkey, int(nbytes), max(a.launches, 12))
+    if a.entry == "replace":
+        return replace_main(a)
     assert os.path.exists(os.path.join(a.old, "roaringregex_amd", "librrx.so")), "build the parent commit under %s first" % a.old
     for kind, pkey, nbytes in CONFIGS:
         n = int(nbytes * a.scale) // 4096 * 4096
