@@ -463,6 +463,64 @@ int rrx_replace_all_longest_extents(const rrx_regex *re, int device, const void 
 int rrx_replace_all_longest_items(const rrx_regex *re, const rrx_items *items, const void *rep, uint32_t rep_len, uint64_t *d_out_off, void *d_out,
                                   size_t cap, size_t *total, void *stream);
 
+/* regexp_extract_all and split on a string column, WRITTEN on the device as an Arrow list<binary> column: from a column and a match
+ * list per item to the PIECES of every item.  Item i is t = d_bytes[d_off[i] .. d_off[i+1] - trim), L its length; its matches
+ * (s_0,e_0) ... (s_{m-1},e_{m-1}) come in the shape rrx_replace_matches_sizes takes (d_first[nitems + 1], match k in slot
+ * d_first[i] + k of d_start / d_end, d_first[0] need not be 0).  Two modes:
+ *   RRX_PIECES_MATCHES (extract_all): m pieces, piece k = t[s_k:e_k];
+ *   RRX_PIECES_GAPS (split): m + 1 pieces, piece k = t[e_{k-1}:s_k] with e_{-1} = 0 and s_m = L.
+ * For a pattern without groups these are Python's [x.group() for x in re.finditer(p, t)] and re.split(p, t): [0-9]+ on "a1 22 333"
+ * gives "1" "22" "333" and "a" " " " " ""; a* on "baab" gives "" "aa" "" "" and "" "b" "" "b" "".  The gaps joined are the item with
+ * every match replaced by nothing.  CLAMPING: with a_0 = 0, for each k: s' = clamp(s_k, a_k, L), e' = clamp(e_k, s', L), the match
+ * piece is [s', e'), the gap piece [a_k, s'), a_{k+1} = e'; the last gap is [a_m, L) - the identity for the list of a search, and no
+ * list makes the kernels read outside the item.
+ * THE COLUMN: d_list_off[nitems + 1] (u64) - the pieces of item i are d_list_off[i] .. d_list_off[i+1]: d_first[i] - d_first[0] for
+ * MATCHES, d_first[i] - d_first[0] + i for GAPS; d_piece_off[npieces + 1] (u64) - the bytes of piece p are d_out[d_piece_off[p] ..
+ * d_piece_off[p+1]); d_out - the pieces' bytes one behind the other, no separators.
+ * rrx_pieces_sizes (pass 1, a lane per item walking its matches): d_list_off - all nitems + 1 words - and for every piece p
+ * d_piece_len[p] (u32, saturated at 0xFFFFFFFF) and d_piece_src[p] (u64: d_off[i] + the piece's clamped start, an absolute offset
+ * into d_bytes), exactly the slots 0 .. npieces - 1.  The caller turns d_piece_len into the prefix d_piece_off (npieces + 1 entries;
+ * entry 0 may be any value: a running offset into a larger buffer).
+ * rrx_pieces_fill (pass 2, the bytes): d_out[d_piece_off[p] + r] = d_bytes[d_piece_src[p] + r] for r < d_piece_off[p+1] -
+ * d_piece_off[p]: exactly the bytes d_out[d_piece_off[0] .. d_piece_off[npieces]), each once; no byte of d_bytes outside a piece is
+ * read.  It takes any ascending d_piece_off and any d_piece_src - it does not know where they came from (a first-match-only
+ * regexp_extract column is rrx_search_longest_extents and this entry).  The kernel divides its work by OUTPUT BYTES alone
+ * (kernels_pieces_items.hip): the waves of a fixed grid take chunks of 4 KiB of the output range, whole dwords aligned by address,
+ * 256 contiguous bytes per wave instruction, the piece of a byte found by searches over d_piece_off - one piece of 64 MiB costs
+ * every wave what 64 MiB of short pieces cost.  d_bytes and d_out may sit at any address and may be null where nothing can be read
+ * or written.
+ * Both generic entries are FULLY asynchronous on `stream` and can be captured into a graph: no read-back, no scratch, no event.
+ * nitems == 0 / npieces == 0 write nothing and return RRX_OK.  RRX_ERR_ARG for null arguments and for a mode other than the two,
+ * checked before any device call.
+ * The one-call forms take EVERY LEFTMOST-LONGEST match of `re` (rrx_search_all_longest_extents' list) and mirror
+ * rrx_replace_all_longest_extents: synchronous; everything temporary lives in device memory the call allocates and frees.
+ * d_list_off has nitems + 1 entries, entry 0 = 0, complete either way; *npieces and *total (the bytes of all pieces) are exact
+ * either way.  d_piece_off holds pieces_cap + 1 entries (entry 0 = 0) and is written iff *npieces <= pieces_cap; d_out holds `cap`
+ * bytes and is written iff additionally *total <= cap - otherwise not a byte of it: call again with the exact sizes.  nitems == 0:
+ * d_list_off[0] = 0, d_piece_off[0] = 0, both counts 0.  The empty language: extract_all gives empty lists, split one piece per
+ * item, the item; a pattern that accepts the empty string follows the rule above.  RRX_ERR_ARG for null arguments, checked before
+ * any device call (d_out may be null when cap == 0); RRX_ERR_UNSUPPORTED exactly where rrx_search_longest_extents returns it, for an
+ * empty batch too, and for a piece of 2^30 bytes or more (the scan carries 30 bits per length: use rrx_search_all_longest_extents
+ * and the generic pair with a prefix of the caller's own).  The _items forms use the handle's bytes, offsets, item count, trim and
+ * device only (not its index).  LONG ITEMS: matches end at or before offset 0xFFFFFFFE of their item (not tested: no test of a few
+ * seconds reaches it).                                                                                                              */
+#define RRX_PIECES_MATCHES 0
+#define RRX_PIECES_GAPS 1
+int rrx_pieces_sizes(int device, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint64_t *d_first, const uint32_t *d_start,
+                     const uint32_t *d_end, int mode, uint64_t *d_list_off, uint32_t *d_piece_len, uint64_t *d_piece_src, void *stream);
+int rrx_pieces_fill(int device, const void *d_bytes, const uint64_t *d_piece_src, const uint64_t *d_piece_off, size_t npieces, void *d_out,
+                    void *stream);
+int rrx_extract_all_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                    uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap, void *d_out, size_t cap, size_t *npieces,
+                                    size_t *total, void *stream);
+int rrx_extract_all_longest_items(const rrx_regex *re, const rrx_items *items, uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap,
+                                  void *d_out, size_t cap, size_t *npieces, size_t *total, void *stream);
+int rrx_split_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                              uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap, void *d_out, size_t cap, size_t *npieces,
+                              size_t *total, void *stream);
+int rrx_split_longest_items(const rrx_regex *re, const rrx_items *items, uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap,
+                            void *d_out, size_t cap, size_t *npieces, size_t *total, void *stream);
+
 /* ONE device-resident string of any length (regex.h:156-159: operator++ consumes the whole string; '\n' and every
  * other byte are ordinary, a NUL or a byte >= 0x80 rejects).  d_accept[0] = 1 iff accepted.  Strings of 32 KiB and
  * more are split into chunks that are stepped in parallel from every table state (automata with <= 254 table

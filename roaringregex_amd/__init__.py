@@ -54,6 +54,8 @@ ABI_SYMBOLS = (
     "rrx_search_all_longest_extents_count", "rrx_search_all_longest_extents_fill", "rrx_search_all_longest_extents",
     "rrx_search_all_longest_items_count", "rrx_search_all_longest_items_fill", "rrx_search_all_longest_items",
     "rrx_replace_matches_sizes", "rrx_replace_matches_fill", "rrx_replace_all_longest_extents", "rrx_replace_all_longest_items",
+    "rrx_pieces_sizes", "rrx_pieces_fill", "rrx_extract_all_longest_extents", "rrx_extract_all_longest_items", "rrx_split_longest_extents",
+    "rrx_split_longest_items",
 )
 
 
@@ -150,6 +152,12 @@ def _load():
         "rrx_replace_matches_fill": (i32, [i32, vp, vp, sz, u32, vp, vp, vp, vp, u32, vp, vp, vp]),
         "rrx_replace_all_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, u32, vp, vp, sz, C.POINTER(sz), vp]),
         "rrx_replace_all_longest_items": (i32, [vp, vp, vp, u32, vp, vp, sz, C.POINTER(sz), vp]),
+        "rrx_pieces_sizes": (i32, [i32, vp, sz, u32, vp, vp, vp, i32, vp, vp, vp, vp]),
+        "rrx_pieces_fill": (i32, [i32, vp, vp, vp, sz, vp, vp]),
+        "rrx_extract_all_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
+        "rrx_extract_all_longest_items": (i32, [vp, vp, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
+        "rrx_split_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
+        "rrx_split_longest_items": (i32, [vp, vp, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -238,6 +246,42 @@ def replace_matches(data, offsets, first, start, end, repl, trim=0, stream=None)
         _check(_L.rrx_replace_matches_fill(d, _ptr(data), _ptr(offsets), n, trim, _ptr(first), _ptr(end), _ptr(pos), _ptr(rep), len(repl), _ptr(out_off),
                                            _ptr(out), s))
     return out, out_off
+
+
+PIECES_MATCHES, PIECES_GAPS = 0, 1
+
+
+def pieces_of_matches(data, offsets, first, start, end, gaps=False, trim=0, stream=None):
+    """regexp_extract_all (gaps=False) or split (gaps=True) from a match list, written on the device as a list<binary> column
+    (rrx_pieces_sizes, a torch.cumsum, rrx_pieces_fill): item i = data[offsets[i] : offsets[i + 1] - trim]; its matches are
+    start/end[first[i] : first[i + 1]], relative to the item, as every search_all*_fused method returns them (`first` has n + 1
+    entries).  -> (out uint8, piece_off int64[npieces + 1], list_off int64[n + 1]): the pieces of item i are list_off[i] ..
+    list_off[i + 1], piece p = out[piece_off[p] : piece_off[p + 1]] - the matches themselves, or what lies between them (one more
+    than the matches: re.split).  The lists need not come from a regex of this library.  Waits for the output's size."""
+    import torch
+    n = offsets.numel() - 1
+    assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+    assert first.is_cuda and first.dtype in (torch.int64, torch.uint64) and first.is_contiguous() and first.numel() == n + 1
+    assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() for t in (start, end)) and start.numel() == end.numel()
+    d = data.device.index
+    with _on(d, stream):
+        s = _stream_ptr(stream)
+        list_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
+        if not n:
+            return torch.empty(0, dtype=torch.uint8, device=data.device), torch.zeros(1, dtype=torch.int64, device=data.device), list_off
+        npieces = int((first[-1] - first[0]).item()) + (n if gaps else 0)
+        if not start.numel():                      # (the entries take no null array, even where the lists are empty)
+            start = end = torch.zeros(1, dtype=torch.int32, device=data.device)
+        length = torch.empty(max(npieces, 1), dtype=torch.int32, device=data.device)
+        src = torch.empty(max(npieces, 1), dtype=torch.int64, device=data.device)
+        piece_off = torch.zeros(npieces + 1, dtype=torch.int64, device=data.device)
+        _check(_L.rrx_pieces_sizes(d, _ptr(offsets), n, trim, _ptr(first), _ptr(start), _ptr(end), PIECES_GAPS if gaps else PIECES_MATCHES, _ptr(list_off),
+                                   _ptr(length), _ptr(src), s))
+        if npieces:
+            torch.cumsum(length[:npieces].to(torch.int64) & 0xFFFFFFFF, dim=0, out=piece_off[1:])
+        out = torch.empty(int(piece_off[-1].item()), dtype=torch.uint8, device=data.device)
+        _check(_L.rrx_pieces_fill(d, _ptr(data), _ptr(src), _ptr(piece_off), npieces, _ptr(out), s))
+    return out, piece_off, list_off
 
 
 class Match:
@@ -801,6 +845,64 @@ class RRegex:
             s = _stream_ptr(stream)
             return self._replace_one_call(items.data.device, items.num_items, int(cap) if cap is not None else items.data.numel(),
                                           lambda f, out, cp, tot: _L.rrx_replace_all_longest_items(self._h, items._h, rep, len(rep), f, out, cp, tot, s))
+
+    def _pieces_one_call(self, dev, n, nbytes, cap, pieces_cap, call):
+        """A one-call pieces entry, repeated with the exact sizes if a cap was too small -> (out, piece_off[npieces + 1], list_off[n + 1])."""
+        import torch
+        cap = int(cap) if cap is not None else nbytes
+        pieces_cap = int(pieces_cap) if pieces_cap is not None else 2 * n
+        list_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        while True:
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            piece_off = torch.empty(pieces_cap + 1, dtype=torch.int64, device=dev)
+            npieces, total = C.c_size_t(0), C.c_size_t(0)
+            _check(call(_ptr(list_off), _ptr(piece_off), pieces_cap, _ptr(out), cap, C.byref(npieces), C.byref(total)))
+            if npieces.value <= pieces_cap and total.value <= cap:
+                break
+            cap, pieces_cap = max(cap, total.value), max(pieces_cap, npieces.value)
+        return out[:total.value], piece_off[:npieces.value + 1], list_off
+
+    def extract_all_longest_extents(self, data, offsets, trim=0, cap=None, pieces_cap=None, stream=None):
+        """regexp_extract_all on a string column (rrx_extract_all_longest_extents): EVERY LEFTMOST-LONGEST match of item i =
+        data[offsets[i] : offsets[i+1] - trim] as a list<binary> column -> (out uint8, piece_off int64[npieces + 1], list_off
+        int64[n + 1]): the matches of item i are the pieces list_off[i] .. list_off[i + 1], piece p = out[piece_off[p] :
+        piece_off[p + 1]] - [x.group() for x in re.finditer(p, item)].  cap / pieces_cap: bytes and pieces to provide for at first
+        (default: the size of `data`, two per item); the call is repeated with the exact sizes if the column is larger."""
+        import torch
+        n = offsets.numel() - 1
+        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+        d, b, o = data.device.index, _ptr(data), C.c_void_p(offsets.data_ptr())
+        with _on(d, stream):
+            s = _stream_ptr(stream)
+            return self._pieces_one_call(data.device, n, data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
+                                         _L.rrx_extract_all_longest_extents(self._h, d, b, o, n, trim, lo, po, pc, out, cp, npc, tot, s))
+
+    def extract_all_longest_items(self, items, cap=None, pieces_cap=None, stream=None):
+        """The same for an indexed batch (rrx_extract_all_longest_items)."""
+        with _on(items.device, stream):
+            s = _stream_ptr(stream)
+            return self._pieces_one_call(items.data.device, items.num_items, items.data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
+                                         _L.rrx_extract_all_longest_items(self._h, items._h, lo, po, pc, out, cp, npc, tot, s))
+
+    def split_longest_extents(self, data, offsets, trim=0, cap=None, pieces_cap=None, stream=None):
+        """split on a string column (rrx_split_longest_extents): what lies between the leftmost-longest matches of every item, one
+        piece more than it has matches, in the shape extract_all_longest_extents returns - re.split(p, item) for a pattern without
+        groups; the separators (`trim`) are not copied."""
+        import torch
+        n = offsets.numel() - 1
+        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+        d, b, o = data.device.index, _ptr(data), C.c_void_p(offsets.data_ptr())
+        with _on(d, stream):
+            s = _stream_ptr(stream)
+            return self._pieces_one_call(data.device, n, data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
+                                         _L.rrx_split_longest_extents(self._h, d, b, o, n, trim, lo, po, pc, out, cp, npc, tot, s))
+
+    def split_longest_items(self, items, cap=None, pieces_cap=None, stream=None):
+        """The same for an indexed batch (rrx_split_longest_items)."""
+        with _on(items.device, stream):
+            s = _stream_ptr(stream)
+            return self._pieces_one_call(items.data.device, items.num_items, items.data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
+                                         _L.rrx_split_longest_items(self._h, items._h, lo, po, pc, out, cp, npc, tot, s))
 
     def match_string(self, data, stream=None):
         """ONE device-resident string of any length (regex.h:156-159); '\n' is an ordinary character.  -> bool"""

@@ -333,6 +333,24 @@ int replace_sizes(const uint64_t *off, size_t nitems, uint32_t trim, const uint6
 int replace_fill(const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim, const uint64_t *first, const uint32_t *match_end,
                  const uint32_t *pos, const uint8_t *rep, uint32_t rep_len, const uint64_t *out_off, uint8_t *out, void *stream);
 
+// ---- regexp_extract_all / split on explicit items, from a match list: kernels_pieces_items.hip
+// Items and lists as for replace_sizes.  The PIECES of item i are its matches (gaps == false: m of them) or what lies between them
+// (gaps == true: m + 1, the stretch before the first match, between two matches, behind the last), every start and end clamped into
+// the item and behind the previous match's end, so that a piece lies inside its item whatever the list holds.
+// pieces_sizes (a lane per item): list_off[i] = the item's first piece (first[i] - first[0], + i with gaps), all nitems + 1 words;
+// for every piece piece_len[p] = its length saturated at ~0u and piece_src[p] = off[i] + its start, exactly the slots 0 .. npieces - 1.
+// too_long != nullptr: *too_long = 1 (a plain store) if some piece has 2^30 bytes or more - what scan_counts cannot carry.
+// pieces_fill: out[piece_off[p] + r] = bytes[piece_src[p] + r], r < piece_off[p + 1] - piece_off[p]: exactly the bytes
+// out[piece_off[0] .. piece_off[npieces]), no byte of `bytes` outside a piece read; `bytes` and `out` may sit at any address, out may
+// be null when nothing can be written.  It knows neither items nor matches: any ascending piece_off and any piece_src will do.  The
+// output range is cut into chunks of kPiecesChunk bytes (at dword-aligned addresses) that the waves of a FIXED grid of
+// kPiecesMaxBlocks workgroups take grid-stride: the output's size is on the device.
+constexpr uint32_t kPiecesChunk = 4096;          // bytes of output per wave and turn of its chunk loop: 16 sweeps of 256 bytes
+constexpr size_t kPiecesMaxBlocks = kReplaceMaxBlocks;
+int pieces_sizes(const uint64_t *off, size_t nitems, uint32_t trim, const uint64_t *first, const uint32_t *match_start, const uint32_t *match_end,
+                 bool gaps, uint64_t *list_off, uint32_t *piece_len, uint64_t *piece_src, uint32_t *too_long, void *stream);
+int pieces_fill(const uint8_t *bytes, const uint64_t *piece_src, const uint64_t *piece_off, size_t npieces, uint8_t *out, void *stream);
+
 // ---- one long string on the plain DFA: kernels_long.hip
 // One long string (regex.h:156-159 consumes it byte by byte): the string is cut into chunks, every chunk is stepped
 // from EVERY table state at once (lane = (chunk, start state); the lanes of a chunk read the same text), which yields

@@ -1,5 +1,5 @@
 // items.cpp — explicit items (an offsets array: rrx_match_extents / rrx_contains_extents / rrx_search_extents / rrx_search_all_extents* /
-// rrx_search_longest_extents / rrx_search_all_longest_extents* / rrx_replace_*, and rrx_items, the batch indexed once)
+// rrx_search_longest_extents / rrx_search_all_longest_extents* / rrx_replace_* / rrx_pieces_*, and rrx_items, the batch indexed once)
 // and single strings (rrx_match_string, rrx_match_cstr).
 #include <algorithm>
 #include <cstring>
@@ -526,6 +526,116 @@ int rrx_replace_all_longest_items(const rrx_regex *re, const rrx_items *it, cons
                                   size_t cap, size_t *total, void *stream) {
     if (!re || !it || !total || !d_out_off || (rep_len && !rep) || (it->nitems && cap && !d_out)) return fail(RRX_ERR_ARG, "null argument");
     return replace_all_longest_one_call(re, batch_of(it), rep, rep_len, d_out_off, d_out, cap, total, stream);
+}
+
+// regexp_extract_all / split from a match list (kernels_pieces_items.hip): the pieces of every item as a list<binary> column.  The
+// generic pair takes no regex, knows nothing on the host and reads nothing back.
+int rrx_pieces_sizes(int device, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint64_t *d_first, const uint32_t *d_start,
+                     const uint32_t *d_end, int mode, uint64_t *d_list_off, uint32_t *d_piece_len, uint64_t *d_piece_src, void *stream) {
+    if (mode != RRX_PIECES_MATCHES && mode != RRX_PIECES_GAPS) return fail(RRX_ERR_ARG, "mode is neither RRX_PIECES_MATCHES nor RRX_PIECES_GAPS");
+    if (nitems && (!d_off || !d_first || !d_start || !d_end || !d_list_off || !d_piece_len || !d_piece_src)) return fail(RRX_ERR_ARG, "null argument");
+    if (!nitems) return RRX_OK;
+    HIP_TRY(hipSetDevice(device));
+    return launched(dev::pieces_sizes(d_off, nitems, trim, d_first, d_start, d_end, mode == RRX_PIECES_GAPS, d_list_off, d_piece_len, d_piece_src, nullptr,
+                                      stream),
+                    "pieces_sizes launch");
+}
+int rrx_pieces_fill(int device, const void *d_bytes, const uint64_t *d_piece_src, const uint64_t *d_piece_off, size_t npieces, void *d_out, void *stream) {
+    if (npieces && (!d_piece_src || !d_piece_off)) return fail(RRX_ERR_ARG, "null argument");
+    if (!npieces) return RRX_OK;
+    HIP_TRY(hipSetDevice(device));
+    return launched(dev::pieces_fill(static_cast<const uint8_t *>(d_bytes), d_piece_src, d_piece_off, npieces, static_cast<uint8_t *>(d_out), stream),
+                    "pieces_fill launch");
+}
+// The pieces of every leftmost-longest match list, in one call (replace_all_longest_one_call's shape): count + scan and fill into
+// match arrays of the call's own, then sizes, a second scan (the piece lengths into the piece offsets - the caller's array if it
+// holds them, one of the call's own otherwise: the total is exact either way) and - if both caps hold - the bytes.  The number of
+// pieces follows from the number of matches on the host.  The sizes kernel raises a device word where a piece has 2^30 bytes or more.
+static int pieces_all_longest_one_call(const rrx_regex *re, const ItemBatch &b, bool gaps, uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap,
+                                       void *d_out, size_t cap, size_t *npieces, size_t *total, void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
+    *npieces = *total = 0;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = search_all_longest_lanes(re, batch_of(device, bytes, off, 0, trim), {}, nullptr, nullptr, nullptr, nullptr, 0, stream);   // (the tables, the device)
+    if (rc) return rc;
+    if (!nitems) {
+        HIP_TRY(hipMemsetAsync(d_list_off, 0, sizeof(uint64_t), st));
+        HIP_TRY(hipMemsetAsync(d_piece_off, 0, sizeof(uint64_t), st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return RRX_OK;
+    }
+    LongestCounts c;
+    DeviceArray<uint64_t> d_first;
+    hipError_t he = d_first.alloc(device, (nitems + 1) * sizeof(uint64_t));
+    if (he != hipSuccess) return hip_fail(he, "hipMalloc(pieces prefix)");
+    size_t nmatches = 0;
+    rc = search_all_longest_count_scan(re, b, c, d_first, &nmatches, stream);
+    if (rc) return rc;
+    const size_t np = nmatches + (gaps ? nitems : 0);
+    *npieces = np;
+    // (one word more than the lists need: the generic kernels are never handed a null array; the last word of d_len is the flag)
+    DeviceArray<uint32_t> d_start, d_end, d_len;
+    DeviceArray<uint64_t> d_src, d_sums, d_own_off;
+    he = d_start.alloc(device, (nmatches + 1) * sizeof(uint32_t));
+    if (he == hipSuccess) he = d_end.alloc(device, (nmatches + 1) * sizeof(uint32_t));
+    if (he == hipSuccess) he = d_len.alloc(device, (np + 2) * sizeof(uint32_t));
+    if (he == hipSuccess) he = d_src.alloc(device, (np + 1) * sizeof(uint64_t));
+    if (he == hipSuccess) he = d_sums.alloc(device, dev::scan_scratch_words(np) * sizeof(uint64_t));
+    if (he == hipSuccess && np > pieces_cap) he = d_own_off.alloc(device, (np + 1) * sizeof(uint64_t));
+    if (he != hipSuccess) return hip_fail(he, "hipMalloc(pieces lists)");
+    uint64_t *piece_off = np > pieces_cap ? (uint64_t *)d_own_off : d_piece_off;
+    if (nmatches) {
+        rc = search_all_longest_lanes(re, b, {c.marks, c.nwords}, nullptr, d_first, d_start, d_end, nmatches, stream);
+        if (rc) return rc;
+    }
+    uint32_t *d_flag = d_len + np + 1;
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st));
+    int le = dev::pieces_sizes(off, nitems, trim, d_first, d_start, d_end, gaps, d_list_off, d_len, d_src, d_flag, stream);
+    if (!le) le = dev::scan_counts(d_len, piece_off, d_sums, np, stream);       // piece_off[np] = total
+    if (le) return hip_fail((hipError_t)le, "pieces sizes and scan launch");
+    he = hipMemsetAsync(piece_off, 0, sizeof(uint64_t), st);                     // the scan marks entry 0 as a stripe start: not here
+    uint64_t tot = 0;
+    uint32_t flag = 0;
+    if (he == hipSuccess) he = hipMemcpyAsync(&tot, piece_off + np, sizeof tot, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return hip_fail(he, "pieces scan");
+    if (flag) return fail(RRX_ERR_UNSUPPORTED, "a piece of 2^30 bytes or more: use rrx_search_all_longest_extents and the two passes rrx_pieces_sizes / _fill");
+    *total = (size_t)tot;
+    if (np <= pieces_cap && tot && tot <= cap) {                                 // a column beyond either cap: not a byte of it is written
+        le = dev::pieces_fill(bytes, d_src, piece_off, np, static_cast<uint8_t *>(d_out), stream);
+        if (le) return hip_fail((hipError_t)le, "pieces_fill launch");
+        he = hipStreamSynchronize(st);
+        if (he != hipSuccess) return hip_fail(he, "pieces fill");
+    }
+    return RRX_OK;
+}
+static bool pieces_args_ok(const void *handle, const uint64_t *d_off, size_t nitems, const uint64_t *d_list_off, const uint64_t *d_piece_off, const void *d_out,
+                           size_t cap, const size_t *npieces, const size_t *total) {
+    return handle && npieces && total && d_list_off && d_piece_off && !(nitems && (!d_off || (cap && !d_out)));
+}
+int rrx_extract_all_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                    uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap, void *d_out, size_t cap, size_t *npieces, size_t *total,
+                                    void *stream) {
+    if (!pieces_args_ok(re, d_off, nitems, d_list_off, d_piece_off, d_out, cap, npieces, total)) return fail(RRX_ERR_ARG, "null argument");
+    return pieces_all_longest_one_call(re, batch_of(device, d_bytes, d_off, nitems, trim), false, d_list_off, d_piece_off, pieces_cap, d_out, cap, npieces, total,
+                                       stream);
+}
+int rrx_extract_all_longest_items(const rrx_regex *re, const rrx_items *it, uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap, void *d_out,
+                                  size_t cap, size_t *npieces, size_t *total, void *stream) {
+    if (!it || !pieces_args_ok(re, it->d_off, it->nitems, d_list_off, d_piece_off, d_out, cap, npieces, total)) return fail(RRX_ERR_ARG, "null argument");
+    return pieces_all_longest_one_call(re, batch_of(it), false, d_list_off, d_piece_off, pieces_cap, d_out, cap, npieces, total, stream);
+}
+int rrx_split_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, uint64_t *d_list_off,
+                              uint64_t *d_piece_off, size_t pieces_cap, void *d_out, size_t cap, size_t *npieces, size_t *total, void *stream) {
+    if (!pieces_args_ok(re, d_off, nitems, d_list_off, d_piece_off, d_out, cap, npieces, total)) return fail(RRX_ERR_ARG, "null argument");
+    return pieces_all_longest_one_call(re, batch_of(device, d_bytes, d_off, nitems, trim), true, d_list_off, d_piece_off, pieces_cap, d_out, cap, npieces, total,
+                                       stream);
+}
+int rrx_split_longest_items(const rrx_regex *re, const rrx_items *it, uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap, void *d_out, size_t cap,
+                            size_t *npieces, size_t *total, void *stream) {
+    if (!it || !pieces_args_ok(re, it->d_off, it->nitems, d_list_off, d_piece_off, d_out, cap, npieces, total)) return fail(RRX_ERR_ARG, "null argument");
+    return pieces_all_longest_one_call(re, batch_of(it), true, d_list_off, d_piece_off, pieces_cap, d_out, cap, npieces, total, stream);
 }
 
 // One device-resident string of any length.  Long strings take the chunk-map path when the automaton has a small

@@ -20,6 +20,14 @@ items (offsets = the line starts, trim 1: the '\\n' is the separator):
                   alternating inside one process.  The parent has no such entry and plays no part: one child per text, this tree
                   alone; the lines and a summary (fill as a share of the copy's rate) go to `--out` as well.
 
+  pieces          the list<binary> columns of extract_all and split (kernels_pieces_items.hip): per launch a device-to-device copy of
+                  the column's bytes, rrx_replace_matches_fill with rep_len 0, rrx_pieces_fill on GAPS - which writes the identical
+                  bytes: this pair is the A/B -, rrx_pieces_fill on MATCHES, rrx_pieces_sizes (GAPS) and both one-call forms, the
+                  seven alternating inside one process, in three rounds of `--launches` launches: the margin of the A/B is the
+                  baseline's own spread, min to max of its three medians.  Per text one child, this tree alone; a fourth child
+                  runs the SKEWED batch: the URL text (a quarter longer) whose first 64 items are merged lines of 16 MiB each - for
+                  replace's fill one wave's work, which is why that child makes two rounds of two launches only.
+
 The parent's side runs from a second checkout under .oldtree/ (git archive <commit> | tar -x -C .oldtree; build there): per text
 four children - parent, tree, parent, tree -, a fresh process each; device events around every launch (every sweep of slices),
 median and spread of `--launches` launches (at least twelve) after warm-up.  A child that fails ends the run: nothing more is
@@ -28,6 +36,7 @@ between its two medians and its own spread - and whether each of the tree's medi
 
     python tools/probe/item_lanes_rate.py --entry search [--old .oldtree] [--launches 15] [--scale 1.0]
     python tools/probe/item_lanes_rate.py --entry replace [--launches 15] [--scale 1.0] [--out profiles/replace_items_rate.txt]
+    python tools/probe/item_lanes_rate.py --entry pieces [--launches 15] [--scale 1.0] [--out profiles/pieces_items_rate.txt]
 """
 import argparse
 import json
@@ -38,12 +47,15 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CONFIGS = (("url", "U2", 1 << 30), ("email", "EMAIL", 1 << 30), ("kwlog", "K1000C", 1 << 30))
-ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "replace")
+ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "replace", "pieces")
+SKEW_ITEMS, SKEW_ITEM_BYTES = 64, 16 << 20     # the skewed batch of --entry pieces: its first 64 items are merged lines of 16 MiB or more
 YARDSTICK = {"search_all_longest": "search_all"}   # entries the parent lacks: what its side runs instead
 SLICE = 65535                                  # items per call of match / contains: one below kItemsStripesMin
 
 
 def child(tree, entry, kind, pkey, nbytes, launches):
+    skew = kind.endswith("-skewed")
+    kind = kind.split("-")[0]
     sys.path.insert(0, os.path.join(ROOT, "tools"))    # synth and bench.patterns(): the same text and patterns for both sides
     sys.path.insert(0, ROOT)
     import numpy as np
@@ -62,6 +74,8 @@ def child(tree, entry, kind, pkey, nbytes, launches):
     n = off.numel() - 1
     if entry == "replace":
         return replace_child(rr, r, kind, dev, off, n, launches)
+    if entry == "pieces":
+        return pieces_child(rr, r, kind, dev, off, launches, skew)
 
     if entry in ("match", "contains"):
         slices = [off[k:k + SLICE + 1] for k in range(0, n, SLICE)]
@@ -147,6 +161,114 @@ def replace_child(rr, r, kind, dev, off, n, launches):
         print(json.dumps(line), flush=True)
 
 
+def pieces_child(rr, r, kind, dev, off, launches, skew):
+    """copy, replace's fill at rep_len 0, pieces fill on GAPS and on MATCHES, pieces sizes and both one-call forms, alternating."""
+    import ctypes as C
+    import torch
+    L, s, nbytes = rr._L, rr._stream_ptr(None), int(dev.numel())
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    rounds = 3
+    if skew:                                   # the first SKEW_ITEMS items: the lines up to the first line start at or behind k * SKEW_ITEM_BYTES
+        cuts = torch.searchsorted(off, torch.arange(1, SKEW_ITEMS + 1, device="cuda") * SKEW_ITEM_BYTES)
+        assert int(cuts[-1]) < off.numel() - 1, "the text is too short for the skewed batch"
+        off = torch.cat([off[:1], off[cuts], off[int(cuts[-1]) + 1:]]).contiguous()
+        rounds, launches = 2, 2
+    n = off.numel() - 1
+    first, start, end = r.search_all_longest_extents_fused(dev, off, trim=1)
+    nmatches = int(start.numel())
+    if not nmatches:
+        start = end = torch.zeros(1, dtype=torch.int32, device="cuda")
+    copy_to = torch.empty_like(dev)
+    # replace at rep_len 0: the baseline of the A/B
+    length, pos = torch.empty(n, dtype=torch.int32, device="cuda"), torch.empty(max(nmatches, 1), dtype=torch.int32, device="cuda")
+    rr._check(L.rrx_replace_matches_sizes(0, ptr(off), n, 1, ptr(first), ptr(start), ptr(end), 0, ptr(length), ptr(pos), s))
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    torch.cumsum(length.to(torch.int64), dim=0, out=out_off[1:])
+    rep_out = torch.empty(int(out_off[-1]), dtype=torch.uint8, device="cuda")
+    replace_fill = lambda: rr._check(L.rrx_replace_matches_fill(0, ptr(dev), ptr(off), n, 1, ptr(first), ptr(end), ptr(pos), None, 0, ptr(out_off), ptr(rep_out), s))
+    # the pieces of both modes
+    col = {}
+    for mode, name in ((1, "gaps"), (0, "matches")):
+        npieces = nmatches + (n if mode else 0)
+        list_off = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+        plen, psrc = torch.empty(max(npieces, 1), dtype=torch.int32, device="cuda"), torch.empty(max(npieces, 1), dtype=torch.int64, device="cuda")
+        sizes = lambda mode=mode, list_off=list_off, plen=plen, psrc=psrc: rr._check(L.rrx_pieces_sizes(0, ptr(off), n, 1, ptr(first), ptr(start), ptr(end), mode,
+                                                                                                         ptr(list_off), ptr(plen), ptr(psrc), s))
+        sizes()
+        poff = torch.zeros(npieces + 1, dtype=torch.int64, device="cuda")
+        torch.cumsum(plen[:npieces].to(torch.int64), dim=0, out=poff[1:])
+        out = torch.empty(max(int(poff[-1]), 1), dtype=torch.uint8, device="cuda")
+        fill = lambda psrc=psrc, poff=poff, npieces=npieces, out=out: rr._check(L.rrx_pieces_fill(0, ptr(dev), ptr(psrc), ptr(poff), npieces, ptr(out), s))
+        one_list, one_poff, one_out = torch.empty_like(list_off), torch.empty_like(poff), torch.empty_like(out)
+        npc, tot = C.c_size_t(0), C.c_size_t(0)
+        fn = L.rrx_split_longest_extents if mode else L.rrx_extract_all_longest_extents
+        one = lambda fn=fn, one_list=one_list, one_poff=one_poff, one_out=one_out, npieces=npieces, total=int(poff[-1]), npc=npc, tot=tot: rr._check(
+            fn(r._h, 0, ptr(dev), ptr(off), n, 1, ptr(one_list), ptr(one_poff), npieces, ptr(one_out), total, C.byref(npc), C.byref(tot), s))
+        col[name] = dict(npieces=npieces, total=int(poff[-1]), sizes=sizes, fill=fill, one=one, out=out, poff=poff, list_off=list_off, one_list=one_list,
+                         one_poff=one_poff, one_out=one_out, npc=npc, tot=tot)
+    calls = {"copy": lambda: copy_to.copy_(dev), "replace_fill": replace_fill, "gaps_fill": col["gaps"]["fill"], "matches_fill": col["matches"]["fill"],
+             "sizes": col["gaps"]["sizes"], "extract_one_call": col["matches"]["one"], "split_one_call": col["gaps"]["one"]}
+    for _ in range(1 if skew else 3):
+        for call in calls.values():
+            call()
+    torch.cuda.synchronize()
+    print("# %s%s: %d items, %d matches, warmed up" % (kind, "-skewed" if skew else "", n, nmatches), file=sys.stderr, flush=True)
+    total = col["gaps"]["total"]
+    assert total == int(out_off[-1]) and torch.equal(col["gaps"]["out"][:total], rep_out), "pieces fill on GAPS and replace's fill at rep_len 0 differ"
+    for c in col.values():
+        assert (c["npc"].value, c["tot"].value) == (c["npieces"], c["total"]) and torch.equal(c["one_out"], c["out"]) and torch.equal(c["one_poff"], c["poff"]) \
+            and torch.equal(c["one_list"], c["list_off"]), "a one-call form and the two passes differ"
+    meds = {k: [] for k in calls}
+    for _ in range(rounds):
+        ms = {k: [] for k in calls}
+        for _ in range(launches):
+            for k, call in calls.items():                   # alternating: every launch has the others right beside it
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(); call(); b.record()
+                b.synchronize()
+                ms[k].append(a.elapsed_time(b))
+        for k in calls:
+            meds[k].append(statistics.median(ms[k]))
+        print("# a round of %d launches done" % launches, file=sys.stderr, flush=True)
+    med = {k: statistics.median(v) for k, v in meds.items()}
+    line = {"config": kind + ("-skewed" if skew else ""), "entry": "pieces", "bytes": nbytes, "items": n, "matches": nmatches, "gaps_bytes": total,
+            "matches_bytes": col["matches"]["total"], "rounds": rounds, "launches": launches}
+    for k in calls:
+        line[k + "_ms"] = [round(x, 4) for x in meds[k]]
+    gbs = lambda nb, ms: nb / ms / 1e6
+    line["copy_GB/s"] = round(gbs(nbytes, med["copy"]), 1)                          # bytes copied (read and written once each)
+    for k, nb in (("replace_fill", total), ("gaps_fill", total), ("matches_fill", col["matches"]["total"])):
+        line[k + "_GB/s"] = round(gbs(nb, med[k]), 1)                               # bytes of the column written
+        line[k + "_share_of_copy"] = round(gbs(nb, med[k]) / gbs(nbytes, med["copy"]), 4)
+    line["gaps_fill_over_replace_fill"] = round(med["gaps_fill"] / med["replace_fill"], 4)
+    line["baseline_margin_ms"] = round(max(meds["replace_fill"]) - min(meds["replace_fill"]), 4)
+    line["gaps_fill_within_margin"] = med["gaps_fill"] <= max(meds["replace_fill"])
+    print(json.dumps(line), flush=True)
+
+
+def pieces_main(a):
+    """One child per text and one for the skewed batch, this tree alone; the lines to a.out as they come."""
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("tools/probe/item_lanes_rate.py --entry pieces --launches %d --scale %g: per call the medians [ms] of three rounds of launches (the\n"
+                "skewed batch: two rounds of two), device-event times, the seven calls alternating in one process per text; GB/s = bytes of the\n"
+                "column written (the fills) or copied (copy) per second; gaps_fill writes the bytes replace_fill writes: that pair is the A/B,\n"
+                "its margin the spread of replace_fill's own medians.\n" % (a.launches, a.scale))
+        skewed = ("url-skewed", "U2", SKEW_ITEMS * SKEW_ITEM_BYTES + (256 << 20))
+        for kind, pkey, nbytes in CONFIGS + (skewed,):
+            n = nbytes if kind.endswith("-skewed") else int(nbytes * a.scale) // 4096 * 4096
+            env = dict(os.environ)
+            env.pop("RRX_LIB", None)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", "pieces", "--launches", str(a.launches), "--child", ROOT, kind, pkey, str(n)],
+                               env=env, timeout=900, stdout=subprocess.PIPE, text=True)
+            sys.stdout.write(p.stdout)
+            sys.stdout.flush()
+            if p.returncode:                   # a fault or a time limit: nothing more is started on the device
+                raise SystemExit("child failed with %d: pieces %s" % (p.returncode, kind))
+            f.write(p.stdout)
+            f.flush()
+
+
 def replace_main(a):
     """One child per text, this tree alone; the lines and a summary to a.out."""
     lines = []
@@ -179,14 +301,18 @@ def main():
     ap.add_argument("--old", default=os.path.join(ROOT, ".oldtree"))
     ap.add_argument("--launches", type=int, default=15)
     ap.add_argument("--scale", type=float, default=1.0, help="corpus sizes times this (a quick run)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "replace_items_rate.txt"), help="--entry replace: where the lines and the summary go")
+    ap.add_argument("--out", default=None, help="--entry replace / pieces: where the lines and the summary go (default: profiles/<entry>_items_rate.txt)")
     ap.add_argument("--child", nargs=4, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
         tree, kind, pkey, nbytes = a.child
         return child(tree, a.entry, kind, pkey, int(nbytes), max(a.launches, 12))
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", a.entry + "_items_rate.txt")
     if a.entry == "replace":
         return replace_main(a)
+    if a.entry == "pieces":
+        return pieces_main(a)
     assert os.path.exists(os.path.join(a.old, "roaringregex_amd", "librrx.so")), "build the parent commit under %s first" % a.old
     for kind, pkey, nbytes in CONFIGS:
         n = int(nbytes * a.scale) // 4096 * 4096
