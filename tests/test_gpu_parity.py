@@ -8,6 +8,7 @@ import pytest
 import roaringregex_amd as rr
 from patterns import EMAIL, K1000, K1000_CONTAINS, KAT, U2, random_pattern, random_text
 from pyoracle import OracleError, OracleRegex
+from search_cases import _oracle_confirms_search
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -1493,41 +1494,6 @@ def _check_search(pattern, data, want_start, want_end, stripes=(0,)):
         bad = np.nonzero((s != want_start) | (e != want_end))[0]
         assert bad.size == 0, (pattern[:40], "stripe", corpus.stripe, "line", int(bad[0]), (int(s[bad[0]]), int(e[bad[0]])),
                                "want", (int(want_start[bad[0]]), int(want_end[bad[0]])))
-
-
-def _oracle_confirms_search(pattern, lines, first=None, every=None, seed=1, starts_per_match=10):
-    """Search results against the ORACLE's own compile of the pattern, not against a replay of the device's tables.  With
-    `contains` = the oracle's automaton of `.*(p).*` (`.` covers all 128 codes, Parser.cpp:106-109) and `o` that of p:
-      * a line reported without a match: `contains` rejects the whole line (no substring is accepted);
-      * a match [s, e) searched from position b: o accepts line[s:e]; `contains` rejects line[b:e-1] (no match ends earlier - a
-        complete check, one oracle run); no s' in a sample of [b, s) (always b, s-1, s-2) has line[s':e] accepted.
-    `first`: one (s, e) per line; `every`: the list of all matches per line, each searched from the end of the one before."""
-    rng = random.Random(seed)
-    o, contains = OracleRegex(pattern), OracleRegex(".*(" + pattern + ").*")
-
-    def confirm(ln, b, s, e):
-        assert b <= s <= e <= len(ln), (pattern[:30], b, s, e)
-        assert o.accepts(ln[s:e].decode("latin-1")), (pattern[:30], "not a match", s, e)
-        if e - 1 >= b:
-            assert not contains.accepts(ln[b:e - 1].decode("latin-1")), (pattern[:30], "a match ends before", e)
-        for s2 in {b, s - 1, s - 2} | {rng.randrange(b, s) for _ in range(starts_per_match) if s > b}:
-            if b <= s2 < s:
-                assert not o.accepts(ln[s2:e].decode("latin-1")), (pattern[:30], "an earlier start", s2, "for", (s, e))
-
-    for i, ln in enumerate(lines):
-        if first is not None:
-            s, e = first[i]
-            if e < 0:
-                assert not contains.accepts(ln.decode("latin-1")), (pattern[:30], "line", i, "has a match")
-            else:
-                confirm(ln, 0, s, e)
-        if every is not None:
-            b = 0
-            for s, e in every[i]:
-                confirm(ln, b, s, e)
-                b = e if e > s else e + 1                       # (an empty match: the search moves on by one byte)
-            if b <= len(ln):
-                assert not contains.accepts(ln[b:].decode("latin-1")), (pattern[:30], "line", i, "has a further match after", b)
 
 
 def test_search_corpus_short_lines_against_the_oracle():
