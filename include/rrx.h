@@ -418,7 +418,7 @@ int rrx_search_all_longest_items(const rrx_regex *re, const rrx_items *items, ui
  * new column (d_out_off[nitems + 1], d_out).  Item i is t = d_bytes[d_off[i] .. d_off[i+1] - trim), empty where trim exceeds its
  * length.  Its matches (s_0,e_0) ... (s_{m-1},e_{m-1}) are in order, s_0 >= 0, e_k >= s_k, s_{k+1} >= e_k, e_{m-1} <= length; the
  * output item is t[0:s_0] + R + t[e_0:s_1] + R + ... + R + t[e_{m-1}:], R the replacement: rep_len >= 0 literal bytes, no group
- * references (the engine has no captures).  An empty match inserts R at its position (a* on "baab" with "<>": "<>b<><>b<>"), an
+ * references (the engine's only capture is rrx_group's top-level group span).  An empty match inserts R at its position (a* on "baab" with "<>": "<>b<><>b<>"), an
  * item without matches is copied verbatim, the `trim` separator bytes are never copied: the output column has no separators.  This
  * is Python's re.sub(p, lambda m: R, t) for the list re.finditer names.
  * THE MATCH LIST is the shape every rrx_search_all* one-call form returns (and the two-pass forms once the caller's prefix has one
@@ -520,6 +520,72 @@ int rrx_split_longest_extents(const rrx_regex *re, int device, const void *d_byt
                               size_t *total, void *stream);
 int rrx_split_longest_items(const rrx_regex *re, const rrx_items *items, uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap,
                             void *d_out, size_t cap, size_t *npieces, size_t *total, void *stream);
+
+/* regexp_extract with a CAPTURE GROUP on a string column: where, inside the leftmost-longest match of every item, does one
+ * TOP-LEVEL group of the pattern sit.  The pattern is a concatenation P = A (B) C and the wanted group is (B); A and C may be absent,
+ * parentheses inside A, B and C are plain grouping.  regexp_extract(col, 'https?://([^/]+)/.*', 1) is group 1 of that pattern.
+ * SEMANTICS.  For item t let [s, e) be its leftmost-longest match under P, exactly what rrx_search_longest_extents reports.  Then
+ *   i = the LARGEST offset in [s, e] such that A accepts t[s:i) and BC accepts t[i:e)     (A absent: i = s),
+ *   j = the LARGEST offset in [i, e] such that B accepts t[i:j) and C accepts t[j:e)      (C absent: j = e),
+ * and the group is [i, j), relative to the item start; no match: 0xFFFFFFFF in both words.  "Accepts" is the reference's whole-string
+ * acceptance (regex.h:156-162), as in every other entry.  This is the longest-match rule applied to the prefix as a whole, then to
+ * the group: the natural continuation of the leftmost-longest rule, and what a user expects wherever the split is unambiguous.  It
+ * is NOT POSIX's subexpression-by-subexpression rule where A is itself ambiguous: (a|ab)(c|bcd)?(d*), group 3, on "abcd" - A =
+ * (a|ab)(c|bcd)? accepts all of "abcd" (a + bcd), so the answer here is [4,4); POSIX answers [3,4).  '\n', NUL and bytes >= 0x80 are
+ * ordinary text, as in rrx_search_longest_extents; LONG ITEMS follow the rule there (an item is searched as if it ended at its offset
+ * 0xFFFFFFFE).
+ * COMPILING.  `group` counts the unescaped '(' outside brackets, left to right from 1, nested ones too (as SQL does).  RRX_ERR_ARG:
+ * group is 0 or larger than the number of groups, unknown engine, null argument.  RRX_ERR_PATTERN: the whole pattern does not compile.
+ * RRX_ERR_UNSUPPORTED, with the reason in the error text: the selected group is not at nesting depth 1; it is directly followed by
+ * '*', '+', '?' or '{'; the top level holds a '|'; the group is empty, the parentheses do not pair up or a part does not compile on
+ * its own; one of the four tables below does not determinise within the state budget (16384 states), or the whole pattern has no
+ * leftmost-longest tables - so that no device entry can fail for that reason.  The pattern is split on the front end's own token
+ * vector (no substring is lexed again).  The handle holds the whole pattern as an ordinary regex (rrx_group_regex: for
+ * rrx_search_longest_*, contains and so on; it belongs to the handle, do not free it) and four tables in the DFA layout, each with
+ * state 0 dead and absorbing and class 0 leading there:                                                                              */
+#define RRX_PROGRAM_GROUP_A 21      /* A, anchored, forwards; 0 words where A is absent                                              */
+#define RRX_PROGRAM_GROUP_REV_BC 22 /* (B)C right to left, anchored; 0 words where A is absent (the first launch is skipped)         */
+#define RRX_PROGRAM_GROUP_B 23      /* B, anchored, forwards (always there; not launched where C is absent)                          */
+#define RRX_PROGRAM_GROUP_REV_C 24  /* C right to left, anchored; 0 words where C is absent                                          */
+/* rrx_group_part: the source text of part `which` (0 / 1 / 2 = A / B / C) into buf, at most cap bytes, no terminator; returns its
+ * length (0 for an absent part, and for a `which` other than the three).  rrx_group_program_words: the table `which` (one of the
+ * four kinds above) as rrx_program_words dumps a DFA.  Both are host only: for tests and error messages.
+ * THE DEVICE ENTRIES.  One lane-per-item kernel, "the longest split point", is launched twice: on (reverse (B)C, A) over [s, e] it
+ * gives i, on (reverse C, B) over [i, e] it gives j; a launch whose part is absent is skipped.  Each launch walks backwards from
+ * the stretch's end on the reverse table, leaving a MARK bit for every offset p whose rest t[p:end) the right-hand part accepts, then
+ * forwards from the stretch's start on the forward table: the last marked offset at which the left-hand part accepts is the answer.
+ * d_marks is rrx_search_all_longest_marks_words' buffer in its layout extended by one position, the stretch's end: the bit of
+ * absolute offset g of item i is bit (g - d_off[0]) & 31 of word ((g - d_off[0]) >> 5) + i; rrx_search_all_longest_marks_words
+ * (extent, nitems) words hold them for every extent >= d_off[nitems] - d_off[0].  It needs no clearing and holds nothing the caller can use
+ * afterwards; words at or beyond marks_words are never touched, marks_words < nitems + 1 is rejected (RRX_ERR_ARG), and d_marks may
+ * be null only when both A and C are absent (no launch).
+ * rrx_group_spans_*: from ANY span list (d_match_start, d_match_end: for example what rrx_search_longest_extents wrote for
+ * rrx_group_regex) to the group's spans.  The output arrays may be the same buffers as the input arrays.  A span that is not a match
+ * of P reports no match (where A or C is present: with both absent the span IS the group and is passed through); a start of
+ * 0xFFFFFFFF reports no match; spans are clamped into their item, so no byte outside an item is read whatever the list holds.
+ * rrx_extract_group_longest_*: rrx_search_longest_* on the whole pattern into the two group arrays, then the two launches in place.
+ * All four are fully asynchronous - no read-back, no scratch of their own, no event: once the handle's tables are on the device (its
+ * first call there) they can be captured into a graph.  Every one of the 2 x nitems result words is written; an item for which
+ * either step finds no split reports 0xFFFFFFFF in BOTH words.  nitems == 0 writes nothing and returns RRX_OK.  Null arguments give
+ * RRX_ERR_ARG, checked before any device call.  The empty language reports no match everywhere: two fills and no table.  Tables are
+ * placed as rrx_search_longest_extents places its two (LDS while a launch's pair fits 64 KiB, else - and under
+ * RRX_ENGINE_DFA_GLOBAL - HBM/L2).  The _items forms use the handle's bytes, offsets, item count, trim and device only.           */
+typedef struct rrx_group rrx_group;
+int rrx_group_compile(const char *pattern, int group, rrx_group **out);
+int rrx_group_compile_ex(const char *pattern, int group, int engine, rrx_group **out);
+void rrx_group_free(rrx_group *grp);
+const rrx_regex *rrx_group_regex(const rrx_group *grp);
+size_t rrx_group_part(const rrx_group *grp, int which, char *buf, size_t cap);
+size_t rrx_group_program_words(const rrx_group *grp, int which, uint32_t *out, size_t cap);
+int rrx_group_spans_extents(const rrx_group *grp, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                            const uint32_t *d_match_start, const uint32_t *d_match_end, uint32_t *d_marks, size_t marks_words,
+                            uint32_t *d_group_start, uint32_t *d_group_end, void *stream);
+int rrx_group_spans_items(const rrx_group *grp, const rrx_items *items, const uint32_t *d_match_start, const uint32_t *d_match_end,
+                          uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start, uint32_t *d_group_end, void *stream);
+int rrx_extract_group_longest_extents(const rrx_group *grp, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                      uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start, uint32_t *d_group_end, void *stream);
+int rrx_extract_group_longest_items(const rrx_group *grp, const rrx_items *items, uint32_t *d_marks, size_t marks_words,
+                                    uint32_t *d_group_start, uint32_t *d_group_end, void *stream);
 
 /* ONE device-resident string of any length (regex.h:156-159: operator++ consumes the whole string; '\n' and every
  * other byte are ordinary, a NUL or a byte >= 0x80 rejects).  d_accept[0] = 1 iff accepted.  Strings of 32 KiB and

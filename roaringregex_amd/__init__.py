@@ -26,6 +26,7 @@ PROGRAM_SAMPLED_DFA2 = 13
 PROGRAM_CONTAINS_DFA, PROGRAM_CONTAINS_DFA2 = 16, 17   # the contains table (rrx_contains_corpus) and its stride-2 form
 PROGRAM_SEARCH_STARTS, PROGRAM_SEARCH_ANCHORED = 19, 20  # the two tables of the leftmost-longest search (rrx_search_longest_extents)
 PROGRAM_CONTAINS_DFA2_ITEMS = 18                       # its stride-2 items form (rrx_contains_extents / rrx_contains_items, trim 1)
+PROGRAM_GROUP_A, PROGRAM_GROUP_REV_BC, PROGRAM_GROUP_B, PROGRAM_GROUP_REV_C = 21, 22, 23, 24   # the four tables of an RGroup (rrx_group_program_words)
 OPT_BACKGROUND_ORDER = 1
 OPT_UNITS_PER_WORKGROUP = 2
 OPT_SAMPLED_TABLE = 3
@@ -56,6 +57,8 @@ ABI_SYMBOLS = (
     "rrx_replace_matches_sizes", "rrx_replace_matches_fill", "rrx_replace_all_longest_extents", "rrx_replace_all_longest_items",
     "rrx_pieces_sizes", "rrx_pieces_fill", "rrx_extract_all_longest_extents", "rrx_extract_all_longest_items", "rrx_split_longest_extents",
     "rrx_split_longest_items",
+    "rrx_group_compile", "rrx_group_compile_ex", "rrx_group_free", "rrx_group_regex", "rrx_group_part", "rrx_group_program_words",
+    "rrx_group_spans_extents", "rrx_group_spans_items", "rrx_extract_group_longest_extents", "rrx_extract_group_longest_items",
 )
 
 
@@ -158,6 +161,16 @@ def _load():
         "rrx_extract_all_longest_items": (i32, [vp, vp, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
         "rrx_split_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
         "rrx_split_longest_items": (i32, [vp, vp, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
+        "rrx_group_compile": (i32, [C.c_char_p, i32, C.POINTER(vp)]),
+        "rrx_group_compile_ex": (i32, [C.c_char_p, i32, i32, C.POINTER(vp)]),
+        "rrx_group_free": (None, [vp]),
+        "rrx_group_regex": (vp, [vp]),
+        "rrx_group_part": (sz, [vp, i32, vp, sz]),
+        "rrx_group_program_words": (sz, [vp, i32, vp, sz]),
+        "rrx_group_spans_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, vp, sz, vp, vp, vp]),
+        "rrx_group_spans_items": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "rrx_extract_group_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, sz, vp, vp, vp]),
+        "rrx_extract_group_longest_items": (i32, [vp, vp, vp, sz, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1077,3 +1090,147 @@ class RRegex:
     @property
     def accepts_empty(self):
         return bool(_L.rrx_accepts_empty(self._h))
+
+
+class _BorrowedRRegex(RRegex):
+    """An RRegex over a handle that somebody else owns (RGroup.regex): never freed here, the owner kept alive."""
+
+    def __init__(self, handle, pattern, device, owner):
+        self.pattern, self.device, self._h, self._owner = pattern, device, C.c_void_p(handle), owner
+
+    def __del__(self):
+        self._h = None
+
+
+class RGroup:
+    """regexp_extract with a capture group on a string column (rrx_group): the pattern is a concatenation A(B)C and `group` selects
+    (B) - the unescaped '(' outside brackets are counted from 1, nested ones too; the selected one must be at the top level, not
+    repeated, and the top level must hold no '|' (RRegexError otherwise).  For every item the group's span lies inside the item's
+    LEFTMOST-LONGEST match [s, e): start = the largest i with A accepting item[s:i] and BC accepting item[i:e], end = the largest j
+    with B accepting item[i:j] and C accepting item[j:e].  RGroup(b"https?://([^/]+)/.*", 1) on b"see http://example.com/a/b" gives
+    [11, 22)."""
+
+    def __init__(self, pattern, group, engine=ENGINE_AUTO, device=0):
+        if isinstance(pattern, str):
+            pattern = pattern.encode("latin-1")
+        self.pattern, self.group, self.device = pattern, group, device
+        self._h = C.c_void_p()
+        _check(_L.rrx_group_compile_ex(pattern, group, engine, C.byref(self._h)))
+        self.regex = _BorrowedRRegex(_L.rrx_group_regex(self._h), pattern, device, self)   # the whole pattern: search_longest_*, contains_* ...
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _L is not None:
+            if getattr(self, "regex", None) is not None:
+                self.regex._h = None
+            _L.rrx_group_free(self._h)
+            self._h = None
+
+    @property
+    def parts(self):
+        """The source text of (A, B, C) as bytes; an absent part is b""."""
+        out = []
+        for which in range(3):
+            n = _L.rrx_group_part(self._h, which, None, 0)
+            buf = C.create_string_buffer(max(n, 1))
+            _L.rrx_group_part(self._h, which, buf, n)
+            out.append(buf.raw[:n])
+        return tuple(out)
+
+    def program(self, which):
+        """One of the four tables (PROGRAM_GROUP_A / _REV_BC / _B / _REV_C) in the DFA layout (numpy uint32), None for an absent part's."""
+        import numpy as np
+        n = _L.rrx_group_program_words(self._h, which, None, 0)
+        if not n:
+            return None
+        out = np.zeros(n, dtype=np.uint32)
+        _L.rrx_group_program_words(self._h, which, C.c_void_p(out.ctypes.data), n)
+        return out
+
+    @staticmethod
+    def _marks(data, n):
+        """The marks buffer of a batch of n items inside `data`, sized from data.numel() as the all-longest entries size theirs."""
+        import torch
+        words = _L.rrx_search_all_longest_marks_words(data.numel(), n)
+        return torch.empty(words, dtype=torch.int32, device=data.device), words
+
+    @staticmethod
+    def _check_batch(data, offsets):
+        import torch
+        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+
+    @staticmethod
+    def _outputs(n, device, out):
+        import torch
+        if out is not None:
+            assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() and t.numel() >= n for t in out)
+            return out
+        return torch.empty(n, dtype=torch.int32, device=device), torch.empty(n, dtype=torch.int32, device=device)
+
+    def spans_extents(self, data, offsets, match_start, match_end, trim=0, out=None, stream=None):
+        """From a span list - (match_start, match_end) int32 per item, relative to the item, as RRegex.search_longest_extents returns
+        it for self.regex - to the group's spans (rrx_group_spans_extents) -> (start, end) int32, (-1, -1) where the item has no match
+        or the span is not one.  out: the two result tensors; they may be match_start / match_end themselves.  Asynchronous."""
+        self._check_batch(data, offsets)
+        n = offsets.numel() - 1
+        d = data.device.index
+        with _on(d, stream):
+            start, end = self._outputs(n, data.device, out)
+            marks, words = self._marks(data, n)
+            _check(_L.rrx_group_spans_extents(self._h, d, _ptr(data), C.c_void_p(offsets.data_ptr()), n, trim, _ptr(match_start), _ptr(match_end),
+                                              _ptr(marks), words, _ptr(start), _ptr(end), _stream_ptr(stream)))
+        return start, end
+
+    def spans_items(self, items, match_start, match_end, out=None, stream=None):
+        """The same for an indexed batch (rrx_group_spans_items)."""
+        n = items.num_items
+        with _on(items.device, stream):
+            start, end = self._outputs(n, items.data.device, out)
+            marks, words = self._marks(items.data, n)
+            _check(_L.rrx_group_spans_items(self._h, items._h, _ptr(match_start), _ptr(match_end), _ptr(marks), words, _ptr(start), _ptr(end),
+                                            _stream_ptr(stream)))
+        return start, end
+
+    def extract_extents(self, data, offsets, trim=0, out=None, marks=None, stream=None):
+        """The group's span per item of a batch nobody has indexed, the search included (rrx_extract_group_longest_extents): item i =
+        data[offsets[i] : offsets[i+1] - trim] -> (start, end) int32, (-1, -1) where nothing is accepted.  Nothing is read back: with
+        `out` and `marks` (an int32 tensor of rrx_search_all_longest_marks_words words) given, the call can be captured into a graph."""
+        self._check_batch(data, offsets)
+        n = offsets.numel() - 1
+        d = data.device.index
+        with _on(d, stream):
+            start, end = self._outputs(n, data.device, out)
+            if marks is None:
+                marks = self._marks(data, n)[0]
+            _check(_L.rrx_extract_group_longest_extents(self._h, d, _ptr(data), C.c_void_p(offsets.data_ptr()), n, trim, _ptr(marks), marks.numel(),
+                                                        _ptr(start), _ptr(end), _stream_ptr(stream)))
+        return start, end
+
+    def extract_items(self, items, out=None, marks=None, stream=None):
+        """The same for an indexed batch (rrx_extract_group_longest_items)."""
+        n = items.num_items
+        with _on(items.device, stream):
+            start, end = self._outputs(n, items.data.device, out)
+            if marks is None:
+                marks = self._marks(items.data, n)[0]
+            _check(_L.rrx_extract_group_longest_items(self._h, items._h, _ptr(marks), marks.numel(), _ptr(start), _ptr(end), _stream_ptr(stream)))
+        return start, end
+
+    def extract_column(self, data, offsets, trim=0, stream=None):
+        """regexp_extract(col, pattern, group) as a column, written on the device -> (valid bool[n], out_offsets int64[n + 1], out_bytes
+        uint8): output item i = out_bytes[out_offsets[i] : out_offsets[i + 1]] is the group's text; an item without a match is invalid
+        and empty.  The spans (extract_extents), their lengths, a torch.cumsum, then rrx_pieces_fill.  Waits for the output's size."""
+        import torch
+        n = offsets.numel() - 1
+        d = data.device.index
+        with _on(d, stream):
+            start, end = self.extract_extents(data, offsets, trim=trim, stream=stream)
+            valid = start >= 0
+            out_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
+            if not n:
+                return valid, out_off, torch.empty(0, dtype=torch.uint8, device=data.device)
+            length = torch.where(valid, (end - start).to(torch.int64), torch.zeros((), dtype=torch.int64, device=data.device))
+            torch.cumsum(length, dim=0, out=out_off[1:])
+            src = (offsets[:n].to(torch.int64) + torch.where(valid, start, torch.zeros_like(start)).to(torch.int64)).contiguous()
+            out = torch.empty(int(out_off[-1].item()), dtype=torch.uint8, device=data.device)
+            _check(_L.rrx_pieces_fill(d, _ptr(data), _ptr(src), _ptr(out_off), n, _ptr(out), _stream_ptr(stream)))
+        return valid, out_off, out

@@ -316,6 +316,25 @@ int search_all_longest_extents_dfa(const SearchLongestDevice &p, bool in_global,
                                    uint32_t trim, uint32_t *marks, size_t marks_words, uint32_t *count, const uint64_t *first, uint32_t *match_start,
                                    uint32_t *match_end, size_t cap, void *stream);
 
+// ---- the span of a top-level capture group inside a known match, a lane per item: kernels_group_items.hip
+// The four plain tables of a pattern A(B)C split at its group (lower.hpp: lower_dfa, lower_dfa_reversed), one image: a = A and b = B
+// anchored forwards, rev_bc = (B)C and rev_c = C right to left, anchored; in each row 0 is dead and absorbing and class 0 leads
+// there (pack_group checks it).  The table of an absent part is empty (nstates = 0, null pointers) and never launched.
+struct GroupDevice {
+    DfaDevice a, rev_bc, b, rev_c;
+};
+// The longest split point: for item i = bytes[off[i] .. off[i+1] - trim) and the stretch [lo[i], hi[i]] of it (relative to the item,
+// clamped into it: no byte outside the item is read whatever the arrays hold), out[i] = the LARGEST x in [lo, hi] with item[lo, x)
+// accepted by `fwd` and item[x, hi), read right to left, accepted by `rev`; ~0u where there is none or lo[i] == ~0u, and then
+// on_none[i] = ~0u too (on_none may be null; it is left alone otherwise).  Every one of the nitems words of `out` is written with a
+// plain store.  lo, hi, out and on_none may be the same arrays: a lane reads its own entries before it writes them.  The backward
+// pass leaves a MARK bit for every offset p of the stretch with item[p, hi) accepted by rev: the bit of absolute offset g is bit
+// (g - off[0]) & 31 of word ((g - off[0]) >> 5) + i of `marks` - every word of an item's stretch stored, no other, none at or
+// beyond marks_words; search_all_longest_marks_words(extent, nitems) words hold them.  Placement (in_global) and long items as
+// search_longest_extents_dfa.
+int longest_split_dfa(const DfaDevice &rev, const DfaDevice &fwd, bool in_global, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
+                      const uint32_t *lo, const uint32_t *hi, uint32_t *marks, size_t marks_words, uint32_t *out, uint32_t *on_none, void *stream);
+
 // ---- regexp_replace on explicit items, from a match list: kernels_replace_items.hip
 // Item i = bytes[off[i] .. off[i+1] - trim); its matches are the slots first[i] .. first[i + 1] of match_start / match_end (relative
 // to the item, in order, not overlapping: what every search_all* launcher above leaves); R = `rep_len` literal bytes.  The output

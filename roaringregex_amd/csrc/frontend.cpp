@@ -132,6 +132,7 @@ struct Token {
     CharSet on;            // ATOM
     long m = 0, n = 0;     // REPEAT
     bool has_tail = false; // REPEAT: a second number was parsed ("{m?n}")
+    size_t at = 0, end = 0; // the token's bytes in the pattern: [at, end), an escaping backslash included (split_group)
 };
 
 class Lexer {
@@ -178,6 +179,7 @@ public:
             if (ch >= 0x80) throw PatternError("non-ASCII byte in pattern");
             if (!escaped && ch == '\\') { escaped = true; continue; }
             Token t{};
+            t.at = escaped ? cp - 1 : cp;
             switch (escaped ? 0 : ch) {
             case '[': t.kind = Token::ATOM; cp = bracket(cp, t.on); break;
             case '(': t.kind = Token::OPEN; break;
@@ -205,6 +207,7 @@ public:
             }
             default: t.kind = Token::ATOM; t.on = CharSet::single(ch); break;      // Parser.cpp:147-150
             }
+            t.end = cp + 1;
             toks.push_back(t);
             escaped = false;
         } while (++cp < ps);
@@ -404,6 +407,63 @@ RefAutomaton build_reference_automaton(const std::string &pattern) {
     Lexer lx(pattern);
     Machine m;
     return m.run(lx.run());
+}
+
+// The split works on the TOKENS of the whole pattern, never on substrings lexed again: Lexer::bracket looks at the distance to the
+// end of the pattern, and "" lexes to an atom, not to the empty word - which is why an absent A or C is a flag here and never a
+// compiled empty pattern.  A slice of the token vector goes through a Machine of its own; the top level of an admitted pattern is a
+// plain concatenation (no '|' at depth 0, no postfix operator on the group), so the three slices fold exactly as they do inside
+// the whole pattern and L(P) = L(A) L(B) L(C) (tests/test_group_items_lowering.py checks it against the oracle).
+GroupSplit split_group(const std::string &pattern, int group) {
+    if (pattern.find('\0') != std::string::npos) throw PatternError("NUL byte in pattern");
+    if (group <= 0) throw GroupArgError("group numbers start at 1");
+    const std::vector<Token> toks = Lexer(pattern).run();
+    { Machine whole; (void)whole.run(toks); }                     // (a pattern that does not compile: PatternError, before anything else)
+    GroupSplit g;
+    size_t open = toks.size(), close = toks.size();
+    int depth = 0, open_depth = 0;
+    bool top_alt = false, unbalanced = false;
+    for (size_t k = 0; k < toks.size(); k++) {
+        const Token &t = toks[k];
+        if (t.kind == Token::OPEN) {
+            depth++;
+            if (++g.groups == (uint32_t)group) { open = k; open_depth = depth; }
+        } else if (t.kind == Token::CLOSE) {
+            if (open < toks.size() && close == toks.size() && depth == open_depth) close = k;
+            if (--depth < 0) { unbalanced = true; depth = 0; }
+        } else if (t.kind == Token::ALT && depth == 0) top_alt = true;
+    }
+    if ((uint32_t)group > g.groups) throw GroupArgError("the pattern has " + std::to_string(g.groups) + " group(s), group " + std::to_string(group) + " was asked for");
+    if (unbalanced || depth != 0) throw GroupUnsupported("unbalanced parentheses: a group can only be told apart in a pattern whose parentheses pair up");
+    if (open_depth != 1)
+        throw GroupUnsupported("group " + std::to_string(group) + " is nested inside another group (depth " + std::to_string(open_depth) +
+                               "): only a top-level group A(B)C can be extracted");
+    if (top_alt) throw GroupUnsupported("the pattern has a '|' at its top level: A(B)C must be a plain concatenation");
+    if (close + 1 < toks.size()) {
+        const Token::Kind next = toks[close + 1].kind;
+        if (next == Token::STAR || next == Token::PLUS || next == Token::OPT || next == Token::REPEAT)
+            throw GroupUnsupported("group " + std::to_string(group) + " is directly followed by '" + pattern.substr(toks[close + 1].at, 1) +
+                                   "': a repeated group has no single span");
+    }
+    if (close == open + 1) throw GroupUnsupported("group " + std::to_string(group) + " is empty");
+    g.has_a = open > 0;
+    g.has_c = close + 1 < toks.size();
+    g.text[0] = pattern.substr(0, toks[open].at);
+    g.text[1] = pattern.substr(toks[open].end, toks[close].at - toks[open].end);
+    g.text[2] = pattern.substr(toks[close].end);
+    auto slice = [&](size_t from, size_t to) {
+        Machine m;
+        return m.run(std::vector<Token>(toks.begin() + (long)from, toks.begin() + (long)to));
+    };
+    try {
+        if (g.has_a) g.a = slice(0, open);
+        g.b = slice(open + 1, close);
+        if (g.has_c) g.c = slice(close + 1, toks.size());
+        g.bc = slice(open, toks.size());
+    } catch (const PatternError &e) {
+        throw GroupUnsupported(std::string("a part of the pattern does not compile on its own (") + e.what() + ")");
+    }
+    return g;
 }
 
 }  // namespace rrx

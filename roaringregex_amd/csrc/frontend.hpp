@@ -72,4 +72,20 @@ constexpr uint64_t kFrontEndBudget = (uint64_t)1 << 26;      // row pieces + dir
 // with our own where the reference has undefined behaviour (stack underflow, bytes >= 0x80, "{m" cut short).
 RefAutomaton build_reference_automaton(const std::string &pattern);
 
+// A pattern P = A (B) C split at its capture group number `group` (unescaped '(' outside brackets counted from 1, left to right,
+// nested ones too): the source text of the three parts and the automata of A, B, C and (B)C, each compiled from the slice of P's
+// own token vector.  A and C may be absent (has_a / has_c false: text empty, automaton empty); parentheses inside the parts are
+// plain grouping.  Throws PatternError where P does not compile, GroupArgError for a group number below 1 or beyond the pattern's
+// groups, GroupUnsupported where the group is not at nesting depth 1, is directly followed by * + ? or {, is empty, where the top
+// level holds a '|', the parentheses do not pair up, or a part does not compile on its own.
+struct GroupArgError : std::runtime_error { using std::runtime_error::runtime_error; };
+struct GroupUnsupported : std::runtime_error { using std::runtime_error::runtime_error; };
+struct GroupSplit {
+    bool has_a = false, has_c = false;
+    uint32_t groups = 0;                          // '(' tokens of the whole pattern
+    std::string text[3];                          // A, B, C
+    RefAutomaton a, b, c, bc;
+};
+GroupSplit split_group(const std::string &pattern, int group);
+
 }  // namespace rrx

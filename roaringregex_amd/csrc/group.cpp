@@ -1,0 +1,190 @@
+// group.cpp — rrx_group: a pattern A(B)C split at one top-level capture group (frontend.hpp: split_group), its four anchored tables,
+// and the entries that turn the leftmost-longest match of every item into the group's span (rrx_group_spans_* /
+// rrx_extract_group_longest_*): the longest split point (kernels_group_items.hip), launched once per part that is there.
+#include <cstring>
+
+#include "handles.hpp"
+
+using namespace rrx;
+
+// The whole pattern as an ordinary regex, the parts' source text, and the tables: a and rev_bc where A is there, rev_c where C is, b
+// always (an absent part's launch is skipped, its tables stay empty).  Everything a device entry could refuse for is settled at compile.
+struct rrx_group {
+    rrx_regex *whole = nullptr;
+    std::string text[3];                                 // A, B, C
+    bool has_a = false, has_c = false;
+    bool empty = false;                                  // the empty language: no match anywhere, no table
+    DfaProgram a, rev_bc, b, rev_c;
+    mutable std::mutex mu;
+    mutable std::map<int, OnDevice<dev::GroupDevice>> on_device;      // (under `mu`)
+    ~rrx_group() { delete whole; }
+    bool in_global() const { return whole->requested == RRX_ENGINE_DFA_GLOBAL; }
+    // The tables on `device`, uploaded once
+    int tables(int device, const dev::GroupDevice **out) const {
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = on_device.find(device);
+        if (it == on_device.end()) {
+            Image img;
+            OnDevice<dev::GroupDevice> t;
+            if (!pack_group(a, rev_bc, b, rev_c, img, t.d)) return fail(RRX_ERR_UNSUPPORTED, "group tables: row 0 of a table is not its dead row");
+            const hipError_t e = upload(device, img, t.mem);
+            if (e != hipSuccess) return hip_fail(e, "device table upload");
+            it = on_device.emplace(device, std::move(t)).first;
+        }
+        *out = &it->second.d;
+        return RRX_OK;
+    }
+};
+
+namespace {
+
+struct ItemBatch { int device; const uint8_t *bytes; const uint64_t *off; size_t nitems; uint32_t trim; };
+struct ItemMarks { uint32_t *words; size_t nwords; };
+
+const char *const kGroupArgError = "null argument, or marks_words below nitems + 1";
+// d_marks may be null only where no launch needs it: both A and C absent
+bool group_args_ok(const rrx_group *g, size_t nitems, const void *d_off, ItemMarks m, const uint32_t *d_start, const uint32_t *d_end) {
+    if (!g) return false;
+    if (!nitems) return true;
+    if (!d_off || !d_start || !d_end) return false;
+    return (!g->has_a && !g->has_c) || (m.words && m.nwords >= nitems + 1);
+}
+
+// From the spans in (in_start, in_end) to the group's spans in (d_start, d_end); the two pairs may be the same arrays.
+//   A there:  launch 1 on (reverse (B)C, A) over [s, e] -> i into d_start            A absent:  i = s, a copy
+//   C there:  launch 2 on (reverse C, B) over [i, e]    -> j into d_end              C absent:  j = e, a copy
+// An item without a split gets ~0u in the launch's own array and, through on_none, in the other one; launch 2 passes an item on
+// whose start is ~0u.  The copies come first: launch 1 reads e from in_end and may write ~0u into d_end.
+int group_spans(const rrx_group *g, const ItemBatch &b, const uint32_t *in_start, const uint32_t *in_end, ItemMarks m, uint32_t *d_start, uint32_t *d_end,
+                void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
+    hipStream_t st = (hipStream_t)stream;
+    if (!nitems) return RRX_OK;                          // (nothing to refuse an empty batch for: compile has settled the tables)
+    const dev::GroupDevice *t = nullptr;
+    if (!g->empty) {
+        const int rc = g->tables(device, &t);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipSetDevice(device));
+    if (g->empty) {
+        HIP_TRY(hipMemsetAsync(d_start, 0xff, nitems * sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(d_end, 0xff, nitems * sizeof(uint32_t), st));
+        return RRX_OK;
+    }
+    if (!g->has_a && d_start != in_start) HIP_TRY(hipMemcpyAsync(d_start, in_start, nitems * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (!g->has_c && d_end != in_end) HIP_TRY(hipMemcpyAsync(d_end, in_end, nitems * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (g->has_a) {
+        const int rc = launched(dev::longest_split_dfa(t->rev_bc, t->a, g->in_global(), bytes, off, nitems, trim, in_start, in_end, m.words, m.nwords, d_start,
+                                                       d_end, stream),
+                                "group split (A | BC) launch");
+        if (rc) return rc;
+    }
+    if (g->has_c) {
+        const uint32_t *lo = g->has_a ? d_start : in_start;
+        const int rc = launched(dev::longest_split_dfa(t->rev_c, t->b, g->in_global(), bytes, off, nitems, trim, lo, in_end, m.words, m.nwords, d_end, d_start,
+                                                       stream),
+                                "group split (B | C) launch");
+        if (rc) return rc;
+    }
+    return RRX_OK;
+}
+
+// rrx_search_longest_* on the whole pattern into the group arrays, then the launches in place
+int group_extract(const rrx_group *g, const ItemBatch &b, ItemMarks m, uint32_t *d_start, uint32_t *d_end, void *stream) {
+    if (!b.nitems) return RRX_OK;
+    const int rc = rrx_search_longest_extents(g->whole, b.device, b.bytes, b.off, b.nitems, b.trim, d_start, d_end, stream);
+    if (rc || g->empty) return rc;          // (the empty language: the search has filled both arrays)
+    return group_spans(g, b, d_start, d_end, m, d_start, d_end, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rrx_group_compile_ex(const char *pattern, int group, int engine, rrx_group **out) {
+    if (!pattern || !out) return fail(RRX_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (group <= 0) return fail(RRX_ERR_ARG, "group numbers start at 1");
+    rrx_regex *whole = nullptr;
+    const int rc = rrx_compile_ex(pattern, engine, &whole);                   // (RRX_ERR_PATTERN, an unknown engine, an automaton no engine takes)
+    if (rc) return rc;
+    std::unique_ptr<rrx_group> g(new rrx_group());
+    g->whole = whole;
+    try {
+        GroupSplit s = split_group(whole->pattern, group);
+        for (int k = 0; k < 3; k++) g->text[k] = s.text[k];
+        g->has_a = s.has_a;
+        g->has_c = s.has_c;
+        {
+            std::lock_guard<std::mutex> lock(whole->mu);
+            const int lrc = whole->build_search_longest();
+            if (lrc) return lrc;
+            g->empty = whole->search_longest.empty;
+        }
+        auto reduced = [](const RefAutomaton &a) { return reduce(trim(a)); };
+        bool ok = true;
+        if (s.has_a) ok = lower_dfa(reduced(s.a), kMaxSubsetStates, g->a) && lower_dfa_reversed(reduced(s.bc), kMaxSubsetStates, g->rev_bc);
+        if (ok && s.has_c) ok = lower_dfa(reduced(s.b), kMaxSubsetStates, g->b) && lower_dfa_reversed(reduced(s.c), kMaxSubsetStates, g->rev_c);
+        if (ok && !s.has_c) ok = lower_dfa(reduced(s.b), kMaxSubsetStates, g->b);      // (not launched: kept for rrx_group_program_words' B)
+        if (!ok) return fail(RRX_ERR_UNSUPPORTED, "a table of the split pattern (A, B, or the reverse of (B)C or C) does not determinise within the state budget");
+    } catch (const GroupArgError &e) {
+        return fail(RRX_ERR_ARG, e.what());
+    } catch (const GroupUnsupported &e) {
+        return fail(RRX_ERR_UNSUPPORTED, e.what());
+    } catch (const PatternError &e) {
+        return fail(RRX_ERR_PATTERN, e.what());
+    } catch (const BudgetError &e) {
+        return fail(RRX_ERR_UNSUPPORTED, e.what());
+    } catch (const std::exception &e) {
+        return fail(RRX_ERR_PATTERN, std::string("internal: ") + e.what());
+    }
+    *out = g.release();
+    return RRX_OK;
+}
+int rrx_group_compile(const char *pattern, int group, rrx_group **out) { return rrx_group_compile_ex(pattern, group, RRX_ENGINE_AUTO, out); }
+void rrx_group_free(rrx_group *grp) { delete grp; }
+const rrx_regex *rrx_group_regex(const rrx_group *grp) { return grp ? grp->whole : nullptr; }
+
+size_t rrx_group_part(const rrx_group *grp, int which, char *buf, size_t cap) {
+    if (!grp || which < 0 || which > 2) return 0;
+    const std::string &s = grp->text[which];
+    if (buf && cap) std::memcpy(buf, s.data(), s.size() < cap ? s.size() : cap);
+    return s.size();
+}
+size_t rrx_group_program_words(const rrx_group *grp, int which, uint32_t *out, size_t cap) {
+    if (!grp) return 0;
+    const DfaProgram *p = which == RRX_PROGRAM_GROUP_A ? &grp->a : which == RRX_PROGRAM_GROUP_REV_BC ? &grp->rev_bc
+                          : which == RRX_PROGRAM_GROUP_B ? &grp->b : which == RRX_PROGRAM_GROUP_REV_C ? &grp->rev_c : nullptr;
+    std::vector<uint32_t> w;
+    if (p && p->nstates) append_words(w, *p);
+    for (size_t i = 0; i < w.size() && i < cap; i++) out[i] = w[i];
+    return w.size();
+}
+
+int rrx_group_spans_extents(const rrx_group *grp, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                            const uint32_t *d_match_start, const uint32_t *d_match_end, uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start,
+                            uint32_t *d_group_end, void *stream) {
+    if (!group_args_ok(grp, nitems, d_off, {d_marks, marks_words}, d_group_start, d_group_end) || (nitems && (!d_match_start || !d_match_end)))
+        return fail(RRX_ERR_ARG, kGroupArgError);
+    return group_spans(grp, {device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim}, d_match_start, d_match_end, {d_marks, marks_words},
+                       d_group_start, d_group_end, stream);
+}
+int rrx_group_spans_items(const rrx_group *grp, const rrx_items *it, const uint32_t *d_match_start, const uint32_t *d_match_end, uint32_t *d_marks,
+                          size_t marks_words, uint32_t *d_group_start, uint32_t *d_group_end, void *stream) {
+    if (!it || !group_args_ok(grp, it->nitems, it->d_off, {d_marks, marks_words}, d_group_start, d_group_end) || (it->nitems && (!d_match_start || !d_match_end)))
+        return fail(RRX_ERR_ARG, kGroupArgError);
+    return group_spans(grp, {it->device, it->d_bytes, it->d_off, it->nitems, it->trim}, d_match_start, d_match_end, {d_marks, marks_words}, d_group_start,
+                       d_group_end, stream);
+}
+int rrx_extract_group_longest_extents(const rrx_group *grp, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                      uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start, uint32_t *d_group_end, void *stream) {
+    if (!group_args_ok(grp, nitems, d_off, {d_marks, marks_words}, d_group_start, d_group_end)) return fail(RRX_ERR_ARG, kGroupArgError);
+    return group_extract(grp, {device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim}, {d_marks, marks_words}, d_group_start, d_group_end, stream);
+}
+int rrx_extract_group_longest_items(const rrx_group *grp, const rrx_items *it, uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start,
+                                    uint32_t *d_group_end, void *stream) {
+    if (!it || !group_args_ok(grp, it->nitems, it->d_off, {d_marks, marks_words}, d_group_start, d_group_end)) return fail(RRX_ERR_ARG, kGroupArgError);
+    return group_extract(grp, {it->device, it->d_bytes, it->d_off, it->nitems, it->trim}, {d_marks, marks_words}, d_group_start, d_group_end, stream);
+}
+
+}  // extern "C"

@@ -1123,6 +1123,7 @@ static Reduced reversed(const Reduced &r) {
 bool search_dfas(const Reduced &r, uint32_t max_states, DfaProgram &fwd, DfaProgram &rev) {
     return subset_construct(r, max_states, true, fwd) && subset_construct(reversed(r), max_states, false, rev);
 }
+bool lower_dfa_reversed(const Reduced &r, uint32_t max_states, DfaProgram &rev) { return subset_construct(reversed(r), max_states, false, rev); }
 bool search_longest_dfas(const Reduced &r, uint32_t max_states, DfaProgram &starts, DfaProgram &anchored) {
     if (subset_construct(reversed(r), max_states, true, starts) && subset_construct(r, max_states, false, anchored)) return true;
     starts = DfaProgram();

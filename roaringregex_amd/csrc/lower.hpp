@@ -166,6 +166,8 @@ bool lower_dfa_sampled(const Reduced &r, const uint8_t *sample, uint32_t pieces,
 // byte kills it, it is accepting exactly at the positions where some match ends.  rev: the DFA of the pattern read
 // right to left - walked backwards from a match end it is accepting exactly at the positions where a match starts.
 bool search_dfas(const Reduced &r, uint32_t max_states, DfaProgram &fwd, DfaProgram &rev);
+// search_dfas' rev alone: the pattern right to left, anchored (the parts of a pattern split at a capture group: frontend.hpp, split_group).
+bool lower_dfa_reversed(const Reduced &r, uint32_t max_states, DfaProgram &rev);
 // Leftmost-longest search (rrx_search_longest_extents): the other two of the four combinations {pattern, pattern reversed} x
 // {anchored, "any bytes first"}.  starts: the DFA of "any bytes, then the pattern right to left" - no byte kills it (no dead row
 // is ever reached: a pass over it has no early exit); stepped from an item's last byte down to its first it is accepting after the

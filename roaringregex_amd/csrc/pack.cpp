@@ -116,33 +116,44 @@ bool pack_items(const DfaProgram &dfa, Image &img, dev::LineDfaDevice &d) {
     return true;
 }
 
+// A DFA in the plain form of the lane-per-item kernels: cls / next / acc
+static void put_plain(const DfaProgram &p, Image &img, dev::DfaDevice &t) {
+    img.put(t.cls, p.cls, 256);
+    img.put(t.next, p.next.data(), p.next.size() * 2);
+    img.put(t.acc, p.accepting.data(), p.accepting.size());
+    t.nstates = p.nstates; t.ncls = p.ncls; t.start = p.start;
+}
+// Row 0 is the dead row: rejecting, every class back to itself (the kernels stop a lane there)
+static bool row0_dead(const DfaProgram &p) {
+    if (p.accepting[0]) return false;
+    for (uint32_t k = 0; k < p.ncls; k++)
+        if (p.next[k] != 0) return false;
+    return true;
+}
+
 bool pack_search_items(const DfaProgram &fwd, const DfaProgram &rev, Image &img, dev::SearchItemsDevice &d) {
-    if (!fwd.nstates || !rev.nstates || rev.accepting[0]) return false;
-    for (uint32_t k = 0; k < rev.ncls; k++)
-        if (rev.next[k] != 0) return false;                      // row 0 of the reverse table must be dead and absorbing
-    auto plain = [&](const DfaProgram &p, dev::DfaDevice &t) {
-        img.put(t.cls, p.cls, 256);
-        img.put(t.next, p.next.data(), p.next.size() * 2);
-        img.put(t.acc, p.accepting.data(), p.accepting.size());
-        t.nstates = p.nstates; t.ncls = p.ncls; t.start = p.start;
-    };
-    plain(fwd, d.fwd);
-    plain(rev, d.rev);
+    if (!fwd.nstates || !rev.nstates || !row0_dead(rev)) return false;
+    put_plain(fwd, img, d.fwd);
+    put_plain(rev, img, d.rev);
     return true;
 }
 
 bool pack_search_longest(const DfaProgram &starts, const DfaProgram &anchored, Image &img, dev::SearchLongestDevice &d) {
-    if (!starts.nstates || !anchored.nstates || anchored.accepting[0]) return false;
-    for (uint32_t k = 0; k < anchored.ncls; k++)
-        if (anchored.next[k] != 0) return false;                 // row 0 of the anchored table must be dead and absorbing
-    auto plain = [&](const DfaProgram &p, dev::DfaDevice &t) {
-        img.put(t.cls, p.cls, 256);
-        img.put(t.next, p.next.data(), p.next.size() * 2);
-        img.put(t.acc, p.accepting.data(), p.accepting.size());
-        t.nstates = p.nstates; t.ncls = p.ncls; t.start = p.start;
-    };
-    plain(starts, d.starts);
-    plain(anchored, d.anchored);
+    if (!starts.nstates || !anchored.nstates || !row0_dead(anchored)) return false;
+    put_plain(starts, img, d.starts);
+    put_plain(anchored, img, d.anchored);
+    return true;
+}
+
+bool pack_group(const DfaProgram &a, const DfaProgram &rev_bc, const DfaProgram &b, const DfaProgram &rev_c, Image &img, dev::GroupDevice &d) {
+    if (!b.nstates) return false;
+    const DfaProgram *const progs[] = {&a, &rev_bc, &b, &rev_c};
+    dev::DfaDevice *const tables[] = {&d.a, &d.rev_bc, &d.b, &d.rev_c};
+    for (int k = 0; k < 4; k++) {
+        if (!progs[k]->nstates) continue;                        // an absent part: no table
+        if (!row0_dead(*progs[k])) return false;                 // both passes of the split kernel stop a lane in row 0
+        put_plain(*progs[k], img, *tables[k]);
+    }
     return true;
 }
 

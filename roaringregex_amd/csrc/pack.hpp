@@ -61,5 +61,8 @@ bool pack_search_items(const DfaProgram &fwd, const DfaProgram &rev, Image &img,
 // The leftmost-longest kernel's tables: starts and anchored in the plain form, one image.  false where the anchored table's row 0
 // is not its dead row - rejecting, every class back to itself (the kernel stops a lane there) - or a table is empty.
 bool pack_search_longest(const DfaProgram &starts, const DfaProgram &anchored, Image &img, dev::SearchLongestDevice &d);
+// The four tables of a pattern split at a capture group (device.hpp: GroupDevice) in the plain form, one image; a table without
+// states is an absent part and stays empty.  false where some table's row 0 is not its dead row, or B has no table.
+bool pack_group(const DfaProgram &a, const DfaProgram &rev_bc, const DfaProgram &b, const DfaProgram &rev_c, Image &img, dev::GroupDevice &d);
 
 }  // namespace rrx

@@ -13,6 +13,12 @@ items (offsets = the line starts, trim 1: the '\\n' is the separator):
                   sides do not find the same and "within_margin" says how far the new entry is from that yardstick, not whether
                   anything got slower.
 
+  extract_group   rrx_extract_group_longest_extents (the fused form: rrx_search_longest_extents, then the longest split point once per
+                  part that is there, in place; marks and result arrays allocated once, outside the timed window) for group 1 of the
+                  text's pattern - the e-mail pattern with its domain in parentheses.  The parent has no such entry: its side runs
+                  `search_longest` on the same pattern and the same items - the part of the work that exists already -, both sides
+                  must find a match in the same number of items, and the last line gives the ratio of the two medians.
+
   replace         the column with every leftmost-longest match replaced (kernels_replace_items.hip), rep_len 1 and 16: per launch
                   rrx_replace_matches_sizes, rrx_replace_matches_fill (the lists found once, outside the timed window) and the
                   one-call rrx_replace_all_longest_extents (search, scans, sizes and fill, its allocations included), and as the
@@ -47,9 +53,11 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CONFIGS = (("url", "U2", 1 << 30), ("email", "EMAIL", 1 << 30), ("kwlog", "K1000C", 1 << 30))
-ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "replace", "pieces")
+ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "extract_group", "replace", "pieces")
+GROUPED = {"EMAIL": r"[A-Za-z0-9._]+@([A-Za-z0-9.]+)"}      # --entry extract_group: the patterns that need a group put in; group 1 everywhere
 SKEW_ITEMS, SKEW_ITEM_BYTES = 64, 16 << 20     # the skewed batch of --entry pieces: its first 64 items are merged lines of 16 MiB or more
-YARDSTICK = {"search_all_longest": "search_all"}   # entries the parent lacks: what its side runs instead
+YARDSTICK = {"search_all_longest": "search_all", "extract_group": "search_longest"}   # entries the parent lacks: what its side runs instead
+SAME_ITEMS = ("extract_group",)                # ... of them those whose yardstick answers for the same items: `found` agrees
 SLICE = 65535                                  # items per call of match / contains: one below kItemsStripesMin
 
 
@@ -66,7 +74,10 @@ def child(tree, entry, kind, pkey, nbytes, launches):
     sys.path.insert(0, tree)
     import roaringregex_amd as rr
     assert os.path.dirname(os.path.abspath(rr.__file__)).startswith(os.path.abspath(tree)), rr.__file__
-    r = rr.RRegex(patterns()[pkey])
+    grouped = pkey.endswith("+group")              # (--entry extract_group: both sides on the pattern as that entry takes it)
+    pkey = pkey.split("+")[0]
+    pattern = GROUPED.get(pkey, patterns()[pkey]) if grouped else patterns()[pkey]
+    r = rr.RGroup(pattern, 1) if entry == "extract_group" else rr.RRegex(pattern)
     host = synth.corpus(kind, 1, nbytes, threads=min(len(os.sched_getaffinity(0)), 16))
     host = host[:int(np.nonzero(host == 10)[0][-1]) + 1]
     dev = torch.from_numpy(host).cuda()
@@ -94,6 +105,11 @@ def child(tree, entry, kind, pkey, nbytes, launches):
     elif entry in ("search_all", "search_all_longest"):
         call = (lambda: r.search_all_extents(dev, off, trim=1)) if entry == "search_all" else (lambda: r.search_all_longest_extents(dev, off, trim=1))
         found = int(call()[2].numel())             # (matches in all)
+    elif entry == "extract_group":
+        out = (torch.empty(n, dtype=torch.int32, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda"))
+        marks = torch.empty(rr._L.rrx_search_all_longest_marks_words(dev.numel(), n), dtype=torch.int32, device="cuda")
+        call = lambda: r.extract_extents(dev, off, trim=1, out=out, marks=marks)
+        found = int((call()[1] >= 0).sum())
     else:
         call = (lambda: r.search_extents(dev, off, trim=1)) if entry == "search" else (lambda: r.search_longest_extents(dev, off, trim=1))
         found = int((call()[1] >= 0).sum())
@@ -321,14 +337,20 @@ def main():
             env = dict(os.environ)
             env.pop("RRX_LIB", None)
             entry = YARDSTICK.get(a.entry, a.entry) if side == "parent" else a.entry
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", entry, "--launches", str(a.launches), "--child", tree, kind, pkey, str(n)],
+            key = pkey + "+group" if a.entry == "extract_group" else pkey
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", entry, "--launches", str(a.launches), "--child", tree, kind, key, str(n)],
                                env=env, timeout=600, stdout=subprocess.PIPE, text=True)
             sys.stdout.write(p.stdout)
             sys.stdout.flush()
             if p.returncode:                   # a fault or a time limit: nothing more is started on the device
                 raise SystemExit("child failed with %d: %s %s %s" % (p.returncode, tree, entry, kind))
             runs[side].append(json.loads(p.stdout.strip().splitlines()[-1]))
-        if a.entry in YARDSTICK:
+        if a.entry in SAME_ITEMS:
+            assert len({x["found"] for x in runs["parent"] + runs["tree"]}) == 1, "the two sides do not find a match in the same items"
+            parent_ms, tree_ms = statistics.median(x["ms"] for x in runs["parent"]), statistics.median(x["ms"] for x in runs["tree"])
+            print("# parent side: %s, tree side: %s, the same pattern and items; tree / parent = %.3f (%.3f against %.3f TB/s)"
+                  % (YARDSTICK[a.entry], a.entry, tree_ms / parent_ms, runs["tree"][0]["bytes"] / tree_ms / 1e9, runs["parent"][0]["bytes"] / parent_ms / 1e9))
+        elif a.entry in YARDSTICK:
             assert len({x["found"] for x in runs["parent"]}) == 1 and len({x["found"] for x in runs["tree"]}) == 1, "a tree does not repeat itself"
             print("# parent side: %s, tree side: %s - a different question, the yardstick is only the nearest thing the parent has" % (YARDSTICK[a.entry], a.entry))
         else:
