@@ -11,11 +11,8 @@ class NfaReplay:
         self.W, self.nbits, self.n_exc, self.accepts_empty = w[0], w[1], w[2], bool(w[3])
         W, o = self.W, 4
 
-        def big(ws):
-            v = 0
-            for i, x in enumerate(ws):
-                v |= x << (32 * i)
-            return v
+        def big(ws):                              # word i = bits [32 i, 32 i + 32)
+            return int.from_bytes(np.asarray(ws, dtype="<u4").tobytes(), "little")
         self.init, self.fin, self.chain, self.self_, self.excm, self.cgrp, self.ctgt = [big(w[o + i * W:o + (i + 1) * W]) for i in range(7)]
         o += 7 * W
         self.B = [big(w[o + c * W:o + (c + 1) * W]) for c in range(256)]
@@ -68,6 +65,78 @@ class NfaReplay:
                 t |= self.X[b]
             S = t & (1 if c == 10 else self.B[c])
         return out
+
+
+class CoopReplay:
+    """The step of the three cooperative NFA engines (kernels_coop.hip: GroupNfa, kernels_wave.hip: WaveNfa, SparseNfa) over an
+    NfaReplay's program, with the engine's LAYOUT of the set's 32-bit words restated:
+        group   word w = lane w / K of the group, slot w % K       (G lanes x K words; `slot0`: the build that masks slot 0 only)
+        wave    word w = lane w / WL, index w % WL                 (64 lanes x WL words)
+        sparse  word w = row w / 64, lane w % 64                   (WR rows of 2048 positions)
+    As the kernels step: {position 0} at the start, nothing injected per byte, no CHAIN mask (gap positions), no carry groups (the
+    lowering gives these programs none), an empty B row for 0x00, >= 0x80 and every byte of class 0.  The slot-0 build of the group
+    engine applies B to slot 0 of every lane alone and kills a line that holds a byte of class 0 by flag.
+
+    mutant: one wrong step at a time - what a kernel would compute with that one mistake in it (test_coop_engines_lowering.py
+    shows that each changes a verdict of every case it applies to):
+        a   the self term applied to word 0 of a lane only (group: slot 0, sparse: row 0)
+        b   exception positions looked for in word 0 of a lane only
+        c   the carry into word 0 of lane 16 of a 32-lane group dropped (the DPP row boundary)
+        d   the carry dropped at every 2048-position block boundary
+        e   the top bit of the neighbouring group's last lane shifted into position 0 (here: a 1 on every byte, the worst neighbour)
+        f   the B mask skipped on slots above 0, and no kill on a byte of class 0
+        g   the bits at and beyond nbits in the program's top word enterable on every byte with a row, and final"""
+    MUTANTS = "abcdefg"
+
+    def __init__(self, rep, engine, lanes, per_lane, slot0=False, mutant=None):
+        assert engine in ("group", "wave", "sparse") and rep.init == 1 and rep.cgrp == 0 and mutant in (None,) + tuple(self.MUTANTS)
+        assert rep.W <= lanes * per_lane
+        self.engine, self.mutant, self.slot0 = engine, mutant, slot0 and engine == "group"
+        nwords = lanes * per_lane
+        self.full = (1 << (32 * nwords)) - 1
+        if engine == "sparse":                               # lanes = 64, per_lane = WR: a lane's word 0 sits in row 0
+            first = [w for w in range(nwords) if w // 64 == 0]
+        else:
+            first = [w for w in range(nwords) if w % per_lane == 0]
+        word0 = sum(0xffffffff << (32 * w) for w in first)
+        self.high = self.full & ~word0
+        self.fin, self.self_, self.excm, self.X = rep.fin, rep.self_, rep.excm, rep.X
+        self.B = [0 if c == 0 or c >= 0x80 else b for c, b in enumerate(rep.B)]
+        self.drop = 0                                        # positions whose carry is lost
+        if mutant == "a":
+            self.self_ &= word0
+        elif mutant == "b":
+            self.excm &= word0
+        elif mutant == "c":
+            assert engine == "group" and lanes == 32
+            self.drop = 1 << (32 * per_lane * 16)
+        elif mutant == "d":
+            self.drop = sum(1 << p for p in range(2048, 32 * nwords, 2048))
+        elif mutant == "g":
+            top = ((1 << (32 * rep.W)) - 1) & ~((1 << rep.nbits) - 1)
+            self.fin |= top
+            self.B = [b | top if b else 0 for b in self.B]
+        self.unmasked = self.high if (self.slot0 or mutant == "f") else 0
+        self.flag = self.slot0 and mutant != "f"
+        self.keep = self.full & ~self.drop
+
+    def accepts(self, s):
+        S, dead = 1, False
+        leak = 1 if self.mutant == "e" else 0
+        for c in s:
+            b = self.B[c]
+            t = ((S << 1) & self.keep) | leak | (S & self.self_)
+            e = S & self.excm
+            while e:
+                p = (e & -e).bit_length() - 1
+                e &= e - 1
+                t |= self.X[p]
+            if not b and self.flag:
+                dead = True
+            S = t & (b | self.unmasked)
+            if not S and not leak:
+                return False
+        return not dead and (S & self.fin) != 0
 
 
 class DfaReplay:
