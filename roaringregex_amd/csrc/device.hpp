@@ -135,17 +135,27 @@ struct LineDfaDevice {
 //        words: the LDS bank is (c1 + c2/2) mod 32, it depends on both bytes); only for corpora without bytes >= 0x80
 //   T2 : u32 [nrows][stride], entry = LDS address of the next row (16 bits) | lines << 16 | verdicts << 24,
 //        2^rep_log2 interleaved copies like the wide table
+//   P8 : u8 [128][136], P8[c1*136 + c2] = the same byte offset, where the largest one - (ncols - 1) * 4 << rep_log2 - fits a byte
+//        (null elsewhere).  Four entries per dword, and the index needs no doubling: the indexed match kernels read it in P's
+//        place (dfa2_byte_pairs_fit; table_engines.hpp: Dfa2T<true>).  Every other stride-2 kernel reads P.
 struct Dfa2Device {
     uint32_t nrows = 0, stride = 0, start_off = 0, rep_log2 = 0;
     const uint16_t *P = nullptr;
     const uint32_t *T2 = nullptr;
+    const uint8_t *P8 = nullptr;
 };
 constexpr uint32_t kDfa2PStride = 130;                // u16 entries per P row
 constexpr uint32_t kDfa2PBytes = 128 * kDfa2PStride * 2;
+// Row stride of P8: 34 dwords.  Simulated on the URL corpus (tools/probe/lds_conflict_sim.py, profiles/p8_lds_conflict_simulation.txt)
+// the strides 131 ... 152 that are not a multiple of 32 cost the same 3.33-3.35 cycles per half-wave; 136 keeps rows dword-aligned
+// and the table a multiple of 16 bytes (copy_table_to_lds).
+constexpr uint32_t kDfa2P8Stride = 136;
+constexpr uint32_t kDfa2P8Bytes = 128 * kDfa2P8Stride;
 // items form (trim 1): code 128 = END OF ITEM - one row more, and column 128 (one of the two pad columns of every row)
 constexpr uint32_t kDfa2PItemsBytes = (129 * kDfa2PStride * 2 + 15) & ~15u;
 // LDS of a stride-2 workgroup: P (32.5 KiB) + one 46 KiB region shared by T2 and the result window = 78.5 KiB, i.e. two
-// 1024-lane workgroups per 160-KiB CU.  Copies of T2 are only made while they leave the window its 16 KiB.
+// 1024-lane workgroups per 160-KiB CU (63 KiB with the byte-wide P8 of 17 KiB: still two - the wave slots bound them - and what
+// that frees is given to nothing).  Copies of T2 are only made while they leave the window its 16 KiB.
 constexpr uint32_t kDfa2RegionBytes = 46 * 1024;
 constexpr uint32_t kDfa2MaxTable = kDfa2RegionBytes - 4 * 1024;       // a table this large leaves a 4 KiB window
 constexpr uint32_t kDfa2TableBudget = 30 * 1024;                      // T2 with its copies

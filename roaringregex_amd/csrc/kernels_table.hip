@@ -32,8 +32,9 @@ __device__ __forceinline__ void feed_load(uint4 (&buf)[kRound / 16], const uint4
 // that holds some).  They are stepped as 0x00 - the same byte class on every table - under the wave-uniform test below.
 // FLUSH_SLOTS: the common flush period in 16-byte slots.  A power of two: known at compile time - the test folds per unrolled slot,
 // and from a whole round on (32: `(r & 3) == 3`) it is one test per round; 0: the period is `flush_mask + 1`, decided per launch.
-template <bool ONEPASS, class PhaseHook, int FLUSH_SLOTS, int KB = 1, bool CLEAN = ONEPASS>
-__device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, const uint64_t window_word, uint32_t *const stage, const uint32_t stage_words,
+// Engine: Dfa2, or Dfa2T<true> on the byte-wide pair table.
+template <bool ONEPASS, class PhaseHook, int FLUSH_SLOTS, int KB = 1, bool CLEAN = ONEPASS, class Engine = Dfa2>
+__device__ __forceinline__ void dfa2_stripe(const Engine &eng, const size_t g, const uint64_t window_word, uint32_t *const stage, const uint32_t stage_words,
                                             const uint8_t *__restrict__ bytes, const size_t nbytes, const uint32_t stripe,
                                             const uint64_t *__restrict__ stripe_base, uint32_t *__restrict__ accept_bits,
                                             uint32_t *__restrict__ counts, uint32_t *__restrict__ slabs, const uint32_t slab_row, PhaseHook &phase,
@@ -54,7 +55,7 @@ __device__ __forceinline__ void dfa2_stripe(const Dfa2 &eng, const size_t g, con
         res.stage_words = stage_words;
         res.drop_mask = (1u << KB) - 1u;
     }
-    Dfa2::State st = fresh ? eng.fresh() : eng.skipping();
+    typename Engine::State st = fresh ? eng.fresh() : eng.skipping();
     auto clean = [](uint32_t w) -> uint32_t {                       // CLEAN: bytes >= 0x80 -> 0x00
         if (CLEAN && __builtin_amdgcn_ballot_w64((w & 0x80808080u) != 0)) {
             const uint32_t hi = (w & 0x80808080u) >> 7;             // 1 in every byte to clear
@@ -196,7 +197,9 @@ __device__ __forceinline__ void settle_shared_word(unsigned long long *slot, uin
 // workgroup b).  The first workgroup owns its first word, the last one every word up to `nwords`, the size of the bitmap.
 // The host launches this form only where the first words of the workgroups are strictly increasing - no word with three
 // writers - and every workgroup's range fits the window (rrx_corpus_one_launch; abi.cpp: own_words_for).
-template <bool ONEPASS, int FLUSH_SLOTS, class PhaseHook = NoPhaseHook, int KB = 1, bool CLEAN = ONEPASS, bool OWN_WORDS = false>
+// PAIRS8: the engine on the byte-wide pair table (prog.P8; the host picks these kernels exactly where the image holds one); P's
+// static array shrinks from 32.5 KiB to 17 KiB, the region T2 and the window share stays what it is.
+template <bool ONEPASS, int FLUSH_SLOTS, class PhaseHook = NoPhaseHook, int KB = 1, bool CLEAN = ONEPASS, bool OWN_WORDS = false, bool PAIRS8 = false>
 __device__ __forceinline__ void dfa2_body(const Dfa2Device &prog, const uint8_t *__restrict__ bytes, size_t nbytes, uint32_t stripe,
                                           const uint64_t *__restrict__ stripe_base, uint32_t *__restrict__ accept_bits,
                                           uint32_t *__restrict__ counts, uint32_t *__restrict__ slabs, PhaseHook phase = PhaseHook(),
@@ -207,9 +210,9 @@ __device__ __forceinline__ void dfa2_body(const Dfa2Device &prog, const uint8_t 
     // more for tables up to 30 KiB, 4 KiB at least).  The arrays are static, so P's base is a link-time constant.
     __shared__ __attribute__((aligned(16))) struct {
         uint8_t t2_and_stage[kDfa2RegionBytes];
-        uint16_t p[kDfa2PBytes / 2];
+        uint8_t p[Dfa2T<PAIRS8>::kPBytes];
     } lds;
-    Dfa2 eng;
+    Dfa2T<PAIRS8> eng;
     eng.load(prog, lds.p, lds.t2_and_stage);
     const uint32_t stage_off = (uint32_t)((Dfa2::lds_bytes(prog) + 15) & ~(size_t)15);
     uint32_t *const stage = reinterpret_cast<uint32_t *>(lds.t2_and_stage + stage_off);
@@ -222,7 +225,7 @@ __device__ __forceinline__ void dfa2_body(const Dfa2Device &prog, const uint8_t 
     const size_t g0 = (size_t)blockIdx.x * kThreads;
     uint64_t window_word = 0;
     if (!ONEPASS) window_word = (line_of(stripe_base[g0]) * KB) >> 5;       // the workgroup's first stripe exists: uniform load
-    dfa2_stripe<ONEPASS, PhaseHook, FLUSH_SLOTS, KB, CLEAN>(eng, g0 + threadIdx.x, window_word, stage, stage_words, bytes, nbytes, stripe, stripe_base, accept_bits,
+    dfa2_stripe<ONEPASS, PhaseHook, FLUSH_SLOTS, KB, CLEAN, Dfa2T<PAIRS8>>(eng, g0 + threadIdx.x, window_word, stage, stage_words, bytes, nbytes, stripe, stripe_base, accept_bits,
                                                             counts, slabs, gridDim.x * kThreads, phase, flush_mask);
     if constexpr (OWN_WORDS) {
         __syncthreads();
@@ -248,21 +251,21 @@ __device__ __forceinline__ void dfa2_body(const Dfa2Device &prog, const uint8_t 
     phase(kPhaseWindowOut);
 }
 // (the unit hand-out inside the workgroup, round 4's option, never won and is gone: profiles/r04_unit_handout_ab.txt)
-template <int FLUSH_SLOTS, bool OWN_WORDS>
+template <int FLUSH_SLOTS, bool OWN_WORDS, bool PAIRS8>
 __global__ __launch_bounds__(kThreads) void match_stripes2_kernel(Dfa2Device prog, const uint8_t *__restrict__ bytes, size_t nbytes,
                                                                    uint32_t stripe, const uint64_t *__restrict__ stripe_base,
                                                                    uint32_t *__restrict__ accept_bits, uint32_t flush_mask,
                                                                    unsigned long long *__restrict__ slots, uint64_t nwords) {
-    dfa2_body<false, FLUSH_SLOTS, NoPhaseHook, 1, false, OWN_WORDS>(prog, bytes, nbytes, stripe, stripe_base, accept_bits, nullptr, nullptr, NoPhaseHook(), flush_mask,
+    dfa2_body<false, FLUSH_SLOTS, NoPhaseHook, 1, false, OWN_WORDS, PAIRS8>(prog, bytes, nbytes, stripe, stripe_base, accept_bits, nullptr, nullptr, NoPhaseHook(), flush_mask,
                                                                     slots, nwords);
 }
 // the same over text that may hold bytes >= 0x80, stepped as 0x00 (rrx_contains_corpus: such bytes are ordinary text there, of the
 // class of NUL, and UTF-8 text stays on the two-bytes-per-lookup kernel)
-template <int FLUSH_SLOTS, bool OWN_WORDS>
+template <int FLUSH_SLOTS, bool OWN_WORDS, bool PAIRS8>
 __global__ __launch_bounds__(kThreads) void match_stripes2_clean_kernel(
     Dfa2Device prog, const uint8_t *__restrict__ bytes, size_t nbytes, uint32_t stripe, const uint64_t *__restrict__ stripe_base,
     uint32_t *__restrict__ accept_bits, uint32_t flush_mask, unsigned long long *__restrict__ slots, uint64_t nwords) {
-    dfa2_body<false, FLUSH_SLOTS, NoPhaseHook, 1, true, OWN_WORDS>(prog, bytes, nbytes, stripe, stripe_base, accept_bits, nullptr, nullptr, NoPhaseHook(), flush_mask,
+    dfa2_body<false, FLUSH_SLOTS, NoPhaseHook, 1, true, OWN_WORDS, PAIRS8>(prog, bytes, nbytes, stripe, stripe_base, accept_bits, nullptr, nullptr, NoPhaseHook(), flush_mask,
                                                                    slots, nwords);
 }
 // two result bits per line (accepted, escaped) into a bitmap of twice the size: the sampled-table engine's first pass
@@ -363,18 +366,25 @@ uint32_t dfa2_window_words(const Dfa2Device &p) {
 }
 bool dfa2_flush_at_compile_time(uint32_t flush_mask) { return flush_mask == 31u; }
 // The period the automatic choice gives text of 33 bytes per line and more - URL, kwlog, a{1,300}, both long-line workloads - is
-// compiled in; every other one is a launch parameter.  `slots` != nullptr: the form that needs no cleared bitmap.
-int match_stripes_dfa2(const Dfa2Device &p, bool clean, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
-                       size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask, unsigned long long *slots, size_t nwords) {
+// compiled in; every other one is a launch parameter.  `slots` != nullptr: the form that needs no cleared bitmap.  An image that
+// holds the byte-wide pair table (p.P8: the host's decision, LineTables::byte_pairs) runs the kernels built on it.
+template <bool PAIRS8>
+static int launch_match_stripes2(const Dfa2Device &p, bool clean, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                                 size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask, unsigned long long *slots, size_t nwords) {
     const bool fixed = dfa2_flush_at_compile_time(flush_mask);
 #define GO(K) launch_dfa2(K, p, bytes, nbytes, stripe, nstripes, kThreads, stream, stripe_base, accept, flush_mask, slots, (uint64_t)nwords)
     if (clean) {
-        if (slots) return fixed ? GO((match_stripes2_clean_kernel<32, true>)) : GO((match_stripes2_clean_kernel<0, true>));
-        return fixed ? GO((match_stripes2_clean_kernel<32, false>)) : GO((match_stripes2_clean_kernel<0, false>));
+        if (slots) return fixed ? GO((match_stripes2_clean_kernel<32, true, PAIRS8>)) : GO((match_stripes2_clean_kernel<0, true, PAIRS8>));
+        return fixed ? GO((match_stripes2_clean_kernel<32, false, PAIRS8>)) : GO((match_stripes2_clean_kernel<0, false, PAIRS8>));
     }
-    if (slots) return fixed ? GO((match_stripes2_kernel<32, true>)) : GO((match_stripes2_kernel<0, true>));
-    return fixed ? GO((match_stripes2_kernel<32, false>)) : GO((match_stripes2_kernel<0, false>));
+    if (slots) return fixed ? GO((match_stripes2_kernel<32, true, PAIRS8>)) : GO((match_stripes2_kernel<0, true, PAIRS8>));
+    return fixed ? GO((match_stripes2_kernel<32, false, PAIRS8>)) : GO((match_stripes2_kernel<0, false, PAIRS8>));
 #undef GO
+}
+int match_stripes_dfa2(const Dfa2Device &p, bool clean, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                       size_t nstripes, uint32_t *accept, void *stream, uint32_t flush_mask, unsigned long long *slots, size_t nwords) {
+    return p.P8 ? launch_match_stripes2<true>(p, clean, bytes, nbytes, stripe, stripe_base, nstripes, accept, stream, flush_mask, slots, nwords)
+                : launch_match_stripes2<false>(p, clean, bytes, nbytes, stripe, stripe_base, nstripes, accept, stream, flush_mask, slots, nwords);
 }
 // ---- the sampled-table engine's second step: the two-bit bitmap (bit 2i = line i accepted, bit 2i + 1 = line i ended in the
 // ESCAPE state) taken apart into the accept bitmap - every word written, nothing to clear beforehand - and the bitmap of the

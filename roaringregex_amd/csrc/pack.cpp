@@ -15,7 +15,7 @@ size_t Image::put(const void *p, size_t n) {
 static int instantiated_width(uint32_t W) { return W <= 4 ? (int)W : W <= 6 ? 6 : W <= 8 ? 8 : W <= 12 ? 12 : 16; }
 
 void pack_dfa_tables(const DfaProgram &dfa, bool wide, bool global, const Dfa2Program *dfa2, const std::vector<uint32_t> &rows,
-                     const std::vector<uint32_t> &cols, Image &img, DeviceTables &t) {
+                     const std::vector<uint32_t> &cols, Image &img, DeviceTables &t, bool byte_pairs) {
     img.put(t.dfa.cls, dfa.cls, 256);
     img.put(t.dfa.next, dfa.next.data(), dfa.next.size() * 2);
     img.put(t.dfa.acc, dfa.accepting.data(), dfa.accepting.size());
@@ -58,16 +58,25 @@ void pack_dfa_tables(const DfaProgram &dfa, bool wide, bool global, const Dfa2Pr
     }
     img.put(t.line.table, T.data(), T.size() * 4);
     img.put(t.line.cls, lcls, 256);
-    if (dfa2) (void)pack_dfa2(*dfa2, rows, cols, img, t.dfa2);
+    if (dfa2) (void)pack_dfa2(*dfa2, rows, cols, img, t.dfa2, 0, byte_pairs);
     t.line.nrows = D; t.line.stride = stride * R; t.line.start_off = dfa.start * row_bytes * R;
     t.line.wide = wide ? 1 : 0; t.line.rep_log2 = rep; t.line.in_global = global ? 1 : 0;
 }
 
-bool pack_dfa2(const Dfa2Program &dfa2, const std::vector<uint32_t> &rs, const std::vector<uint32_t> &cs, Image &img, dev::Dfa2Device &d,
-               uint32_t p_region) {
+uint32_t dfa2_copies_log2(const Dfa2Program &dfa2) {
     const uint32_t D2 = dfa2.nstates, C2 = dfa2.ncols, s2 = C2 | 1u;
     uint32_t rep2 = 0;
     while (rep2 < 5 && (size_t)D2 * s2 * 4 * (2u << rep2) <= dev::kDfa2TableBudget && (size_t)C2 * 4 * (2u << rep2) <= 65535) rep2++;
+    return rep2;
+}
+bool dfa2_byte_pairs_fit(const Dfa2Program &dfa2) {
+    return dfa2.pair_dim == 128 && dfa2.ncols && ((size_t)(dfa2.ncols - 1) * 4 << dfa2_copies_log2(dfa2)) <= 255;
+}
+
+bool pack_dfa2(const Dfa2Program &dfa2, const std::vector<uint32_t> &rs, const std::vector<uint32_t> &cs, Image &img, dev::Dfa2Device &d,
+               uint32_t p_region, bool byte_pairs) {
+    const uint32_t D2 = dfa2.nstates, C2 = dfa2.ncols, s2 = C2 | 1u;
+    const uint32_t rep2 = dfa2_copies_log2(dfa2);
     const uint32_t R2 = 1u << rep2;
     std::vector<uint32_t> T2((size_t)D2 * s2 * R2, 0);
     const bool ordered = rs.size() == D2 && cs.size() == C2 && rs[0] == 0;
@@ -88,6 +97,13 @@ bool pack_dfa2(const Dfa2Program &dfa2, const std::vector<uint32_t> &rs, const s
     img.put(d.P, P.data(), P.size() * 2);
     if (p_region) img.bytes.resize(img.bytes.size() - P.size() * 2 + p_region);
     img.put(d.T2, T2.data(), T2.size() * 4);
+    if (byte_pairs) {                                   // the same entries a byte each (the caller has asked dfa2_byte_pairs_fit)
+        if (!dfa2_byte_pairs_fit(dfa2)) return false;
+        std::vector<uint8_t> P8(dev::kDfa2P8Bytes, 0);
+        for (unsigned c1 = 0; c1 < 128; c1++)
+            for (unsigned c2 = 0; c2 < 128; c2++) P8[c1 * dev::kDfa2P8Stride + c2] = (uint8_t)P[c1 * dev::kDfa2PStride + c2];
+        img.put(d.P8, P8.data(), P8.size());
+    }
     return true;
 }
 

@@ -37,11 +37,15 @@ struct DeviceTables {
 // Table engine: the plain DFA arrays (cls / next / acc), the line-mode table (wide with R interleaved copies, classed, or the
 // global form) and, with `dfa2`, the stride-2 table in the order rows / cols (empty: as numbered).
 void pack_dfa_tables(const DfaProgram &dfa, bool wide, bool global, const Dfa2Program *dfa2, const std::vector<uint32_t> &rows,
-                     const std::vector<uint32_t> &cols, Image &img, DeviceTables &t);
+                     const std::vector<uint32_t> &cols, Image &img, DeviceTables &t, bool byte_pairs = false);
 // A stride-2 table: P (pair -> byte offset of its column), then T2 rows of `ncols | 1` entries, R interleaved copies, entry = LDS
 // byte offset of the next row | lines << 16 | verdicts << 24.  p_region: P's bytes, zero-filled (false if P does not fit them).
+// byte_pairs (only where dfa2_byte_pairs_fit): behind T2 the byte-wide pair table P8 with the same entries (device.hpp).
 bool pack_dfa2(const Dfa2Program &dfa2, const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, Image &img, dev::Dfa2Device &d,
-               uint32_t p_region = 0);
+               uint32_t p_region = 0, bool byte_pairs = false);
+uint32_t dfa2_copies_log2(const Dfa2Program &dfa2);      // log2 of the interleaved copies pack_dfa2 makes of T2
+// Every entry of the pair table fits a byte: (ncols - 1) * 4 << dfa2_copies_log2 <= 255, on the line form (128 codes) only.
+bool dfa2_byte_pairs_fit(const Dfa2Program &dfa2);
 // The items table: the plain table, wide, kItemColumns columns (129 = END OF ITEM); false where row offsets pass 16 bits.
 bool pack_items(const DfaProgram &dfa, Image &img, dev::LineDfaDevice &d);
 void pack_lane_nfa(const NfaProgram &nfa, Image &img, dev::NfaDevice &d);

@@ -22,13 +22,15 @@ bool LineTables::decide(int requested_engine) {
     if (global && !global_fits(dfa)) return false;
     // stride-2 form: when the table (rows of distinct pair columns) fits next to the 32 KiB pair table
     has_dfa2 = !global && requested_engine != RRX_ENGINE_DFA && lower_dfa2_that_fits(dfa, dfa2);
+    // ... and its pair table a byte per entry where the largest column offset fits one: what the indexed match kernels then read
+    byte_pairs = has_dfa2 && dfa2_byte_pairs_fit(dfa2);
     return true;
 }
 const char *LineTables::name() const {
     return has_dfa2 ? "dfa-stride2-table" : global ? "dfa-global-table" : wide ? "dfa-wide-table" : "dfa-classed-table";
 }
 void LineTables::pack(const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, Image &img, DeviceTables &t) const {
-    pack_dfa_tables(dfa, wide, global, has_dfa2 ? &dfa2 : nullptr, rows, cols, img, t);
+    pack_dfa_tables(dfa, wide, global, has_dfa2 ? &dfa2 : nullptr, rows, cols, img, t, has_dfa2 && byte_pairs);
 }
 
 bool ItemsForms::stride2(const LineTables &lt) {

@@ -30,7 +30,8 @@ struct LineTables {
     DfaProgram dfa;
     Dfa2Program dfa2;
     bool has_dfa2 = false;
-    bool wide = false;           // byte-indexed rows (<= kWideMaxStates states) or class-indexed rows
+    bool byte_pairs = false;     // the stride-2 table also gets the byte-wide pair table (pack.hpp: dfa2_byte_pairs_fit)
+    bool wide = false;          // byte-indexed rows (<= kWideMaxStates states) or class-indexed rows
     bool global = false;         // class-indexed table too large for LDS, kept in global memory
     // The forms of `dfa` under the requested RRX_ENGINE_*; false: no table (the global form holds 2^24 entries).
     bool decide(int requested_engine);

@@ -170,7 +170,7 @@ void rrx_regex::apply_t2_order(std::vector<uint32_t> &&rows, std::vector<uint32_
     for (int device : up) {
         Image img;
         OnDevice<dev::Dfa2Device> t;
-        (void)pack_dfa2(match.dfa2, rows, cols, img, t.d);
+        (void)pack_dfa2(match.dfa2, rows, cols, img, t.d, 0, match.byte_pairs);
         hipStream_t st2 = nullptr;
         bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&st2, hipStreamNonBlocking) == hipSuccess &&
                   upload(device, img, t.mem, st2) == hipSuccess;

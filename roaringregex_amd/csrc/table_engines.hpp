@@ -185,51 +185,59 @@ struct PlainDfaGlobalEngine {
 // The per-byte table step is bounded by the latency of its dependent LDS round trip (add -> ds_read -> wait, ~210
 // cycles at 8 chains per SIMD).  Here ONE dependent lookup consumes TWO bytes: the pair's column comes from the
 // state-independent table P (its read does not wait for the state), then e = T2[row(e)][column].  U2: 46 distinct
-// pair columns of 289 class pairs, T2 = 16 KiB.  Per pair: 6 VALU + 2 LDS reads (3 VALU per byte).
-struct Dfa2 {
+// pair columns of 289 class pairs, T2 = 16 KiB.  Per pair: 5 VALU + 2 LDS reads, and one shift per text dword where P holds
+// 16-bit entries: 2.75 VALU per byte on the u16 table, 2.5 on the byte-wide one.
+// PAIRS8: the pair table is the byte-wide P8[128][kDfa2P8Stride] (device.hpp) - four entries per LDS dword where the u16 table
+// has two, and an index made of the raw text bytes.  The entries are the same byte offsets; only the line form has it.
+template <bool PAIRS8>
+struct Dfa2T {
     typedef const __attribute__((address_space(3))) uint32_t *lds_u32_ptr;
     struct State { uint32_t e; };          // low 16 bits = LDS address of the current row (of this lane's copy)
-    const uint16_t *P;                     // LDS (a static array at a link-time address: no base to add per pair)
+    const uint8_t *P;                      // LDS (a static array at a link-time address: no base to add per pair)
     uint32_t start_off, dead_off;
+    static constexpr uint32_t kPBytes = PAIRS8 ? kDfa2P8Bytes : kDfa2PBytes;
 
     __host__ __device__ static size_t lds_bytes(const Dfa2Device &p) { return (size_t)p.nrows * p.stride * 4; }     // dynamic part: T2
-    __device__ void load(const Dfa2Device &p, uint16_t *p_lds, uint8_t *t_lds, uint32_t p_bytes = kDfa2PBytes) {
+    __device__ void load(const Dfa2Device &p, void *p_lds, uint8_t *t_lds, uint32_t p_bytes = kPBytes) {
         const uint32_t tbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)t_lds;
-        copy_table_to_lds(p_lds, p.P, p_bytes);
+        copy_table_to_lds(p_lds, PAIRS8 ? static_cast<const void *>(p.P8) : static_cast<const void *>(p.P), p_bytes);
         copy_table_to_lds(t_lds, p.T2, p.nrows * p.stride * 4, tbase);
         const uint32_t copy = (threadIdx.x & ((1u << p.rep_log2) - 1u)) * 4u;
-        P = p_lds;
+        P = static_cast<const uint8_t *>(p_lds);
         start_off = p.start_off + tbase + copy;
         dead_off = tbase + copy;
     }
     __device__ __forceinline__ State fresh() const { return State{start_off}; }
     __device__ __forceinline__ State skipping() const { return State{dead_off}; }
+#define RRX_LDS_U8(x) (*(P + (x)))
+#define RRX_LDS_U16(x) (*reinterpret_cast<const uint16_t *>(P + (x)))
+#define RRX_LDS_U32(x) (*reinterpret_cast<lds_u32_ptr>(x))
     // generic pair step (tails and the walk past the stripe end)
     __device__ __forceinline__ void step2(State &st, uint32_t c1, uint32_t c2, uint32_t &lines, uint32_t &verdicts) const {
-        const uint32_t col = P[c1 * kDfa2PStride + c2];
+        const uint32_t col = PAIRS8 ? (uint32_t)RRX_LDS_U8(c1 * kDfa2P8Stride + c2) : (uint32_t)RRX_LDS_U16((c1 * kDfa2PStride + c2) * 2);
         st.e = *reinterpret_cast<lds_u32_ptr>((st.e & 0xffffu) + col);
         lines = (st.e >> 16) & 0xffu;
         verdicts = st.e >> 24;
     }
-    // the four bytes of text word w (two pairs), fused with bits = (bits << lines) | verdicts.  Per pair:
+    // the four bytes of text word w (two pairs), fused with bits = (bits << lines) | verdicts.  Per pair, on the u16 table
+    // (w2 = w << 1, once per text word: every byte < 0x80, doubling stays inside the byte):
     //     t    = (2 c1) * 130                v_mul_u32_u24_sdwa   src0_sel:BYTE_even
     //     idx  = t + 2 c2                    v_add_u32_sdwa       src1_sel:BYTE_odd        (byte offset into P)
     //     col  = P[idx]                      ds_read_u16                                   (does not wait for the state)
     //     addr = e.word[0] + col             v_add_u32_sdwa       src0_sel:WORD_0
     //     e    = LDS[addr]                   ds_read_b32
     //     bits = (bits << e.byte[2]) | e.byte[3]                 2 x SDWA
+    // and on the byte-wide one, on w itself: t = c1 * 136, idx = t + c2, col = P8[idx] (ds_read_u8), then the same.
     __device__ __forceinline__ void consume_dword(State &st, uint32_t w, uint32_t &bits) const {
-        const uint32_t w2 = w << 1;                      // every byte < 0x80: doubling stays inside the byte
-        const uint32_t stride = kDfa2PStride;
+        const uint32_t w2 = PAIRS8 ? w : w << 1;
+        const uint32_t stride = PAIRS8 ? kDfa2P8Stride : kDfa2PStride;
         uint32_t ta, ia, tb, ib;
         asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(ta) : "v"(w2), "v"(stride));
         asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(ia) : "v"(ta), "v"(w2));
         asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(tb) : "v"(w2), "v"(stride));
         asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(ib) : "v"(tb), "v"(w2));
-#define RRX_LDS_U16(x) (*reinterpret_cast<const uint16_t *>(reinterpret_cast<const uint8_t *>(P) + (x)))
-#define RRX_LDS_U32(x) (*reinterpret_cast<lds_u32_ptr>(x))
-        const uint32_t ca = RRX_LDS_U16(ia);
-        const uint32_t cb = RRX_LDS_U16(ib);
+        const uint32_t ca = PAIRS8 ? (uint32_t)RRX_LDS_U8(ia) : (uint32_t)RRX_LDS_U16(ia);
+        const uint32_t cb = PAIRS8 ? (uint32_t)RRX_LDS_U8(ib) : (uint32_t)RRX_LDS_U16(ib);
         uint32_t addr;
         asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD" : "=v"(addr) : "v"(st.e), "v"(ca));
         st.e = RRX_LDS_U32(addr);
@@ -241,8 +249,9 @@ struct Dfa2 {
         asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(bits) : "v"(st.e), "v"(bits));
     }
     // The items form (codes 0 ... 128, 128 = END OF ITEM): a byte can no longer be doubled inside the text word, so the entry index
-    // c1 * 130 + c2 is made first and doubled afterwards - one VALU more per pair.
+    // c1 * 130 + c2 is made first and doubled afterwards - one VALU more per pair.  (u16 table only: 129 codes have no byte-wide form.)
     __device__ __forceinline__ void consume_dword_items(State &st, uint32_t w, uint32_t &bits) const {
+        static_assert(!PAIRS8, "the items form indexes the u16 pair table");
         const uint32_t stride = kDfa2PStride;
         uint32_t ta, ia, tb, ib;
         asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(ta) : "v"(w), "v"(stride));
@@ -262,6 +271,7 @@ struct Dfa2 {
         asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(bits) : "v"(st.e), "v"(bits));
     }
 };
+typedef Dfa2T<false> Dfa2;
 
 }  // namespace
 }  // namespace dev

@@ -69,3 +69,28 @@ K = int(cls.max()) + 2
 k1 = np.where(c1 == 10, K - 1, cls[c1]); k2 = np.where(c2 == 10, K - 1, cls[c2])
 print("class-pair table u32 [%d][%d]: %.2f ; distinct %.1f" % (K, K, cost(k1 * K + k2), distinct_mean(k1 * K + k2)))
 print("class-pair table u16: %.2f" % cost((k1 * K + k2) // 2))
+
+# ---- the byte-wide pair table (Dfa2Device::P8: entry = the column's byte offset in a T2 row, four entries per dword) and the
+# class forms it was priced against (profiles/p8_lds_conflict_simulation.txt)
+print("P u8 [128][S], dword = (c1*S + c2) // 4; fits a byte while (columns - 1) * 4 * copies <= 255: here %d" % ((C - 1) * 4))
+for S in (128, 129, 131, 133, 134, 136, 138, 144, 148, 152, 160, 176, 192):
+    print("P u8 row stride %d bytes (%.1f KiB): %.2f" % (S, 128 * S / 1024, cost((c1 * S + c2) // 4)))
+print("distinct P8 dwords per half-wave at stride 136: %.1f" % distinct_mean((c1 * 136 + c2) // 4))
+g1, g2 = cost(c1 // 4), cost(c2 // 4)               # byte -> class from a 128-byte table: 32 dwords, one per bank
+print("class gather u8 [128]: first byte %.2f, second byte %.2f" % (g1, g2))
+best = None
+for width, name in ((1, "u8"), (2, "u16")):
+    for S in (128, 130, 132, 136, 144, 160):
+        v = cost((k1 * S + c2) * width // 4)
+        print("[class of c1][c2] %s row stride %d entries: %.2f, with the class gather %.2f" % (name, S, v, v + g1))
+        best = v if best is None else min(best, v)
+print("[class of c1][c2] at its best: %.2f + %.2f = %.2f" % (best, g1, best + g1))
+best = None
+for width, name in ((1, "u8"), (2, "u16")):
+    for S in sorted({K, K | 1, (K + 3) & ~3, ((K + 3) & ~3) + 4, 32, 36}):
+        if S < K:
+            continue
+        v = cost((c1 * S + k2) * width // 4)
+        print("[c1][class of c2] %s row stride %d entries: %.2f, with the class gather %.2f" % (name, S, v, v + g2))
+        best = v if best is None else min(best, v)
+print("[c1][class of c2] at its best: %.2f + %.2f = %.2f" % (best, g2, best + g2))
