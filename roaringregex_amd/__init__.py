@@ -221,7 +221,7 @@ def bitmap_count(bits, nlines, stream=None):
     assert bits.is_cuda and bits.dtype in (torch.int32, torch.uint32) and bits.is_contiguous() and bits.numel() * 32 >= nlines
     with _on(bits.device.index, stream):
         count = torch.empty(1, dtype=torch.int64, device=bits.device)
-        _check(_L.rrx_bitmap_count(bits.device.index, C.c_void_p(bits.data_ptr() if nlines else 0), nlines, C.c_void_p(count.data_ptr()),
+        _check(_L.rrx_bitmap_count(bits.device.index, _ptr(bits[:(nlines + 31) // 32]), nlines, C.c_void_p(count.data_ptr()),
                                    _stream_ptr(stream)))
         return int(count.item())
 
@@ -231,6 +231,20 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr() if t.numel() else 0)
 
 
+def _batch(data, offsets):
+    """A batch of items nobody has indexed, as every _extents method takes it: item i = data[offsets[i] : offsets[i + 1] - trim] ->
+    (n, the device's index, the address of the bytes, the address of the offsets)."""
+    import torch
+    assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+    return offsets.numel() - 1, data.device.index, _ptr(data), C.c_void_p(offsets.data_ptr())
+
+
+def _span_pair(n, device):
+    """The (start, end) outputs of a search: two int32 tensors of n entries."""
+    import torch
+    return torch.empty(n, dtype=torch.int32, device=device), torch.empty(n, dtype=torch.int32, device=device)
+
+
 def replace_matches(data, offsets, first, start, end, repl, trim=0, stream=None):
     """regexp_replace from a match list, written on the device (rrx_replace_matches_sizes, a torch.cumsum, rrx_replace_matches_fill):
     item i = data[offsets[i] : offsets[i + 1] - trim]; its matches are start/end[first[i] : first[i + 1]], relative to the item, as
@@ -238,12 +252,10 @@ def replace_matches(data, offsets, first, start, end, repl, trim=0, stream=None)
     out_off int64[n + 1]): output item i = out[out_off[i] : out_off[i + 1]], the item with every match replaced by `repl`; the
     separators are not copied.  The lists need not come from a regex of this library.  Waits for the output's size."""
     import torch
-    n = offsets.numel() - 1
-    assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+    n, d = _batch(data, offsets)[:2]
     assert first.is_cuda and first.dtype in (torch.int64, torch.uint64) and first.is_contiguous() and first.numel() == n + 1
     assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() for t in (start, end)) and start.numel() == end.numel()
     assert isinstance(repl, (bytes, bytearray))
-    d = data.device.index
     with _on(d, stream):
         s = _stream_ptr(stream)
         if not start.numel():                      # (the entries take no null array, even where the lists are empty)
@@ -272,11 +284,9 @@ def pieces_of_matches(data, offsets, first, start, end, gaps=False, trim=0, stre
     list_off[i + 1], piece p = out[piece_off[p] : piece_off[p + 1]] - the matches themselves, or what lies between them (one more
     than the matches: re.split).  The lists need not come from a regex of this library.  Waits for the output's size."""
     import torch
-    n = offsets.numel() - 1
-    assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
+    n, d = _batch(data, offsets)[:2]
     assert first.is_cuda and first.dtype in (torch.int64, torch.uint64) and first.is_contiguous() and first.numel() == n + 1
     assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() for t in (start, end)) and start.numel() == end.numel()
-    d = data.device.index
     with _on(d, stream):
         s = _stream_ptr(stream)
         list_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
@@ -351,7 +361,7 @@ class Corpus:
         self.device = data.device.index
         self._h = C.c_void_p()
         with _on(self.device, stream):
-            _check(_L.rrx_corpus_create_ex(self.device, C.c_void_p(data.data_ptr() if data.numel() else 0), data.numel(),
+            _check(_L.rrx_corpus_create_ex(self.device, _ptr(data), data.numel(),
                                            stripe, _stream_ptr(stream), C.byref(self._h)))
 
     def __del__(self):
@@ -397,7 +407,7 @@ class Items:
         self.device = data.device.index
         self._h = C.c_void_p()
         with _on(self.device, stream):
-            _check(_L.rrx_items_create(self.device, C.c_void_p(data.data_ptr() if data.numel() else 0), C.c_void_p(offsets.data_ptr()),
+            _check(_L.rrx_items_create(self.device, _ptr(data), C.c_void_p(offsets.data_ptr()),
                                        offsets.numel() - 1, trim, _stream_ptr(stream), C.byref(self._h)))
 
     def __del__(self):
@@ -447,8 +457,9 @@ class RRegex:
             if out is None:
                 out = torch.empty(nw, dtype=torch.int32, device=corpus.data.device)
             assert out.is_cuda and out.dtype == torch.int32 and out.numel() >= nw
-            _check(_L.rrx_match_corpus(self._h, corpus._h, C.c_void_p(out.data_ptr() if nw else 0), _stream_ptr(stream)))
-        return out[:nw]
+            out = out[:nw]
+            _check(_L.rrx_match_corpus(self._h, corpus._h, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def match_device_bits(self, data, cap_lines=None, out=None, stream=None):
         """One-shot (rrx_match_device): a device tensor nobody has indexed -> (accept bitmap as int32 words, number of
@@ -465,7 +476,7 @@ class RRegex:
                 out = torch.empty(cap_words, dtype=torch.int32, device=data.device)
             assert out.is_cuda and out.dtype == torch.int32 and out.numel() >= cap_words
             nlines = C.c_size_t(0)
-            _check(_L.rrx_match_device(self._h, data.device.index, C.c_void_p(data.data_ptr() if n else 0), n,
+            _check(_L.rrx_match_device(self._h, data.device.index, _ptr(data), n,
                                        C.c_void_p(out.data_ptr()), cap_words, C.byref(nlines), _stream_ptr(stream)))
         return out[:(nlines.value + 31) // 32], nlines.value
 
@@ -478,9 +489,9 @@ class RRegex:
             if out is None:
                 out = torch.empty(n, dtype=torch.uint8, device=corpus.data.device)
             assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
-            _check(_L.rrx_bitmap_to_bytes(corpus.device, C.c_void_p(bits.data_ptr() if n else 0), n,
-                                          C.c_void_p(out.data_ptr() if n else 0), _stream_ptr(stream)))
-        return out[:n]
+            out = out[:n]
+            _check(_L.rrx_bitmap_to_bytes(corpus.device, _ptr(bits), n, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def contains_corpus_bits(self, corpus, out=None, stream=None):
         """Which lines CONTAIN a match (rrx_contains_corpus): a bitmap of 32-bit words, an int32 tensor like match_corpus_bits',
@@ -492,8 +503,9 @@ class RRegex:
             if out is None:
                 out = torch.empty(nw, dtype=torch.int32, device=corpus.data.device)
             assert out.is_cuda and out.dtype == torch.int32 and out.numel() >= nw
-            _check(_L.rrx_contains_corpus(self._h, corpus._h, C.c_void_p(out.data_ptr() if nw else 0), _stream_ptr(stream)))
-        return out[:nw]
+            out = out[:nw]
+            _check(_L.rrx_contains_corpus(self._h, corpus._h, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def contains_corpus(self, corpus, out=None, stream=None):
         """contains[i] = 1 iff line i of the corpus contains a match (one byte per line: bitmap + expansion)."""
@@ -504,20 +516,16 @@ class RRegex:
             if out is None:
                 out = torch.empty(n, dtype=torch.uint8, device=corpus.data.device)
             assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
-            _check(_L.rrx_bitmap_to_bytes(corpus.device, C.c_void_p(bits.data_ptr() if n else 0), n,
-                                          C.c_void_p(out.data_ptr() if n else 0), _stream_ptr(stream)))
-        return out[:n]
+            out = out[:n]
+            _check(_L.rrx_bitmap_to_bytes(corpus.device, _ptr(bits), n, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def search_corpus(self, corpus, stream=None):
         """Per string the accepted substring [start, end) with the smallest end, then the smallest start, as two int32
         tensors of offsets relative to the start of the string; (-1, -1) where nothing is accepted."""
-        import torch
-        n = corpus.num_lines
         with _on(corpus.device, stream):
-            start = torch.empty(n, dtype=torch.int32, device=corpus.data.device)
-            end = torch.empty(n, dtype=torch.int32, device=corpus.data.device)
-            _check(_L.rrx_search_corpus(self._h, corpus._h, C.c_void_p(start.data_ptr() if n else 0), C.c_void_p(end.data_ptr() if n else 0),
-                                        _stream_ptr(stream)))
+            start, end = _span_pair(corpus.num_lines, corpus.data.device)
+            _check(_L.rrx_search_corpus(self._h, corpus._h, _ptr(start), _ptr(end), _stream_ptr(stream)))
         return start, end
 
     def search_all(self, corpus, stream=None):
@@ -528,15 +536,14 @@ class RRegex:
         dev = corpus.data.device
         with _on(corpus.device, stream):
             count = torch.zeros(n, dtype=torch.int32, device=dev)
-            _check(_L.rrx_search_all_count(self._h, corpus._h, C.c_void_p(count.data_ptr() if n else 0), _stream_ptr(stream)))
+            _check(_L.rrx_search_all_count(self._h, corpus._h, _ptr(count), _stream_ptr(stream)))
             inclusive = torch.cumsum(count, dim=0, dtype=torch.int64)
             first = inclusive - count
             total = int(inclusive[-1].item()) if n else 0
             start = torch.empty(total, dtype=torch.int32, device=dev)
             end = torch.empty(total, dtype=torch.int32, device=dev)
             if total:
-                _check(_L.rrx_search_all_fill(self._h, corpus._h, C.c_void_p(first.data_ptr()), C.c_void_p(start.data_ptr() if total else 0),
-                                              C.c_void_p(end.data_ptr() if total else 0), _stream_ptr(stream)))
+                _check(_L.rrx_search_all_fill(self._h, corpus._h, C.c_void_p(first.data_ptr()), _ptr(start), _ptr(end), _stream_ptr(stream)))
         return count, first, start, end
 
     def search_all_fused(self, corpus, cap=None, stream=None):
@@ -553,8 +560,7 @@ class RRegex:
                 start = torch.empty(cap, dtype=torch.int32, device=dev)
                 end = torch.empty(cap, dtype=torch.int32, device=dev)
                 total = C.c_size_t(0)
-                _check(_L.rrx_search_all(self._h, corpus._h, C.c_void_p(first.data_ptr()), C.c_void_p(start.data_ptr() if cap else 0),
-                                         C.c_void_p(end.data_ptr() if cap else 0), cap, C.byref(total), _stream_ptr(stream)))
+                _check(_L.rrx_search_all(self._h, corpus._h, C.c_void_p(first.data_ptr()), _ptr(start), _ptr(end), cap, C.byref(total), _stream_ptr(stream)))
                 if total.value <= cap:
                     break
                 cap = total.value
@@ -568,21 +574,20 @@ class RRegex:
             if out is None:
                 out = torch.empty(n, dtype=torch.uint8, device=items.data.device)
             assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
-            _check(_L.rrx_match_items(self._h, items._h, C.c_void_p(out.data_ptr() if n else 0), _stream_ptr(stream)))
-        return out[:n]
+            out = out[:n]
+            _check(_L.rrx_match_items(self._h, items._h, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def match_extents(self, data, offsets, trim=0, out=None, stream=None):
         """item i = data[offsets[i] : offsets[i+1] - trim]; '\\n' is an ordinary character."""
         import torch
-        n = offsets.numel() - 1
-        assert data.is_cuda and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64)
-        with _on(data.device.index, stream):
+        n, d, b, o = _batch(data, offsets)
+        with _on(d, stream):
             if out is None:
                 out = torch.empty(n, dtype=torch.uint8, device=data.device)
-            _check(_L.rrx_match_extents(self._h, data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0),
-                                        C.c_void_p(offsets.data_ptr()), n, trim, C.c_void_p(out.data_ptr() if n else 0),
-                                        _stream_ptr(stream)))
-        return out[:n]
+            out = out[:n]
+            _check(_L.rrx_match_extents(self._h, d, b, o, n, trim, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def contains_items_bits(self, items, out=None, stream=None):
         """Which items of an indexed batch (Items) CONTAIN a match (rrx_contains_items): a bitmap of 32-bit words, an int32 tensor,
@@ -595,8 +600,9 @@ class RRegex:
             if out is None:
                 out = torch.empty(nw, dtype=torch.int32, device=items.data.device)
             assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= nw
-            _check(_L.rrx_contains_items(self._h, items._h, C.c_void_p(out.data_ptr() if nw else 0), _stream_ptr(stream)))
-        return out[:nw]
+            out = out[:nw]
+            _check(_L.rrx_contains_items(self._h, items._h, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def contains_items(self, items, out=None, stream=None):
         """contains[i] = 1 iff item i of the indexed batch contains a match (one byte per item: bitmap + expansion)."""
@@ -607,71 +613,60 @@ class RRegex:
             if out is None:
                 out = torch.empty(n, dtype=torch.uint8, device=items.data.device)
             assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
-            _check(_L.rrx_bitmap_to_bytes(items.device, C.c_void_p(bits.data_ptr() if n else 0), n,
-                                          C.c_void_p(out.data_ptr() if n else 0), _stream_ptr(stream)))
-        return out[:n]
+            out = out[:n]
+            _check(_L.rrx_bitmap_to_bytes(items.device, _ptr(bits), n, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def contains_extents_bits(self, data, offsets, trim=0, out=None, stream=None):
         """The same for a batch nobody has indexed (rrx_contains_extents): item i = data[offsets[i] : offsets[i+1] - trim] -> the
         bitmap of the items that contain a match, ceil(n / 32) int32 words."""
         import torch
-        n = offsets.numel() - 1
+        n, d, b, o = _batch(data, offsets)
         nw = (n + 31) // 32
-        assert data.is_cuda and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
-        with _on(data.device.index, stream):
+        with _on(d, stream):
             if out is None:
                 out = torch.empty(nw, dtype=torch.int32, device=data.device)
             assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= nw
-            _check(_L.rrx_contains_extents(self._h, data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0),
-                                           C.c_void_p(offsets.data_ptr()), n, trim, C.c_void_p(out.data_ptr() if nw else 0),
-                                           _stream_ptr(stream)))
-        return out[:nw]
+            out = out[:nw]
+            _check(_L.rrx_contains_extents(self._h, d, b, o, n, trim, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def contains_extents(self, data, offsets, trim=0, out=None, stream=None):
         """contains[i] = 1 iff item i = data[offsets[i] : offsets[i+1] - trim] contains a match (one byte per item)."""
         import torch
-        n = offsets.numel() - 1
-        with _on(data.device.index, stream):
+        n, d = _batch(data, offsets)[:2]
+        with _on(d, stream):
             bits = self.contains_extents_bits(data, offsets, trim=trim, stream=stream)
             if out is None:
                 out = torch.empty(n, dtype=torch.uint8, device=data.device)
             assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
-            _check(_L.rrx_bitmap_to_bytes(data.device.index, C.c_void_p(bits.data_ptr() if n else 0), n,
-                                          C.c_void_p(out.data_ptr() if n else 0), _stream_ptr(stream)))
-        return out[:n]
+            out = out[:n]
+            _check(_L.rrx_bitmap_to_bytes(d, _ptr(bits), n, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def search_items(self, items, stream=None):
         """Per item of an indexed batch (Items) the accepted substring [start, end) with the smallest end, then the smallest start
         (rrx_search_items), as two int32 tensors of offsets relative to the start of the item; (-1, -1) where nothing is accepted.
         '\\n', NUL and bytes >= 0x80 are ordinary text inside an item.  Asynchronous on `stream`."""
-        import torch
-        n = items.num_items
         with _on(items.device, stream):
-            start = torch.empty(n, dtype=torch.int32, device=items.data.device)
-            end = torch.empty(n, dtype=torch.int32, device=items.data.device)
-            _check(_L.rrx_search_items(self._h, items._h, C.c_void_p(start.data_ptr() if n else 0), C.c_void_p(end.data_ptr() if n else 0),
-                                       _stream_ptr(stream)))
+            start, end = _span_pair(items.num_items, items.data.device)
+            _check(_L.rrx_search_items(self._h, items._h, _ptr(start), _ptr(end), _stream_ptr(stream)))
         return start, end
 
     def search_extents(self, data, offsets, trim=0, stream=None):
         """The same for a batch nobody has indexed (rrx_search_extents): item i = data[offsets[i] : offsets[i+1] - trim] ->
         (start, end), int32, (-1, -1) where nothing is accepted.  Nothing is read back: the call can be captured into a graph."""
-        import torch
-        n = offsets.numel() - 1
-        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
-        with _on(data.device.index, stream):
-            start = torch.empty(n, dtype=torch.int32, device=data.device)
-            end = torch.empty(n, dtype=torch.int32, device=data.device)
-            _check(_L.rrx_search_extents(self._h, data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0),
-                                         C.c_void_p(offsets.data_ptr()), n, trim, C.c_void_p(start.data_ptr() if n else 0),
-                                         C.c_void_p(end.data_ptr() if n else 0), _stream_ptr(stream)))
+        n, d, b, o = _batch(data, offsets)
+        with _on(d, stream):
+            start, end = _span_pair(n, data.device)
+            _check(_L.rrx_search_extents(self._h, d, b, o, n, trim, _ptr(start), _ptr(end), _stream_ptr(stream)))
         return start, end
 
     def _search_all_two_pass(self, dev, n, count_call, fill_call):
         """count, the prefix with torch, fill -> (count, first, start, end), as search_all shapes them."""
         import torch
         count = torch.zeros(n, dtype=torch.int32, device=dev)
-        _check(count_call(C.c_void_p(count.data_ptr() if n else 0)))
+        _check(count_call(_ptr(count)))
         inclusive = torch.cumsum(count, dim=0, dtype=torch.int64)
         first = inclusive - count
         total = int(inclusive[-1].item()) if n else 0
@@ -690,8 +685,7 @@ class RRegex:
             start = torch.empty(cap, dtype=torch.int32, device=dev)
             end = torch.empty(cap, dtype=torch.int32, device=dev)
             total = C.c_size_t(0)
-            _check(call(C.c_void_p(first.data_ptr()), C.c_void_p(start.data_ptr() if cap else 0), C.c_void_p(end.data_ptr() if cap else 0), cap,
-                        C.byref(total)))
+            _check(call(C.c_void_p(first.data_ptr()), _ptr(start), _ptr(end), cap, C.byref(total)))
             if total.value <= cap:
                 break
             cap = total.value
@@ -710,10 +704,7 @@ class RRegex:
 
     def search_all_extents(self, data, offsets, trim=0, stream=None):
         """The same for a batch nobody has indexed (rrx_search_all_extents_count / _fill): item i = data[offsets[i] : offsets[i+1] - trim]."""
-        import torch
-        n = offsets.numel() - 1
-        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
-        d, b, o = data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0), C.c_void_p(offsets.data_ptr())
+        n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
             return self._search_all_two_pass(data.device, n,
@@ -731,10 +722,7 @@ class RRegex:
 
     def search_all_extents_fused(self, data, offsets, trim=0, cap=None, stream=None):
         """The one-call entry for a batch nobody has indexed (rrx_search_all_extents) -> (first[n + 1], start, end)."""
-        import torch
-        n = offsets.numel() - 1
-        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
-        d, b, o = data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0), C.c_void_p(offsets.data_ptr())
+        n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
             return self._search_all_one_call(data.device, n, cap,
@@ -744,27 +732,18 @@ class RRegex:
         """Per item of an indexed batch (Items) the LEFTMOST-LONGEST match [start, end) (rrx_search_longest_items): the smallest start
         of any accepted substring, then the largest end from there, as two int32 tensors of offsets relative to the start of the item;
         (-1, -1) where nothing is accepted.  '\\n', NUL and bytes >= 0x80 are ordinary text inside an item.  Asynchronous on `stream`."""
-        import torch
-        n = items.num_items
         with _on(items.device, stream):
-            start = torch.empty(n, dtype=torch.int32, device=items.data.device)
-            end = torch.empty(n, dtype=torch.int32, device=items.data.device)
-            _check(_L.rrx_search_longest_items(self._h, items._h, C.c_void_p(start.data_ptr() if n else 0), C.c_void_p(end.data_ptr() if n else 0),
-                                               _stream_ptr(stream)))
+            start, end = _span_pair(items.num_items, items.data.device)
+            _check(_L.rrx_search_longest_items(self._h, items._h, _ptr(start), _ptr(end), _stream_ptr(stream)))
         return start, end
 
     def search_longest_extents(self, data, offsets, trim=0, stream=None):
         """The same for a batch nobody has indexed (rrx_search_longest_extents): item i = data[offsets[i] : offsets[i+1] - trim] ->
         (start, end), int32, (-1, -1) where nothing is accepted.  Nothing is read back: the call can be captured into a graph."""
-        import torch
-        n = offsets.numel() - 1
-        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
-        with _on(data.device.index, stream):
-            start = torch.empty(n, dtype=torch.int32, device=data.device)
-            end = torch.empty(n, dtype=torch.int32, device=data.device)
-            _check(_L.rrx_search_longest_extents(self._h, data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0),
-                                                 C.c_void_p(offsets.data_ptr()), n, trim, C.c_void_p(start.data_ptr() if n else 0),
-                                                 C.c_void_p(end.data_ptr() if n else 0), _stream_ptr(stream)))
+        n, d, b, o = _batch(data, offsets)
+        with _on(d, stream):
+            start, end = _span_pair(n, data.device)
+            _check(_L.rrx_search_longest_extents(self._h, d, b, o, n, trim, _ptr(start), _ptr(end), _stream_ptr(stream)))
         return start, end
 
     @staticmethod
@@ -790,10 +769,7 @@ class RRegex:
 
     def search_all_longest_extents(self, data, offsets, trim=0, stream=None):
         """The same for a batch nobody has indexed (rrx_search_all_longest_extents_count / _fill): item i = data[offsets[i] : offsets[i+1] - trim]."""
-        import torch
-        n = offsets.numel() - 1
-        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
-        d, b, o = data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0), C.c_void_p(offsets.data_ptr())
+        n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
             marks, words = self._search_all_longest_marks(data, n)
@@ -813,10 +789,7 @@ class RRegex:
 
     def search_all_longest_extents_fused(self, data, offsets, trim=0, cap=None, stream=None):
         """The one-call entry for a batch nobody has indexed (rrx_search_all_longest_extents) -> (first[n + 1], start, end)."""
-        import torch
-        n = offsets.numel() - 1
-        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
-        d, b, o = data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0), C.c_void_p(offsets.data_ptr())
+        n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
             return self._search_all_one_call(data.device, n, cap,
@@ -840,11 +813,8 @@ class RRegex:
         EVERY LEFTMOST-LONGEST match replaced by the literal `repl` (bytes; no group references) -> (out uint8, out_off int64[n + 1]),
         output item i = out[out_off[i] : out_off[i + 1]] - re.sub(p, lambda m: repl, item); the separators are not copied.  cap: bytes
         to provide for at first (default: the size of `data`); the call is repeated with the exact size if the column is larger."""
-        import torch
-        n = offsets.numel() - 1
-        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
         assert isinstance(repl, (bytes, bytearray))
-        d, b, o, rep = data.device.index, _ptr(data), C.c_void_p(offsets.data_ptr()), bytes(repl)
+        (n, d, b, o), rep = _batch(data, offsets), bytes(repl)
         with _on(d, stream):
             s = _stream_ptr(stream)
             return self._replace_one_call(data.device, n, int(cap) if cap is not None else data.numel(),
@@ -881,10 +851,7 @@ class RRegex:
         int64[n + 1]): the matches of item i are the pieces list_off[i] .. list_off[i + 1], piece p = out[piece_off[p] :
         piece_off[p + 1]] - [x.group() for x in re.finditer(p, item)].  cap / pieces_cap: bytes and pieces to provide for at first
         (default: the size of `data`, two per item); the call is repeated with the exact sizes if the column is larger."""
-        import torch
-        n = offsets.numel() - 1
-        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
-        d, b, o = data.device.index, _ptr(data), C.c_void_p(offsets.data_ptr())
+        n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
             return self._pieces_one_call(data.device, n, data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
@@ -901,10 +868,7 @@ class RRegex:
         """split on a string column (rrx_split_longest_extents): what lies between the leftmost-longest matches of every item, one
         piece more than it has matches, in the shape extract_all_longest_extents returns - re.split(p, item) for a pattern without
         groups; the separators (`trim`) are not copied."""
-        import torch
-        n = offsets.numel() - 1
-        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
-        d, b, o = data.device.index, _ptr(data), C.c_void_p(offsets.data_ptr())
+        n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
             return self._pieces_one_call(data.device, n, data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
@@ -923,7 +887,7 @@ class RRegex:
         assert data.is_cuda and data.dtype == torch.uint8
         with _on(data.device.index, stream):
             out = torch.zeros(1, dtype=torch.uint8, device=data.device)
-            _check(_L.rrx_match_string(self._h, data.device.index, C.c_void_p(data.data_ptr() if data.numel() else 0), data.numel(),
+            _check(_L.rrx_match_string(self._h, data.device.index, _ptr(data), data.numel(),
                                        C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
         return bool(out.item())
 
@@ -1154,30 +1118,23 @@ class RGroup:
         return torch.empty(words, dtype=torch.int32, device=data.device), words
 
     @staticmethod
-    def _check_batch(data, offsets):
-        import torch
-        assert data.is_cuda and data.dtype == torch.uint8 and offsets.is_cuda and offsets.dtype in (torch.int64, torch.uint64) and offsets.is_contiguous()
-
-    @staticmethod
     def _outputs(n, device, out):
         import torch
         if out is not None:
             assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() and t.numel() >= n for t in out)
             return out
-        return torch.empty(n, dtype=torch.int32, device=device), torch.empty(n, dtype=torch.int32, device=device)
+        return _span_pair(n, device)
 
     def spans_extents(self, data, offsets, match_start, match_end, trim=0, out=None, stream=None):
         """From a span list - (match_start, match_end) int32 per item, relative to the item, as RRegex.search_longest_extents returns
         it for self.regex - to the group's spans (rrx_group_spans_extents) -> (start, end) int32, (-1, -1) where the item has no match
         or the span is not one.  out: the two result tensors; they may be match_start / match_end themselves.  Asynchronous."""
-        self._check_batch(data, offsets)
-        n = offsets.numel() - 1
-        d = data.device.index
+        n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             start, end = self._outputs(n, data.device, out)
             marks, words = self._marks(data, n)
-            _check(_L.rrx_group_spans_extents(self._h, d, _ptr(data), C.c_void_p(offsets.data_ptr()), n, trim, _ptr(match_start), _ptr(match_end),
-                                              _ptr(marks), words, _ptr(start), _ptr(end), _stream_ptr(stream)))
+            _check(_L.rrx_group_spans_extents(self._h, d, b, o, n, trim, _ptr(match_start), _ptr(match_end), _ptr(marks), words, _ptr(start), _ptr(end),
+                                              _stream_ptr(stream)))
         return start, end
 
     def spans_items(self, items, match_start, match_end, out=None, stream=None):
@@ -1194,15 +1151,12 @@ class RGroup:
         """The group's span per item of a batch nobody has indexed, the search included (rrx_extract_group_longest_extents): item i =
         data[offsets[i] : offsets[i+1] - trim] -> (start, end) int32, (-1, -1) where nothing is accepted.  Nothing is read back: with
         `out` and `marks` (an int32 tensor of rrx_search_all_longest_marks_words words) given, the call can be captured into a graph."""
-        self._check_batch(data, offsets)
-        n = offsets.numel() - 1
-        d = data.device.index
+        n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             start, end = self._outputs(n, data.device, out)
             if marks is None:
                 marks = self._marks(data, n)[0]
-            _check(_L.rrx_extract_group_longest_extents(self._h, d, _ptr(data), C.c_void_p(offsets.data_ptr()), n, trim, _ptr(marks), marks.numel(),
-                                                        _ptr(start), _ptr(end), _stream_ptr(stream)))
+            _check(_L.rrx_extract_group_longest_extents(self._h, d, b, o, n, trim, _ptr(marks), marks.numel(), _ptr(start), _ptr(end), _stream_ptr(stream)))
         return start, end
 
     def extract_items(self, items, out=None, marks=None, stream=None):

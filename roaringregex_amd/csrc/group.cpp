@@ -3,7 +3,7 @@
 // rrx_extract_group_longest_*): the longest split point (kernels_group_items.hip), launched once per part that is there.
 #include <cstring>
 
-#include "handles.hpp"
+#include "items.hpp"
 
 using namespace rrx;
 
@@ -38,16 +38,10 @@ struct rrx_group {
 
 namespace {
 
-struct ItemBatch { int device; const uint8_t *bytes; const uint64_t *off; size_t nitems; uint32_t trim; };
-struct ItemMarks { uint32_t *words; size_t nwords; };
-
 const char *const kGroupArgError = "null argument, or marks_words below nitems + 1";
 // d_marks may be null only where no launch needs it: both A and C absent
-bool group_args_ok(const rrx_group *g, size_t nitems, const void *d_off, ItemMarks m, const uint32_t *d_start, const uint32_t *d_end) {
-    if (!g) return false;
-    if (!nitems) return true;
-    if (!d_off || !d_start || !d_end) return false;
-    return (!g->has_a && !g->has_c) || (m.words && m.nwords >= nitems + 1);
+bool group_args_ok(const rrx_group *g, const ItemBatch &b, ItemMarks m, const uint32_t *d_start, const uint32_t *d_end) {
+    return batch_args_ok(g, b, {d_start, d_end}) && ((!g->has_a && !g->has_c) || marks_ok(b.nitems, m));
 }
 
 // From the spans in (in_start, in_end) to the group's spans in (d_start, d_end); the two pairs may be the same arrays.
@@ -164,27 +158,28 @@ size_t rrx_group_program_words(const rrx_group *grp, int which, uint32_t *out, s
 int rrx_group_spans_extents(const rrx_group *grp, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                             const uint32_t *d_match_start, const uint32_t *d_match_end, uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start,
                             uint32_t *d_group_end, void *stream) {
-    if (!group_args_ok(grp, nitems, d_off, {d_marks, marks_words}, d_group_start, d_group_end) || (nitems && (!d_match_start || !d_match_end)))
+    const ItemBatch b = batch_of(device, d_bytes, d_off, nitems, trim);
+    if (!group_args_ok(grp, b, {d_marks, marks_words}, d_group_start, d_group_end) || !batch_args_ok(grp, b, {d_match_start, d_match_end}))
         return fail(RRX_ERR_ARG, kGroupArgError);
-    return group_spans(grp, {device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim}, d_match_start, d_match_end, {d_marks, marks_words},
-                       d_group_start, d_group_end, stream);
+    return group_spans(grp, b, d_match_start, d_match_end, {d_marks, marks_words}, d_group_start, d_group_end, stream);
 }
 int rrx_group_spans_items(const rrx_group *grp, const rrx_items *it, const uint32_t *d_match_start, const uint32_t *d_match_end, uint32_t *d_marks,
                           size_t marks_words, uint32_t *d_group_start, uint32_t *d_group_end, void *stream) {
-    if (!it || !group_args_ok(grp, it->nitems, it->d_off, {d_marks, marks_words}, d_group_start, d_group_end) || (it->nitems && (!d_match_start || !d_match_end)))
-        return fail(RRX_ERR_ARG, kGroupArgError);
-    return group_spans(grp, {it->device, it->d_bytes, it->d_off, it->nitems, it->trim}, d_match_start, d_match_end, {d_marks, marks_words}, d_group_start,
-                       d_group_end, stream);
+    if (!it) return fail(RRX_ERR_ARG, kGroupArgError);
+    return rrx_group_spans_extents(grp, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_match_start, d_match_end, d_marks, marks_words, d_group_start,
+                                   d_group_end, stream);
 }
 int rrx_extract_group_longest_extents(const rrx_group *grp, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                                       uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start, uint32_t *d_group_end, void *stream) {
-    if (!group_args_ok(grp, nitems, d_off, {d_marks, marks_words}, d_group_start, d_group_end)) return fail(RRX_ERR_ARG, kGroupArgError);
-    return group_extract(grp, {device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim}, {d_marks, marks_words}, d_group_start, d_group_end, stream);
+    const ItemBatch b = batch_of(device, d_bytes, d_off, nitems, trim);
+    if (!group_args_ok(grp, b, {d_marks, marks_words}, d_group_start, d_group_end)) return fail(RRX_ERR_ARG, kGroupArgError);
+    return group_extract(grp, b, {d_marks, marks_words}, d_group_start, d_group_end, stream);
 }
 int rrx_extract_group_longest_items(const rrx_group *grp, const rrx_items *it, uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start,
                                     uint32_t *d_group_end, void *stream) {
-    if (!it || !group_args_ok(grp, it->nitems, it->d_off, {d_marks, marks_words}, d_group_start, d_group_end)) return fail(RRX_ERR_ARG, kGroupArgError);
-    return group_extract(grp, {it->device, it->d_bytes, it->d_off, it->nitems, it->trim}, {d_marks, marks_words}, d_group_start, d_group_end, stream);
+    if (!it) return fail(RRX_ERR_ARG, kGroupArgError);
+    return rrx_extract_group_longest_extents(grp, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_marks, marks_words, d_group_start, d_group_end,
+                                             stream);
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // handles.hpp — what the units of the C ABI of librrx.so (include/rrx.h) share: the error helpers, the owners of device and pinned
 // memory, the one upload path, the mailbox, and the three handles.  The units: regex.cpp (rrx_regex: compile, accessors, options,
 // program dumps, table order and sampled table, its tables on the device), corpus.cpp (rrx_corpus, the batch entries, the one-shot
-// entry, the host pipeline), search.cpp, items.cpp (explicit items, single strings), group.cpp (rrx_group: a
-// pattern split at a capture group, with a handle of its own).  What a pattern compiles to and which table
+// entry, the host pipeline), search.cpp, the units of explicit items - items.cpp (batches, match and contains), item_search.cpp
+// (where the matches are), item_columns.cpp (replace and pieces); what they share is items.hpp -, strings.cpp (single strings),
+// group.cpp (rrx_group: a pattern split at a capture group, with a handle of its own).  What a pattern compiles to and which table
 // forms it gets is decided in plan.cpp, the life of a sampled table in sampled.cpp.
 #pragma once
 #include <hip/hip_runtime.h>

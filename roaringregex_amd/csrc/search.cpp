@@ -1,6 +1,6 @@
 // search.cpp — first match and all matches per line of a corpus (rrx_search_corpus, rrx_search_all*): the corpus' line offsets
 // and chunk index, built at the first search, and the launches.
-#include "handles.hpp"
+#include "items.hpp"
 
 using namespace rrx;
 
@@ -139,13 +139,10 @@ int rrx_search_all(const rrx_regex *re, const rrx_corpus *c, uint64_t *d_first, 
     hipError_t he = d_sums.alloc(c->device, dev::scan_scratch_words(c->nlines) * sizeof(uint64_t));
     if (he != hipSuccess) return hip_fail(he, "hipMalloc");
     int e = dev::empty_matches(c->d_line_off, c->nlines, d_count, nullptr, nullptr, nullptr, stream);
-    if (!e) e = dev::scan_counts(d_count, d_first, d_sums, c->nlines, stream);  // d_first[nlines] = total
     if (e) return hip_fail((hipError_t)e, "empty_matches / scan launch");
-    he = hipMemsetAsync(d_first, 0, sizeof(uint64_t), st);                      // the scan marks entry 0 as a stripe start: not here
     uint64_t tot = 0;
-    if (he == hipSuccess) he = hipMemcpyAsync(&tot, d_first + c->nlines, sizeof tot, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return hip_fail(he, "search_all scan");
+    rc = scan_total(d_count, d_first, d_sums, c->nlines, stream, "empty_matches / scan launch", "search_all scan", &tot);
+    if (rc) return rc;
     *total = (size_t)tot;
     if (tot && cap) {                                                            // matches beyond `cap` are counted, not written (as rrx.h says)
         e = dev::empty_matches(c->d_line_off, c->nlines, nullptr, d_first, d_start, d_end, stream, cap);

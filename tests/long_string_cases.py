@@ -27,9 +27,9 @@ K_LONG_GROUP = 128          # device.hpp kLongGroup
 K_LONG_SLOTS = 4            # kernels_long.hip kLongSlots
 K_LONG_PREFIX = 64          # kernels_long.hip kLongPrefix
 K_LONG_MAX_STATES = 254     # device.hpp kLongMaxStates
-TABLE_FROM = 1024           # items.cpp kLongStringBytesTable
-NFA_FROM = 32 * 1024        # items.cpp kLongStringBytes
-NFA_MAX_BITS = 256          # items.cpp kLongNfaMaxBits
+TABLE_FROM = 1024           # strings.cpp kLongStringBytesTable
+NFA_FROM = 32 * 1024        # strings.cpp kLongStringBytes
+NFA_MAX_BITS = 256          # strings.cpp kLongNfaMaxBits
 
 
 def Z(k):

@@ -34,6 +34,18 @@ items (offsets = the line starts, trim 1: the '\\n' is the separator):
                   runs the SKEWED batch: the URL text (a quarter longer) whose first 64 items are merged lines of 16 MiB each - for
                   replace's fill one wave's work, which is why that child makes two rounds of two launches only.
 
+  one_call        the entries that count, scan, read a total back and fill inside one call - rrx_search_all_extents,
+                  rrx_search_all_longest_extents, rrx_replace_all_longest_extents (rep_len 1), rrx_extract_all_longest_extents and
+                  rrx_split_longest_extents - on the first 4096 lines of the e-mail text: a batch so small that a call is its
+                  launches' latencies, its allocations and its synchronisations, which is what a change of the host code can move.
+                  Both sides run THIS tree's Python and differ in the library alone: the parent's children load
+                  .oldtree/roaringregex_amd/librrx.so through RRX_LIB.  Exact caps (learnt by a call with cap 0), the five calls
+                  alternating, host time per call - each returns behind its last synchronise -, the same four children and the same
+                  margin as below, per entry; the lines go to `--out` as well.
+
+A yardstick stands in only for a parent that lacks the entry (its wrapper shows it): a later parent runs the entry itself, and both
+sides must find the same.
+
 The parent's side runs from a second checkout under .oldtree/ (git archive <commit> | tar -x -C .oldtree; build there): per text
 four children - parent, tree, parent, tree -, a fresh process each; device events around every launch (every sweep of slices),
 median and spread of `--launches` launches (at least twelve) after warm-up.  A child that fails ends the run: nothing more is
@@ -43,6 +55,7 @@ between its two medians and its own spread - and whether each of the tree's medi
     python tools/probe/item_lanes_rate.py --entry search [--old .oldtree] [--launches 15] [--scale 1.0]
     python tools/probe/item_lanes_rate.py --entry replace [--launches 15] [--scale 1.0] [--out profiles/replace_items_rate.txt]
     python tools/probe/item_lanes_rate.py --entry pieces [--launches 15] [--scale 1.0] [--out profiles/pieces_items_rate.txt]
+    python tools/probe/item_lanes_rate.py --entry one_call [--old .oldtree] [--launches 15] [--out profiles/one_call_items_rate.txt]
 """
 import argparse
 import json
@@ -53,12 +66,15 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CONFIGS = (("url", "U2", 1 << 30), ("email", "EMAIL", 1 << 30), ("kwlog", "K1000C", 1 << 30))
-ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "extract_group", "replace", "pieces")
+ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "extract_group", "replace", "pieces", "one_call")
 GROUPED = {"EMAIL": r"[A-Za-z0-9._]+@([A-Za-z0-9.]+)"}      # --entry extract_group: the patterns that need a group put in; group 1 everywhere
 SKEW_ITEMS, SKEW_ITEM_BYTES = 64, 16 << 20     # the skewed batch of --entry pieces: its first 64 items are merged lines of 16 MiB or more
 YARDSTICK = {"search_all_longest": "search_all", "extract_group": "search_longest"}   # entries the parent lacks: what its side runs instead
 SAME_ITEMS = ("extract_group",)                # ... of them those whose yardstick answers for the same items: `found` agrees
+NEWER = {"search_all_longest": "def search_all_longest_extents", "extract_group": "class RGroup"}     # how a parent's wrapper shows that it has the entry
 SLICE = 65535                                  # items per call of match / contains: one below kItemsStripesMin
+ONE_CALL_ITEMS, ONE_CALL_TEXT = 4096, ("email", "EMAIL", 1 << 20)      # --entry one_call: the batch, and the text it is the head of
+ONE_CALL_ENTRIES = ("search_all", "search_all_longest", "replace_all_longest", "extract_all_longest", "split_longest")
 
 
 def child(tree, entry, kind, pkey, nbytes, launches):
@@ -87,6 +103,8 @@ def child(tree, entry, kind, pkey, nbytes, launches):
         return replace_child(rr, r, kind, dev, off, n, launches)
     if entry == "pieces":
         return pieces_child(rr, r, kind, dev, off, launches, skew)
+    if entry == "one_call":
+        return one_call_child(rr, r, kind, dev, off, launches)
 
     if entry in ("match", "contains"):
         slices = [off[k:k + SLICE + 1] for k in range(0, n, SLICE)]
@@ -262,6 +280,94 @@ def pieces_child(rr, r, kind, dev, off, launches, skew):
     print(json.dumps(line), flush=True)
 
 
+def one_call_child(rr, r, kind, dev, off, launches):
+    """The five one-call entries on the first ONE_CALL_ITEMS items with exact caps, alternating; host time per call, one JSON line."""
+    import ctypes as C
+    import time
+    import torch
+    assert off.numel() > ONE_CALL_ITEMS, "the text is too short for the batch"
+    n, off = ONE_CALL_ITEMS, off[:ONE_CALL_ITEMS + 1].contiguous()
+    L, s = rr._L, rr._stream_ptr(None)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+    i64 = lambda k: torch.empty(k, dtype=torch.int64, device="cuda")
+    prefix, tot, npc = i64(n + 1), C.c_size_t(0), C.c_size_t(0)
+    calls, found = {}, {}
+    for name in ONE_CALL_ENTRIES:                   # a call with cap 0 for the sizes, then the closure with the exact caps
+        if name.startswith("search_all"):
+            fn = getattr(L, "rrx_%s_extents" % name)
+            call = lambda cap, st, en, fn=fn: rr._check(fn(r._h, 0, ptr(dev), ptr(off), n, 1, ptr(prefix), ptr(st), ptr(en), cap, C.byref(tot), s))
+            call(0, i64(0), i64(0))
+            found[name] = tot.value
+            st, en = (torch.empty(tot.value, dtype=torch.int32, device="cuda") for _ in range(2))
+            calls[name] = lambda call=call, cap=tot.value, st=st, en=en: call(cap, st, en)
+        elif name == "replace_all_longest":
+            call = lambda cap, out: rr._check(L.rrx_replace_all_longest_extents(r._h, 0, ptr(dev), ptr(off), n, 1, b"#", 1, ptr(prefix), ptr(out), cap,
+                                                                                C.byref(tot), s))
+            call(0, i64(0))
+            found[name] = tot.value
+            out = torch.empty(tot.value, dtype=torch.uint8, device="cuda")
+            calls[name] = lambda call=call, cap=tot.value, out=out: call(cap, out)
+        else:
+            fn = getattr(L, "rrx_%s_extents" % name)
+            call = lambda pcap, poff, cap, out, fn=fn: rr._check(fn(r._h, 0, ptr(dev), ptr(off), n, 1, ptr(prefix), ptr(poff), pcap, ptr(out), cap, C.byref(npc),
+                                                                    C.byref(tot), s))
+            call(0, i64(1), 0, i64(0))
+            found[name] = [npc.value, tot.value]
+            poff, out = i64(npc.value + 1), torch.empty(tot.value, dtype=torch.uint8, device="cuda")
+            calls[name] = lambda call=call, pcap=npc.value, poff=poff, cap=tot.value, out=out: call(pcap, poff, cap, out)
+    for _ in range(3):
+        for call in calls.values():
+            call()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in calls}
+    for _ in range(launches):
+        for k, call in calls.items():               # alternating: every call of an entry has the others right beside it
+            t0 = time.perf_counter()
+            call()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    line = {"config": kind, "entry": "one_call", "lib": os.path.relpath(os.environ["RRX_LIB"], ROOT) if "RRX_LIB" in os.environ else "tree", "items": n, "bytes": int(off[-1] - off[0]), "found": found, "ms": {},
+            "spread": {}}
+    for k, v in ms.items():
+        line["ms"][k] = round(statistics.median(v), 4)
+        line["spread"][k] = round((max(v) - min(v)) / statistics.median(v), 4)
+    print(json.dumps(line), flush=True)
+
+
+def one_call_main(a):
+    """Four children - parent's library, tree's, parent's, tree's - on this tree's Python; per entry the margin of the other modes."""
+    old_lib = os.path.join(a.old, "roaringregex_amd", "librrx.so")
+    assert os.path.exists(old_lib), "build the parent commit under %s first" % a.old
+    kind, pkey, nbytes = ONE_CALL_TEXT
+    runs = {"parent": [], "tree": []}
+    for side in ("parent", "tree") * 2:
+        env = dict(os.environ)
+        env.pop("RRX_LIB", None)
+        if side == "parent":
+            env["RRX_LIB"] = os.path.abspath(old_lib)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", "one_call", "--launches", str(a.launches), "--child", ROOT, kind, pkey, str(nbytes)],
+                           env=env, timeout=300, stdout=subprocess.PIPE, text=True)
+        sys.stdout.write(p.stdout)
+        sys.stdout.flush()
+        if p.returncode:                       # a fault or a time limit: nothing more is started on the device
+            raise SystemExit("child failed with %d: one_call %s" % (p.returncode, side))
+        runs[side].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    assert all(x["found"] == runs["parent"][0]["found"] for x in runs["parent"] + runs["tree"]), "the two libraries do not find the same"
+    assert all(x["lib"] != "tree" for x in runs["parent"]) and all(x["lib"] == "tree" for x in runs["tree"])
+    lines = runs["parent"][:1] + runs["tree"][:1] + runs["parent"][1:] + runs["tree"][1:]
+    for k in ONE_CALL_ENTRIES:
+        pm, tm = [x["ms"][k] for x in runs["parent"]], [x["ms"][k] for x in runs["tree"]]
+        margin = max(abs(pm[0] - pm[1]), max(x["spread"][k] * x["ms"][k] for x in runs["parent"]))
+        lines.append({"entry": k, "parent_ms": pm, "tree_ms": tm, "margin_ms": round(margin, 4), "within_margin": all(t <= max(pm) + margin for t in tm)})
+        print(json.dumps(lines[-1]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("tools/probe/item_lanes_rate.py --entry one_call --launches %d: medians of the host time per call [ms] on %d items, the five calls\n"
+                "alternating in each of four children (the parent's library through RRX_LIB, the tree's, and again); margin = what the parent\n"
+                "differs from itself: the larger of the distance between its two medians and its own spread.\n" % (max(a.launches, 12), ONE_CALL_ITEMS))
+        for x in lines:
+            f.write(json.dumps(x) + "\n")
+
+
 def pieces_main(a):
     """One child per text and one for the skewed batch, this tree alone; the lines to a.out as they come."""
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -329,14 +435,18 @@ def main():
         return replace_main(a)
     if a.entry == "pieces":
         return pieces_main(a)
+    if a.entry == "one_call":
+        return one_call_main(a)
     assert os.path.exists(os.path.join(a.old, "roaringregex_amd", "librrx.so")), "build the parent commit under %s first" % a.old
+    # a parent that has the entry runs the entry itself: the yardsticks are for the commit that added it
+    yardstick = a.entry in YARDSTICK and NEWER[a.entry] not in open(os.path.join(a.old, "roaringregex_amd", "__init__.py")).read()
     for kind, pkey, nbytes in CONFIGS:
         n = int(nbytes * a.scale) // 4096 * 4096
         runs = {"parent": [], "tree": []}
         for side, tree in (("parent", a.old), ("tree", ROOT)) * 2:
             env = dict(os.environ)
             env.pop("RRX_LIB", None)
-            entry = YARDSTICK.get(a.entry, a.entry) if side == "parent" else a.entry
+            entry = YARDSTICK[a.entry] if side == "parent" and yardstick else a.entry
             key = pkey + "+group" if a.entry == "extract_group" else pkey
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", entry, "--launches", str(a.launches), "--child", tree, kind, key, str(n)],
                                env=env, timeout=600, stdout=subprocess.PIPE, text=True)
@@ -345,12 +455,12 @@ def main():
             if p.returncode:                   # a fault or a time limit: nothing more is started on the device
                 raise SystemExit("child failed with %d: %s %s %s" % (p.returncode, tree, entry, kind))
             runs[side].append(json.loads(p.stdout.strip().splitlines()[-1]))
-        if a.entry in SAME_ITEMS:
+        if yardstick and a.entry in SAME_ITEMS:
             assert len({x["found"] for x in runs["parent"] + runs["tree"]}) == 1, "the two sides do not find a match in the same items"
             parent_ms, tree_ms = statistics.median(x["ms"] for x in runs["parent"]), statistics.median(x["ms"] for x in runs["tree"])
             print("# parent side: %s, tree side: %s, the same pattern and items; tree / parent = %.3f (%.3f against %.3f TB/s)"
                   % (YARDSTICK[a.entry], a.entry, tree_ms / parent_ms, runs["tree"][0]["bytes"] / tree_ms / 1e9, runs["parent"][0]["bytes"] / parent_ms / 1e9))
-        elif a.entry in YARDSTICK:
+        elif yardstick:
             assert len({x["found"] for x in runs["parent"]}) == 1 and len({x["found"] for x in runs["tree"]}) == 1, "a tree does not repeat itself"
             print("# parent side: %s, tree side: %s - a different question, the yardstick is only the nearest thing the parent has" % (YARDSTICK[a.entry], a.entry))
         else:
