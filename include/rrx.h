@@ -417,8 +417,8 @@ int rrx_search_all_longest_items(const rrx_regex *re, const rrx_items *items, ui
 /* regexp_replace on a string column, WRITTEN on the device: from a column, a match list per item and a literal replacement to the
  * new column (d_out_off[nitems + 1], d_out).  Item i is t = d_bytes[d_off[i] .. d_off[i+1] - trim), empty where trim exceeds its
  * length.  Its matches (s_0,e_0) ... (s_{m-1},e_{m-1}) are in order, s_0 >= 0, e_k >= s_k, s_{k+1} >= e_k, e_{m-1} <= length; the
- * output item is t[0:s_0] + R + t[e_0:s_1] + R + ... + R + t[e_{m-1}:], R the replacement: rep_len >= 0 literal bytes, no group
- * references (the engine's only capture is rrx_group's top-level group span).  An empty match inserts R at its position (a* on "baab" with "<>": "<>b<><>b<>"), an
+ * output item is t[0:s_0] + R + t[e_0:s_1] + R + ... + R + t[e_{m-1}:], R the replacement: rep_len >= 0 literal bytes (a
+ * replacement with group references: rrx_replace_template_* / rrx_replace_groups_longest_* below).  An empty match inserts R at its position (a* on "baab" with "<>": "<>b<><>b<>"), an
  * item without matches is copied verbatim, the `trim` separator bytes are never copied: the output column has no separators.  This
  * is Python's re.sub(p, lambda m: R, t) for the list re.finditer names.
  * THE MATCH LIST is the shape every rrx_search_all* one-call form returns (and the two-pass forms once the caller's prefix has one
@@ -586,6 +586,76 @@ int rrx_extract_group_longest_extents(const rrx_group *grp, int device, const vo
                                       uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start, uint32_t *d_group_end, void *stream);
 int rrx_extract_group_longest_items(const rrx_group *grp, const rrx_items *items, uint32_t *d_marks, size_t marks_words,
                                     uint32_t *d_group_start, uint32_t *d_group_end, void *stream);
+
+/* THE GROUP'S SPAN FOR EVERY MATCH OF A MATCH LIST: rrx_group_spans_* with a list per item in the shape every rrx_search_all*
+ * one-call form returns - d_first has nitems + 1 entries, match k of item i is slot d_first[i] + k of d_match_start / d_match_end, the
+ * arrays (the two outputs too) are indexed by the slot itself, d_first[0] need not be 0.  For every slot the answer is exactly what
+ * rrx_group_spans_extents gives for that span on that item: the rule for i and j above, spans clamped into the item, a start of
+ * 0xFFFFFFFF passed on as "none", no split: 0xFFFFFFFF in both words, a span that is no match of P: none where A or C is present.
+ * Exactly the slots d_first[0] .. d_first[nitems] of d_group_start / d_group_end are written; they may be the input arrays.  d_marks,
+ * its size (rrx_search_all_longest_marks_words) and the rejection of marks_words < nitems + 1 are those of rrx_group_spans_extents.
+ * Fully asynchronous - no read-back, no scratch - and capturable into a graph once the handle's tables are on the device.  A lane
+ * per ITEM walks the item's slots in order (kernels_group_items.hip: longest_split_list_kernel), the two phases per slot:
+ * consecutive matches of an item share mark words, and a lane's stores to them follow one another.  Launched as rrx_group_spans_*
+ * launches; an absent part's copy and the empty language's fill run over the slot range as a small kernel (the host does not know
+ * the range).  An item with many matches is one lane's work.                                                                      */
+int rrx_group_spans_list_extents(const rrx_group *grp, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                 const uint64_t *d_first, const uint32_t *d_match_start, const uint32_t *d_match_end, uint32_t *d_marks,
+                                 size_t marks_words, uint32_t *d_group_start, uint32_t *d_group_end, void *stream);
+int rrx_group_spans_list_items(const rrx_group *grp, const rrx_items *items, const uint64_t *d_first, const uint32_t *d_match_start,
+                               const uint32_t *d_match_end, uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start,
+                               uint32_t *d_group_end, void *stream);
+
+/* regexp_replace WITH GROUP REFERENCES: regexp_replace(col, '([0-9]+)/([0-9]+)/([0-9]+)', '\3-\1-\2').
+ * THE TEMPLATE (rrx_template, host only to compile): the bytes of `rep` are literal except '\': \0 ... \9 is a reference (0 the
+ * whole match; ONE digit: \12 is group 1 followed by a literal 2), \\ is one backslash; any other byte behind '\' and a trailing
+ * '\' give RRX_ERR_PATTERN with the offset of that '\' in rrx_last_error().  Adjacent literals merge; a template is at most 32
+ * segments (literals and references; more: RRX_ERR_UNSUPPORTED); the empty template is valid and has none.  rrx_template_refs: the
+ * distinct referenced groups >= 1 in ascending order into groups[0 .. cap), returns their number - the r-th of them is PLANE r
+ * below.  rrx_template_segments (for tests): refs[k] = -1 for a literal, else the referenced group; lit_lens[k] = the literal's
+ * length (0 for a reference), at most cap entries each; lits receives the literals' bytes one behind the other, at most lits_cap;
+ * returns the number of segments.  Null arrays are skipped.
+ * THE TWO GENERIC PASSES mirror rrx_replace_matches_sizes / _fill argument for argument, with BOTH d_start and d_end in both and, in
+ * place of the literal, the template and the spans of its references: word r * plane_stride + q of d_ref_start / d_ref_end is the
+ * span of plane r in slot q (relative to the item; plane_stride >= the largest slot + 1; both pointers may be null when the template
+ * references no group >= 1).  The replacement R_q of slot q is its segments one behind the other: a literal's bytes; for \0
+ * t[s':e') of the match; for \g t[s':e') of its plane's span - s' = min(s, L), e' = clamp(e, s', L) for an item of L bytes, and a
+ * start of 0xFFFFFFFF contributes nothing: no byte outside the item is read, whatever the arrays hold.  Everything else is the
+ * literal pair's with R_k in place of R: d_pos[slot] = where R_k begins in the output item, d_len[i] saturated, the output item
+ * t[0:s_0] + R_0 + t[e_0:s_1] + ... + R_{m-1} + t[e_{m-1}:] (the text behind a match from the raw d_end, a source offset at or beyond
+ * the item's end yields 0), exactly d_out[d_out_off[0] .. d_out_off[nitems]) written, d_out_off[0] any value, RRX_ERR_ARG for null
+ * arguments before any device call.  Both passes are fully asynchronous and capturable once the template has been used on that
+ * device (its first use uploads the segment program, 12 bytes per segment, and the literals).  The kernels
+ * (kernels_replace_template_items.hip) are the literal pair's with one walk over the segments per match (sizes) and per located
+ * byte (fill); the segment program is in LDS.  The literal entries are untouched and remain the faster way for a fixed R.
+ * THE ONE-CALL FORMS replace every leftmost-longest match of ONE pattern: groups[g - 1] is the rrx_group handle of group g of that
+ * pattern (null for a group the template does not reference; ngroups entries).  RRX_ERR_ARG before any device call: no handle is
+ * non-null, the non-null handles do not share their pattern's bytes, the template references a group without a handle, null
+ * arguments (d_out may be null when cap == 0).  The first non-null handle's rrx_group_regex searches; then
+ * rrx_group_spans_list_* into one plane per referenced group, the template's sizes, the scan, its fill.  All else mirrors
+ * rrx_replace_all_longest_extents: synchronous, temporaries allocated and freed by the call, d_out_off complete and *total exact
+ * either way, not a byte of d_out written when *total > cap, RRX_ERR_UNSUPPORTED for an output item of 2^30 bytes or more and
+ * exactly where the search returns it, nitems == 0: d_out_off[0] = 0; the empty language copies the items.  EACH GROUP'S SPAN
+ * FOLLOWS ITS OWN rrx_group RULE INDEPENDENTLY: for an ambiguous pattern the spans of two groups need not come from one parse
+ * (each is the longest-prefix rule above applied to that group's own A(B)C split; see the POSIX note there).  Out of scope, as for
+ * rrx_group: nested, repeated or alternated groups; $1 and \g<name>; replacing only the n-th match.                               */
+typedef struct rrx_template rrx_template;
+int rrx_template_compile(const void *rep, size_t rep_len, rrx_template **out);
+void rrx_template_free(rrx_template *tpl);
+size_t rrx_template_refs(const rrx_template *tpl, int *groups, size_t cap);
+size_t rrx_template_segments(const rrx_template *tpl, int *refs, uint32_t *lit_lens, size_t cap, void *lits, size_t lits_cap);
+int rrx_replace_template_sizes(int device, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint64_t *d_first, const uint32_t *d_start,
+                               const uint32_t *d_end, const rrx_template *tpl, const uint32_t *d_ref_start, const uint32_t *d_ref_end,
+                               size_t plane_stride, uint32_t *d_len, uint32_t *d_pos, void *stream);
+int rrx_replace_template_fill(int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint64_t *d_first,
+                              const uint32_t *d_start, const uint32_t *d_end, const uint32_t *d_pos, const rrx_template *tpl,
+                              const uint32_t *d_ref_start, const uint32_t *d_ref_end, size_t plane_stride, const uint64_t *d_out_off, void *d_out,
+                              void *stream);
+int rrx_replace_groups_longest_extents(const rrx_group *const *groups, size_t ngroups, const rrx_template *tpl, int device, const void *d_bytes,
+                                       const uint64_t *d_off, size_t nitems, uint32_t trim, uint64_t *d_out_off, void *d_out, size_t cap,
+                                       size_t *total, void *stream);
+int rrx_replace_groups_longest_items(const rrx_group *const *groups, size_t ngroups, const rrx_template *tpl, const rrx_items *items,
+                                     uint64_t *d_out_off, void *d_out, size_t cap, size_t *total, void *stream);
 
 /* ONE device-resident string of any length (regex.h:156-159: operator++ consumes the whole string; '\n' and every
  * other byte are ordinary, a NUL or a byte >= 0x80 rejects).  d_accept[0] = 1 iff accepted.  Strings of 32 KiB and

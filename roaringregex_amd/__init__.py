@@ -59,6 +59,9 @@ ABI_SYMBOLS = (
     "rrx_split_longest_items",
     "rrx_group_compile", "rrx_group_compile_ex", "rrx_group_free", "rrx_group_regex", "rrx_group_part", "rrx_group_program_words",
     "rrx_group_spans_extents", "rrx_group_spans_items", "rrx_extract_group_longest_extents", "rrx_extract_group_longest_items",
+    "rrx_group_spans_list_extents", "rrx_group_spans_list_items",
+    "rrx_template_compile", "rrx_template_free", "rrx_template_refs", "rrx_template_segments",
+    "rrx_replace_template_sizes", "rrx_replace_template_fill", "rrx_replace_groups_longest_extents", "rrx_replace_groups_longest_items",
 )
 
 
@@ -171,6 +174,16 @@ def _load():
         "rrx_group_spans_items": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
         "rrx_extract_group_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, sz, vp, vp, vp]),
         "rrx_extract_group_longest_items": (i32, [vp, vp, vp, sz, vp, vp, vp]),
+        "rrx_group_spans_list_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "rrx_group_spans_list_items": (i32, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "rrx_template_compile": (i32, [vp, sz, C.POINTER(vp)]),
+        "rrx_template_free": (None, [vp]),
+        "rrx_template_refs": (sz, [vp, vp, sz]),
+        "rrx_template_segments": (sz, [vp, vp, vp, sz, vp, sz]),
+        "rrx_replace_template_sizes": (i32, [i32, vp, sz, u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "rrx_replace_template_fill": (i32, [i32, vp, vp, sz, u32, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "rrx_replace_groups_longest_extents": (i32, [vp, sz, vp, i32, vp, vp, sz, u32, vp, vp, sz, C.POINTER(sz), vp]),
+        "rrx_replace_groups_longest_items": (i32, [vp, sz, vp, vp, vp, vp, sz, C.POINTER(sz), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -270,6 +283,83 @@ def replace_matches(data, offsets, first, start, end, repl, trim=0, stream=None)
         rep = torch.frombuffer(bytearray(repl), dtype=torch.uint8).to(data.device) if repl else torch.empty(0, dtype=torch.uint8, device=data.device)
         _check(_L.rrx_replace_matches_fill(d, _ptr(data), _ptr(offsets), n, trim, _ptr(first), _ptr(end), _ptr(pos), _ptr(rep), len(repl), _ptr(out_off),
                                            _ptr(out), s))
+    return out, out_off
+
+
+class Template:
+    """A replacement with group references (rrx_template): bytes are literal except b"\\": \\0 ... \\9 is a reference (0 the whole
+    match, one digit: \\12 is group 1 and a literal 2), \\\\ one backslash; anything else behind a backslash raises RRegexError with
+    the offset.  At most 32 segments.  Template(rb"\\3-\\1-\\2").refs == (1, 2, 3)."""
+
+    def __init__(self, repl):
+        if isinstance(repl, str):
+            repl = repl.encode("latin-1")
+        assert isinstance(repl, (bytes, bytearray))
+        self.repl = bytes(repl)
+        self._h = C.c_void_p()
+        _check(_L.rrx_template_compile(self.repl, len(self.repl), C.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _L is not None:
+            _L.rrx_template_free(self._h)
+            self._h = None
+
+    @property
+    def refs(self):
+        """The distinct referenced groups >= 1, ascending: the r-th is plane r of replace_template."""
+        n = _L.rrx_template_refs(self._h, None, 0)
+        out = (C.c_int * max(n, 1))()
+        _L.rrx_template_refs(self._h, out, n)
+        return tuple(out[:n])
+
+    @property
+    def segments(self):
+        """The segments in order: bytes for a literal, an int for a reference."""
+        n = _L.rrx_template_segments(self._h, None, None, 0, None, 0)
+        refs, lens, lits = (C.c_int * max(n, 1))(), (C.c_uint32 * max(n, 1))(), C.create_string_buffer(max(len(self.repl), 1))
+        _L.rrx_template_segments(self._h, refs, lens, n, lits, len(self.repl))
+        out, at = [], 0
+        for k in range(n):
+            if refs[k] < 0:
+                out.append(lits.raw[at:at + lens[k]])
+                at += lens[k]
+            else:
+                out.append(int(refs[k]))
+        return tuple(out)
+
+
+def replace_template(data, offsets, first, start, end, template, ref_start=None, ref_end=None, plane_stride=None, trim=0, stream=None):
+    """replace_matches with a Template in place of the literal (rrx_replace_template_sizes, a torch.cumsum, rrx_replace_template_fill):
+    ref_start / ref_end hold the span of plane r (the r-th of template.refs) in slot q at index r * plane_stride + q, relative to the
+    item, -1 for "none" - for example RGroup.spans_list_extents' outputs, one group behind the other; plane_stride defaults to
+    start.numel().  They may be left out when the template references no group >= 1.  -> (out uint8, out_off int64[n + 1]).  Waits
+    for the output's size."""
+    import torch
+    n, d = _batch(data, offsets)[:2]
+    assert isinstance(template, Template)
+    assert first.is_cuda and first.dtype in (torch.int64, torch.uint64) and first.is_contiguous() and first.numel() == n + 1
+    assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() for t in (start, end)) and start.numel() == end.numel()
+    nrefs = len(template.refs)
+    stride = int(plane_stride) if plane_stride is not None else start.numel()
+    if nrefs:
+        assert all(t is not None and t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() for t in (ref_start, ref_end))
+        assert stride >= start.numel() and min(ref_start.numel(), ref_end.numel()) >= (nrefs - 1) * stride + start.numel()
+    with _on(d, stream):
+        s = _stream_ptr(stream)
+        if not start.numel():                      # (the entries take no null array, even where the lists are empty)
+            start = end = torch.zeros(1, dtype=torch.int32, device=data.device)
+        if not nrefs or not ref_start.numel():
+            ref_start = ref_end = torch.zeros(1, dtype=torch.int32, device=data.device)
+        length = torch.empty(n, dtype=torch.int32, device=data.device)
+        pos = torch.empty(start.numel(), dtype=torch.int32, device=data.device)
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
+        _check(_L.rrx_replace_template_sizes(d, _ptr(offsets), n, trim, _ptr(first), _ptr(start), _ptr(end), template._h, _ptr(ref_start), _ptr(ref_end),
+                                             stride, _ptr(length), _ptr(pos), s))
+        torch.cumsum(length.to(torch.int64) & 0xFFFFFFFF, dim=0, out=out_off[1:])
+        total = int(out_off[-1].item())
+        out = torch.empty(total, dtype=torch.uint8, device=data.device)
+        _check(_L.rrx_replace_template_fill(d, _ptr(data), _ptr(offsets), n, trim, _ptr(first), _ptr(start), _ptr(end), _ptr(pos), template._h,
+                                            _ptr(ref_start), _ptr(ref_end), stride, _ptr(out_off), _ptr(out), s))
     return out, out_off
 
 
@@ -810,7 +900,7 @@ class RRegex:
 
     def replace_all_longest_extents(self, data, offsets, repl, trim=0, cap=None, stream=None):
         """regexp_replace on a string column (rrx_replace_all_longest_extents): item i = data[offsets[i] : offsets[i+1] - trim] with
-        EVERY LEFTMOST-LONGEST match replaced by the literal `repl` (bytes; no group references) -> (out uint8, out_off int64[n + 1]),
+        EVERY LEFTMOST-LONGEST match replaced by the literal `repl` (bytes; group references: replace_groups_longest_extents) -> (out uint8, out_off int64[n + 1]),
         output item i = out[out_off[i] : out_off[i + 1]] - re.sub(p, lambda m: repl, item); the separators are not copied.  cap: bytes
         to provide for at first (default: the size of `data`); the call is repeated with the exact size if the column is larger."""
         assert isinstance(repl, (bytes, bytearray))
@@ -1147,6 +1237,31 @@ class RGroup:
                                             _stream_ptr(stream)))
         return start, end
 
+    def spans_list_extents(self, data, offsets, first, match_start, match_end, trim=0, out=None, marks=None, stream=None):
+        """spans_extents for every match of a match list (rrx_group_spans_list_extents): match k of item i is slot first[i] + k of
+        match_start / match_end, as every search_all*_fused method returns them -> (start, end) int32 indexed by the slot, (-1, -1)
+        where the slot has no split.  out: the two result tensors (at least first[-1] entries); they may be match_start / match_end
+        themselves.  Asynchronous."""
+        n, d, b, o = _batch(data, offsets)
+        with _on(d, stream):
+            start, end = self._outputs(match_start.numel(), data.device, out)
+            if marks is None:
+                marks = self._marks(data, n)[0]
+            _check(_L.rrx_group_spans_list_extents(self._h, d, b, o, n, trim, _ptr(first), _ptr(match_start), _ptr(match_end), _ptr(marks), marks.numel(),
+                                                   _ptr(start), _ptr(end), _stream_ptr(stream)))
+        return start, end
+
+    def spans_list_items(self, items, first, match_start, match_end, out=None, marks=None, stream=None):
+        """The same for an indexed batch (rrx_group_spans_list_items)."""
+        n = items.num_items
+        with _on(items.device, stream):
+            start, end = self._outputs(match_start.numel(), items.data.device, out)
+            if marks is None:
+                marks = self._marks(items.data, n)[0]
+            _check(_L.rrx_group_spans_list_items(self._h, items._h, _ptr(first), _ptr(match_start), _ptr(match_end), _ptr(marks), marks.numel(), _ptr(start),
+                                                 _ptr(end), _stream_ptr(stream)))
+        return start, end
+
     def extract_extents(self, data, offsets, trim=0, out=None, marks=None, stream=None):
         """The group's span per item of a batch nobody has indexed, the search included (rrx_extract_group_longest_extents): item i =
         data[offsets[i] : offsets[i+1] - trim] -> (start, end) int32, (-1, -1) where nothing is accepted.  Nothing is read back: with
@@ -1188,3 +1303,34 @@ class RGroup:
             out = torch.empty(int(out_off[-1].item()), dtype=torch.uint8, device=data.device)
             _check(_L.rrx_pieces_fill(d, _ptr(data), _ptr(src), _ptr(out_off), n, _ptr(out), _stream_ptr(stream)))
         return valid, out_off, out
+
+
+def _group_handles(groups):
+    """The handle array of the one-call forms: groups[g - 1] is the RGroup of group g, None where the template does not use it."""
+    assert len(groups) and all(g is None or isinstance(g, RGroup) for g in groups)
+    return (C.c_void_p * len(groups))(*[g._h if g is not None else None for g in groups])
+
+
+def replace_groups_longest_extents(groups, template, data, offsets, trim=0, cap=None, stream=None):
+    """regexp_replace with group references on a string column (rrx_replace_groups_longest_extents): item i = data[offsets[i] :
+    offsets[i+1] - trim] with EVERY LEFTMOST-LONGEST match of the groups' pattern replaced by `template` (a Template, or bytes) ->
+    (out uint8, out_off int64[n + 1]).  groups[g - 1] is the RGroup of group g of ONE pattern (None for a group the template does not
+    reference); each group's span follows RGroup's rule on its own.  cap: bytes to provide for at first (default: the size of
+    `data`); the call is repeated with the exact size if the column is larger."""
+    tpl = template if isinstance(template, Template) else Template(template)
+    h = _group_handles(groups)
+    n, d, b, o = _batch(data, offsets)
+    with _on(d, stream):
+        s = _stream_ptr(stream)
+        return RRegex._replace_one_call(None, data.device, n, int(cap) if cap is not None else data.numel(),
+                                        lambda f, out, cp, tot: _L.rrx_replace_groups_longest_extents(h, len(groups), tpl._h, d, b, o, n, trim, f, out, cp, tot, s))
+
+
+def replace_groups_longest_items(groups, template, items, cap=None, stream=None):
+    """The same for an indexed batch (rrx_replace_groups_longest_items) -> (out uint8, out_off int64[n + 1])."""
+    tpl = template if isinstance(template, Template) else Template(template)
+    h = _group_handles(groups)
+    with _on(items.device, stream):
+        s = _stream_ptr(stream)
+        return RRegex._replace_one_call(None, items.data.device, items.num_items, int(cap) if cap is not None else items.data.numel(),
+                                        lambda f, out, cp, tot: _L.rrx_replace_groups_longest_items(h, len(groups), tpl._h, items._h, f, out, cp, tot, s))

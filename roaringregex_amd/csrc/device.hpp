@@ -345,6 +345,16 @@ struct GroupDevice {
 int longest_split_dfa(const DfaDevice &rev, const DfaDevice &fwd, bool in_global, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
                       const uint32_t *lo, const uint32_t *hi, uint32_t *marks, size_t marks_words, uint32_t *out, uint32_t *on_none, void *stream);
 
+// The same for every match of a match list (first: nitems + 1 entries, match k of item i is slot first[i] + k; lo, hi, out and
+// on_none are indexed by the slot itself): a lane per item walking its slots, exactly the slots first[0] .. first[nitems] written.
+// The marks as above, except that the consecutive slots of an item store the words they share one after the other.
+int longest_split_list_dfa(const DfaDevice &rev, const DfaDevice &fwd, bool in_global, const uint8_t *bytes, const uint64_t *off, size_t nitems,
+                           uint32_t trim, const uint64_t *first, const uint32_t *lo, const uint32_t *hi, uint32_t *marks, size_t marks_words, uint32_t *out,
+                           uint32_t *on_none, void *stream);
+// The slots first[0] .. first[nitems] of dst_a and dst_b (either may be null: left out), copied from src_a / src_b or, where that is
+// null, filled with ~0u: the slot range is known on the device only.
+int slot_range_copy(const uint64_t *first, size_t nitems, const uint32_t *src_a, uint32_t *dst_a, const uint32_t *src_b, uint32_t *dst_b, void *stream);
+
 // ---- regexp_replace on explicit items, from a match list: kernels_replace_items.hip
 // Item i = bytes[off[i] .. off[i+1] - trim); its matches are the slots first[i] .. first[i + 1] of match_start / match_end (relative
 // to the item, in order, not overlapping: what every search_all* launcher above leaves); R = `rep_len` literal bytes.  The output
@@ -361,6 +371,25 @@ int replace_sizes(const uint64_t *off, size_t nitems, uint32_t trim, const uint6
                   uint32_t rep_len, uint32_t *len, uint32_t *pos, uint32_t *too_long, void *stream);
 int replace_fill(const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim, const uint64_t *first, const uint32_t *match_end,
                  const uint32_t *pos, const uint8_t *rep, uint32_t rep_len, const uint64_t *out_off, uint8_t *out, void *stream);
+
+// ---- regexp_replace with group references, from a match list and reference spans: kernels_replace_template_items.hip
+// The replacement of slot q is the concatenation of the template's segments (template.hpp), at most kTemplateMaxSegments: the bytes
+// of a literal, item[s', e') of the match itself (kind 1) or of plane r's span (kind 2 + r: words r * plane_stride + q of ref_start /
+// ref_end), s' = min(s, L), e' = clamp(e, s', L), nothing for a start of ~0u.  The segment program is three words per segment (kind,
+// the literal's offset into `lits`, its length) in device memory; the kernels keep it in LDS.
+constexpr uint32_t kTemplateMaxSegments = 32;
+struct TemplateDevice {
+    const uint32_t *segs = nullptr;              // nseg x 3 words
+    const uint8_t *lits = nullptr;               // the literals' bytes, one behind the other
+    uint32_t nseg = 0;
+};
+// replace_template_sizes / _fill: replace_sizes / replace_fill with R_k, the replacement of slot k, in place of R.
+int replace_template_sizes(const TemplateDevice &tpl, const uint64_t *off, size_t nitems, uint32_t trim, const uint64_t *first, const uint32_t *match_start,
+                           const uint32_t *match_end, const uint32_t *ref_start, const uint32_t *ref_end, uint64_t plane_stride, uint32_t *len, uint32_t *pos,
+                           uint32_t *too_long, void *stream);
+int replace_template_fill(const TemplateDevice &tpl, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim, const uint64_t *first,
+                          const uint32_t *match_start, const uint32_t *match_end, const uint32_t *pos, const uint32_t *ref_start, const uint32_t *ref_end,
+                          uint64_t plane_stride, const uint64_t *out_off, uint8_t *out, void *stream);
 
 // ---- regexp_extract_all / split on explicit items, from a match list: kernels_pieces_items.hip
 // Items and lists as for replace_sizes.  The PIECES of item i are its matches (gaps == false: m of them) or what lies between them

@@ -1,6 +1,8 @@
 // group.cpp — rrx_group: a pattern A(B)C split at one top-level capture group (frontend.hpp: split_group), its four anchored tables,
 // and the entries that turn the leftmost-longest match of every item into the group's span (rrx_group_spans_* /
-// rrx_extract_group_longest_*): the longest split point (kernels_group_items.hip), launched once per part that is there.
+// rrx_extract_group_longest_*): the longest split point (kernels_group_items.hip), launched once per part that is there.  Also
+// the same for every match of a match list (rrx_group_spans_list_*) and regexp_replace with group references in one call
+// (rrx_replace_groups_longest_*), which needs the handles' insides.
 #include <cstring>
 
 #include "items.hpp"
@@ -83,12 +85,112 @@ int group_spans(const rrx_group *g, const ItemBatch &b, const uint32_t *in_start
     return RRX_OK;
 }
 
+// group_spans for every match of a match list: the arrays are indexed by the slot, the slot range d_first[0] .. d_first[nitems] is
+// known on the device only - an absent part's copy and the empty language's fill are a small kernel over it, not a memcpy.
+int group_spans_list(const rrx_group *g, const ItemBatch &b, const uint64_t *d_first, const uint32_t *in_start, const uint32_t *in_end, ItemMarks m,
+                     uint32_t *d_start, uint32_t *d_end, void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
+    if (!nitems) return RRX_OK;
+    const dev::GroupDevice *t = nullptr;
+    if (!g->empty) {
+        const int rc = g->tables(device, &t);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipSetDevice(device));
+    if (g->empty) return launched(dev::slot_range_copy(d_first, nitems, nullptr, d_start, nullptr, d_end, stream), "group list fill launch");
+    {
+        uint32_t *copy_start = !g->has_a && d_start != in_start ? d_start : nullptr, *copy_end = !g->has_c && d_end != in_end ? d_end : nullptr;
+        const int rc = launched(dev::slot_range_copy(d_first, nitems, in_start, copy_start, in_end, copy_end, stream), "group list copy launch");
+        if (rc) return rc;
+    }
+    if (g->has_a) {
+        const int rc = launched(dev::longest_split_list_dfa(t->rev_bc, t->a, g->in_global(), bytes, off, nitems, trim, d_first, in_start, in_end, m.words,
+                                                            m.nwords, d_start, d_end, stream),
+                                "group list split (A | BC) launch");
+        if (rc) return rc;
+    }
+    if (g->has_c) {
+        const uint32_t *lo = g->has_a ? d_start : in_start;
+        const int rc = launched(dev::longest_split_list_dfa(t->rev_c, t->b, g->in_global(), bytes, off, nitems, trim, d_first, lo, in_end, m.words, m.nwords,
+                                                            d_end, d_start, stream),
+                                "group list split (B | C) launch");
+        if (rc) return rc;
+    }
+    return RRX_OK;
+}
+
 // rrx_search_longest_* on the whole pattern into the group arrays, then the launches in place
 int group_extract(const rrx_group *g, const ItemBatch &b, ItemMarks m, uint32_t *d_start, uint32_t *d_end, void *stream) {
     if (!b.nitems) return RRX_OK;
     const int rc = rrx_search_longest_extents(g->whole, b.device, b.bytes, b.off, b.nitems, b.trim, d_start, d_end, stream);
     if (rc || g->empty) return rc;          // (the empty language: the search has filled both arrays)
     return group_spans(g, b, d_start, d_end, m, d_start, d_end, stream);
+}
+
+
+// regexp_replace with group references in one call: rrx_replace_all_longest_*'s steps with the spans of the referenced groups between
+// the match list and the sizes - one plane per referenced group, each from its own handle - and the template's two passes in place
+// of the literal ones.  groups[g - 1]: the handle of group g of ONE pattern; the first one there is searches.
+int replace_groups_one_call(const rrx_group *const *groups, size_t ngroups, const rrx_template *tpl, const ItemBatch &b, uint64_t *d_out_off, void *d_out,
+                            size_t cap, size_t *total, void *stream) {
+    const auto &[device, bytes, off, nitems, trim] = b;
+    if (!groups || !tpl || !total || !d_out_off || (nitems && (!off || (cap && !d_out)))) return fail(RRX_ERR_ARG, "null argument");
+    const rrx_group *lead = nullptr;
+    for (size_t k = 0; k < ngroups; k++) {
+        if (!groups[k]) continue;
+        if (!lead) lead = groups[k];
+        else if (groups[k]->whole->pattern != lead->whole->pattern) return fail(RRX_ERR_ARG, "the group handles are not of one pattern");
+    }
+    if (!lead) return fail(RRX_ERR_ARG, "no group handle");
+    for (int ref : tpl->t.refs)
+        if ((size_t)ref > ngroups || !groups[ref - 1]) return fail(RRX_ERR_ARG, "the template references group " + std::to_string(ref) + ", which has no handle");
+    const rrx_regex *re = lead->whole;
+    *total = 0;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = search_longest_tables_on(re, device);
+    if (rc) return rc;
+    if (!nitems) { HIP_TRY(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
+    dev::TemplateDevice t;
+    rc = tpl->on(device, &t);
+    if (rc) return rc;
+    LongestMatchList m;
+    rc = m.count(re, b, "hipMalloc(replace prefix)", stream);
+    if (rc) return rc;
+    // (one word more than the lists need: the generic kernels are never handed a null array; the last word of d_len is the flag)
+    const size_t nplanes = tpl->t.refs.size(), stride = m.nmatches;
+    DeviceArray<uint32_t> d_pos, d_len, d_ref_start, d_ref_end;
+    hipError_t he = m.alloc_lists(device);
+    if (he == hipSuccess) he = d_pos.alloc(device, (m.nmatches + 1) * sizeof(uint32_t));
+    if (he == hipSuccess) he = d_len.alloc(device, (nitems + 1) * sizeof(uint32_t));
+    if (he == hipSuccess) he = d_ref_start.alloc(device, (nplanes * stride + 1) * sizeof(uint32_t));
+    if (he == hipSuccess) he = d_ref_end.alloc(device, (nplanes * stride + 1) * sizeof(uint32_t));
+    if (he != hipSuccess) return hip_fail(he, "hipMalloc(replace lists)");
+    rc = m.fill(re, b, stream);
+    if (rc) return rc;
+    // the marks of the count pass have served the fill: the planes' launches take the buffer over, one after the other on the stream
+    for (size_t r = 0; r < nplanes && m.nmatches; r++) {
+        rc = group_spans_list(groups[tpl->t.refs[r] - 1], b, m.first, m.start, m.end, {m.c.marks, m.c.nwords}, d_ref_start + r * stride, d_ref_end + r * stride,
+                              stream);
+        if (rc) return rc;
+    }
+    uint32_t *d_flag = d_len + nitems;
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st));
+    int le = dev::replace_template_sizes(t, off, nitems, trim, m.first, m.start, m.end, d_ref_start, d_ref_end, stride, d_len, d_pos, d_flag, stream);
+    if (le) return hip_fail((hipError_t)le, "replace sizes and scan launch");
+    uint64_t tot = 0;
+    uint32_t flag = 0;
+    rc = scan_total(d_len, d_out_off, m.c.sums, nitems, stream, "replace sizes and scan launch", "replace scan", &tot, d_flag, &flag);
+    if (rc) return rc;
+    if (flag) return fail(RRX_ERR_UNSUPPORTED, "an output item of 2^30 bytes or more: use rrx_search_all_longest_extents, rrx_group_spans_list_extents and the two passes rrx_replace_template_sizes / _fill");
+    *total = (size_t)tot;
+    if (tot && tot <= cap) {                                                     // a column beyond cap: not a byte of it is written
+        le = dev::replace_template_fill(t, bytes, off, nitems, trim, m.first, m.start, m.end, d_pos, d_ref_start, d_ref_end, stride, d_out_off,
+                                        static_cast<uint8_t *>(d_out), stream);
+        if (le) return hip_fail((hipError_t)le, "replace_template_fill launch");
+        he = hipStreamSynchronize(st);
+        if (he != hipSuccess) return hip_fail(he, "replace fill");
+    }
+    return RRX_OK;
 }
 
 }  // namespace
@@ -168,6 +270,31 @@ int rrx_group_spans_items(const rrx_group *grp, const rrx_items *it, const uint3
     if (!it) return fail(RRX_ERR_ARG, kGroupArgError);
     return rrx_group_spans_extents(grp, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_match_start, d_match_end, d_marks, marks_words, d_group_start,
                                    d_group_end, stream);
+}
+int rrx_group_spans_list_extents(const rrx_group *grp, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                                 const uint64_t *d_first, const uint32_t *d_match_start, const uint32_t *d_match_end, uint32_t *d_marks, size_t marks_words,
+                                 uint32_t *d_group_start, uint32_t *d_group_end, void *stream) {
+    const ItemBatch b = batch_of(device, d_bytes, d_off, nitems, trim);
+    if (!group_args_ok(grp, b, {d_marks, marks_words}, d_group_start, d_group_end) || !batch_args_ok(grp, b, {d_first, d_match_start, d_match_end}))
+        return fail(RRX_ERR_ARG, kGroupArgError);
+    return group_spans_list(grp, b, d_first, d_match_start, d_match_end, {d_marks, marks_words}, d_group_start, d_group_end, stream);
+}
+int rrx_group_spans_list_items(const rrx_group *grp, const rrx_items *it, const uint64_t *d_first, const uint32_t *d_match_start,
+                               const uint32_t *d_match_end, uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start, uint32_t *d_group_end,
+                               void *stream) {
+    if (!it) return fail(RRX_ERR_ARG, kGroupArgError);
+    return rrx_group_spans_list_extents(grp, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_first, d_match_start, d_match_end, d_marks,
+                                        marks_words, d_group_start, d_group_end, stream);
+}
+int rrx_replace_groups_longest_extents(const rrx_group *const *groups, size_t ngroups, const rrx_template *tpl, int device, const void *d_bytes,
+                                       const uint64_t *d_off, size_t nitems, uint32_t trim, uint64_t *d_out_off, void *d_out, size_t cap, size_t *total,
+                                       void *stream) {
+    return replace_groups_one_call(groups, ngroups, tpl, batch_of(device, d_bytes, d_off, nitems, trim), d_out_off, d_out, cap, total, stream);
+}
+int rrx_replace_groups_longest_items(const rrx_group *const *groups, size_t ngroups, const rrx_template *tpl, const rrx_items *it, uint64_t *d_out_off,
+                                     void *d_out, size_t cap, size_t *total, void *stream) {
+    if (!it) return fail(RRX_ERR_ARG, "null argument");
+    return replace_groups_one_call(groups, ngroups, tpl, batch_of(it), d_out_off, d_out, cap, total, stream);
 }
 int rrx_extract_group_longest_extents(const rrx_group *grp, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                                       uint32_t *d_marks, size_t marks_words, uint32_t *d_group_start, uint32_t *d_group_end, void *stream) {

@@ -21,6 +21,7 @@
 #include "pack.hpp"
 #include "plan.hpp"
 #include "sampled.hpp"
+#include "template.hpp"
 
 // ---- errors: the calling thread's text behind rrx_last_error (regex.cpp)
 std::string &last_error();
@@ -268,4 +269,13 @@ struct rrx_items {
     DeviceAlloc d_index;
     mutable std::mutex mu;
     DeviceAlloc d_result;                // result bitmap of a match (one match at a time per handle)
+};
+
+// A replacement template (template.hpp: what the parser left) and, per device, its segment program and literals as the kernels of
+// kernels_replace_template_items.hip take them, uploaded at the first use there (item_columns.cpp).
+struct rrx_template {
+    rrx::ReplaceTemplate t;
+    mutable std::mutex mu;
+    mutable std::map<int, OnDevice<rrx::dev::TemplateDevice>> on_device;       // (under `mu`)
+    int on(int device, rrx::dev::TemplateDevice *out) const;
 };

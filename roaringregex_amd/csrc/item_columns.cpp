@@ -2,9 +2,40 @@
 // rrx_replace_all_longest_* in one call) and the list<binary> columns of regexp_extract_all and split (rrx_pieces_* from any match
 // list, rrx_extract_all_longest_* / rrx_split_longest_* in one call).  A one-call entry is the leftmost-longest match list of the
 // call's own (items.hpp: LongestMatchList), then what is the column's: sizes, a second scan, the cap rule and the fill.
+#include <cstring>
+
 #include "items.hpp"
 
 using namespace rrx;
+
+// The template on `device`, uploaded once (a synchronous copy: after it the two passes queue launches only), `device` made current.
+// Three words per segment - kind (0 a literal, 1 the match, 2 + r plane r), the literal's offset and length - then the literals.
+static_assert(kTemplateSegments == dev::kTemplateMaxSegments, "the parser's limit is what the kernels' LDS copy holds");
+int rrx_template::on(int device, dev::TemplateDevice *out) const {
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = on_device.find(device);
+    if (it == on_device.end()) {
+        OnDevice<dev::TemplateDevice> d;
+        std::vector<uint32_t> words;
+        for (const TemplateSegment &s : t.segs) {
+            words.push_back(s.ref < 0 ? 0u : s.ref == 0 ? 1u : 2u + (uint32_t)t.plane_of(s.ref));
+            words.push_back(s.lit_off);
+            words.push_back(s.lit_len);
+        }
+        const size_t seg_bytes = words.size() * sizeof(uint32_t);
+        hipError_t e = d.mem.alloc(device, seg_bytes + t.lits.size() + 16);
+        if (e == hipSuccess && seg_bytes) e = hipMemcpy(d.mem.p, words.data(), seg_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !t.lits.empty()) e = hipMemcpy(static_cast<uint8_t *>(d.mem.p) + seg_bytes, t.lits.data(), t.lits.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "replacement template upload");
+        d.d.segs = static_cast<const uint32_t *>(d.mem.p);
+        d.d.lits = static_cast<const uint8_t *>(d.mem.p) + seg_bytes;
+        d.d.nseg = (uint32_t)t.segs.size();
+        it = on_device.emplace(device, std::move(d)).first;
+    }
+    *out = it->second.d;
+    HIP_TRY(hipSetDevice(device));
+    return RRX_OK;
+}
 
 extern "C" {
 
@@ -79,6 +110,73 @@ int rrx_replace_all_longest_items(const rrx_regex *re, const rrx_items *it, cons
                                   size_t cap, size_t *total, void *stream) {
     if (!it) return fail(RRX_ERR_ARG, "null argument");
     return replace_all_longest_one_call(re, batch_of(it), rep, rep_len, d_out_off, d_out, cap, total, stream);
+}
+
+// Replacement templates (template.cpp parses; the handle keeps what the kernels take, per device).
+int rrx_template_compile(const void *rep, size_t rep_len, rrx_template **out) {
+    if (!out || (rep_len && !rep)) return fail(RRX_ERR_ARG, "null argument");
+    *out = nullptr;
+    std::unique_ptr<rrx_template> tpl(new rrx_template());
+    size_t at = 0;
+    switch (parse_template(static_cast<const uint8_t *>(rep), rep_len, tpl->t, &at)) {
+    case TemplateError::syntax:
+        return fail(RRX_ERR_PATTERN, "replacement template: '\\' at offset " + std::to_string(at) + " is followed by neither a digit nor '\\'");
+    case TemplateError::too_many_segments:
+        return fail(RRX_ERR_UNSUPPORTED, "replacement template: more than " + std::to_string(kTemplateSegments) + " segments");
+    case TemplateError::none:
+        break;
+    }
+    *out = tpl.release();
+    return RRX_OK;
+}
+void rrx_template_free(rrx_template *tpl) { delete tpl; }
+size_t rrx_template_refs(const rrx_template *tpl, int *groups, size_t cap) {
+    if (!tpl) return 0;
+    for (size_t k = 0; groups && k < tpl->t.refs.size() && k < cap; k++) groups[k] = tpl->t.refs[k];
+    return tpl->t.refs.size();
+}
+size_t rrx_template_segments(const rrx_template *tpl, int *refs, uint32_t *lit_lens, size_t cap, void *lits, size_t lits_cap) {
+    if (!tpl) return 0;
+    const auto &t = tpl->t;
+    for (size_t k = 0; k < t.segs.size() && k < cap; k++) {
+        if (refs) refs[k] = t.segs[k].ref;
+        if (lit_lens) lit_lens[k] = t.segs[k].lit_len;
+    }
+    if (lits && lits_cap) std::memcpy(lits, t.lits.data(), t.lits.size() < lits_cap ? t.lits.size() : lits_cap);
+    return t.segs.size();
+}
+
+// regexp_replace with group references from a match list and the references' spans (kernels_replace_template_items.hip): the two
+// passes of rrx_replace_matches_*, the replacement of a match put together from the template's segments.  Asynchronous but for the
+// template's first use on a device (its upload).
+static bool template_refs_ok(const rrx_template *tpl, size_t nitems, const uint32_t *d_ref_start, const uint32_t *d_ref_end) {
+    return tpl && (!nitems || tpl->t.refs.empty() || (d_ref_start && d_ref_end));
+}
+int rrx_replace_template_sizes(int device, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint64_t *d_first, const uint32_t *d_start,
+                               const uint32_t *d_end, const rrx_template *tpl, const uint32_t *d_ref_start, const uint32_t *d_ref_end, size_t plane_stride,
+                               uint32_t *d_len, uint32_t *d_pos, void *stream) {
+    if (!template_refs_ok(tpl, nitems, d_ref_start, d_ref_end) || (nitems && (!d_off || !d_first || !d_start || !d_end || !d_len || !d_pos)))
+        return fail(RRX_ERR_ARG, "null argument");
+    if (!nitems) return RRX_OK;
+    dev::TemplateDevice t;
+    const int rc = tpl->on(device, &t);
+    if (rc) return rc;
+    return launched(dev::replace_template_sizes(t, d_off, nitems, trim, d_first, d_start, d_end, d_ref_start, d_ref_end, plane_stride, d_len, d_pos, nullptr,
+                                                stream),
+                    "replace_template_sizes launch");
+}
+int rrx_replace_template_fill(int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint64_t *d_first,
+                              const uint32_t *d_start, const uint32_t *d_end, const uint32_t *d_pos, const rrx_template *tpl, const uint32_t *d_ref_start,
+                              const uint32_t *d_ref_end, size_t plane_stride, const uint64_t *d_out_off, void *d_out, void *stream) {
+    if (!template_refs_ok(tpl, nitems, d_ref_start, d_ref_end) || (nitems && (!d_off || !d_first || !d_start || !d_end || !d_pos || !d_out_off)))
+        return fail(RRX_ERR_ARG, "null argument");
+    if (!nitems) return RRX_OK;
+    dev::TemplateDevice t;
+    const int rc = tpl->on(device, &t);
+    if (rc) return rc;
+    return launched(dev::replace_template_fill(t, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_first, d_start, d_end, d_pos, d_ref_start,
+                                               d_ref_end, plane_stride, d_out_off, static_cast<uint8_t *>(d_out), stream),
+                    "replace_template_fill launch");
 }
 
 // regexp_extract_all / split from a match list (kernels_pieces_items.hip): the pieces of every item as a list<binary> column.  The

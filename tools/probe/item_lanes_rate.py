@@ -43,6 +43,14 @@ items (offsets = the line starts, trim 1: the '\\n' is the separator):
                   alternating, host time per call - each returns behind its last synchronise -, the same four children and the same
                   margin as below, per entry; the lines go to `--out` as well.
 
+  replace_groups  regexp_replace with group references (kernels_replace_template_items.hip, longest_split_list_kernel) on the e-mail
+                  text, the pattern with its domain in parentheses: the one-call rrx_replace_groups_longest_extents with the
+                  templates \\0, a literal and \\1 beside rrx_replace_all_longest_extents with the same literal - the parent commit's
+                  entry, its code untouched in this tree - and, to say where the time goes, the stages behind them on lists found
+                  once: rrx_replace_matches_sizes / _fill (the literal), rrx_replace_template_sizes / _fill with the template literal
+                  and with \\1, and rrx_group_spans_list_extents; all alternating inside one process.  One child, this tree alone;
+                  the lines and a summary (what a group reference costs over the literal path) go to `--out` as well.
+
 A yardstick stands in only for a parent that lacks the entry (its wrapper shows it): a later parent runs the entry itself, and both
 sides must find the same.
 
@@ -56,6 +64,7 @@ between its two medians and its own spread - and whether each of the tree's medi
     python tools/probe/item_lanes_rate.py --entry replace [--launches 15] [--scale 1.0] [--out profiles/replace_items_rate.txt]
     python tools/probe/item_lanes_rate.py --entry pieces [--launches 15] [--scale 1.0] [--out profiles/pieces_items_rate.txt]
     python tools/probe/item_lanes_rate.py --entry one_call [--old .oldtree] [--launches 15] [--out profiles/one_call_items_rate.txt]
+    python tools/probe/item_lanes_rate.py --entry replace_groups [--launches 15] [--scale 1.0] [--out profiles/replace_template_items_rate.txt]
 """
 import argparse
 import json
@@ -66,7 +75,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CONFIGS = (("url", "U2", 1 << 30), ("email", "EMAIL", 1 << 30), ("kwlog", "K1000C", 1 << 30))
-ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "extract_group", "replace", "pieces", "one_call")
+ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "extract_group", "replace", "pieces", "one_call", "replace_groups")
 GROUPED = {"EMAIL": r"[A-Za-z0-9._]+@([A-Za-z0-9.]+)"}      # --entry extract_group: the patterns that need a group put in; group 1 everywhere
 SKEW_ITEMS, SKEW_ITEM_BYTES = 64, 16 << 20     # the skewed batch of --entry pieces: its first 64 items are merged lines of 16 MiB or more
 YARDSTICK = {"search_all_longest": "search_all", "extract_group": "search_longest"}   # entries the parent lacks: what its side runs instead
@@ -93,7 +102,9 @@ def child(tree, entry, kind, pkey, nbytes, launches):
     grouped = pkey.endswith("+group")              # (--entry extract_group: both sides on the pattern as that entry takes it)
     pkey = pkey.split("+")[0]
     pattern = GROUPED.get(pkey, patterns()[pkey]) if grouped else patterns()[pkey]
-    r = rr.RGroup(pattern, 1) if entry == "extract_group" else rr.RRegex(pattern)
+    if entry == "replace_groups":
+        pattern = GROUPED[pkey]
+    r = rr.RGroup(pattern, 1) if entry in ("extract_group", "replace_groups") else rr.RRegex(pattern)
     host = synth.corpus(kind, 1, nbytes, threads=min(len(os.sched_getaffinity(0)), 16))
     host = host[:int(np.nonzero(host == 10)[0][-1]) + 1]
     dev = torch.from_numpy(host).cuda()
@@ -105,6 +116,8 @@ def child(tree, entry, kind, pkey, nbytes, launches):
         return pieces_child(rr, r, kind, dev, off, launches, skew)
     if entry == "one_call":
         return one_call_child(rr, r, kind, dev, off, launches)
+    if entry == "replace_groups":
+        return replace_groups_child(rr, r, kind, dev, off, n, launches)
 
     if entry in ("match", "contains"):
         slices = [off[k:k + SLICE + 1] for k in range(0, n, SLICE)]
@@ -193,6 +206,92 @@ def replace_child(rr, r, kind, dev, off, n, launches):
         line["fill_GB/s"] = round(total / med["fill"] / 1e6, 1)                     # bytes of the new column written
         line["fill_share_of_copy"] = round((total / med["fill"]) / (nbytes / med["copy"]), 4)
         print(json.dumps(line), flush=True)
+
+
+REPLACE_GROUPS_LITERAL = b"<dom>"
+
+
+def replace_groups_child(rr, g, kind, dev, off, n, launches):
+    """The four one-call forms and the stages behind them, alternating; one JSON line."""
+    import ctypes as C
+    import torch
+    L, s, nbytes, lit = rr._L, rr._stream_ptr(None), int(dev.numel()), REPLACE_GROUPS_LITERAL
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    r = g.regex
+    first, start, end = r.search_all_longest_extents_fused(dev, off, trim=1)
+    nmatches = int(start.numel())
+    handles = rr._group_handles([g])
+    templates = {"whole": rr.Template(rb"\0"), "literal": rr.Template(lit), "group": rr.Template(rb"\1")}
+    calls, totals, outs = {}, {}, {}
+    one_off, tot = torch.empty(n + 1, dtype=torch.int64, device="cuda"), C.c_size_t(0)
+    rr._check(L.rrx_replace_all_longest_extents(r._h, 0, ptr(dev), ptr(off), n, 1, lit, len(lit), ptr(one_off), None, 0, C.byref(tot), s))
+    totals["parent_literal"] = tot.value
+    for k, tpl in templates.items():
+        rr._check(L.rrx_replace_groups_longest_extents(handles, 1, tpl._h, 0, ptr(dev), ptr(off), n, 1, ptr(one_off), None, 0, C.byref(tot), s))
+        totals[k] = tot.value
+    assert totals["literal"] == totals["parent_literal"] and totals["whole"] == nbytes - n, totals
+    one_out = torch.empty(max(totals.values()), dtype=torch.uint8, device="cuda")
+    calls["one_call_parent_literal"] = lambda: rr._check(L.rrx_replace_all_longest_extents(r._h, 0, ptr(dev), ptr(off), n, 1, lit, len(lit), ptr(one_off),
+                                                                                           ptr(one_out), one_out.numel(), C.byref(tot), s))
+    for k, tpl in templates.items():
+        calls["one_call_" + k] = (lambda tpl=tpl: rr._check(L.rrx_replace_groups_longest_extents(handles, 1, tpl._h, 0, ptr(dev), ptr(off), n, 1, ptr(one_off),
+                                                                                                 ptr(one_out), one_out.numel(), C.byref(tot), s)))
+    # the stages, on the lists found once
+    words = L.rrx_search_all_longest_marks_words(nbytes, n)
+    marks = torch.empty(words, dtype=torch.int32, device="cuda")
+    ref_start, ref_end = torch.empty(max(nmatches, 1), dtype=torch.int32, device="cuda"), torch.empty(max(nmatches, 1), dtype=torch.int32, device="cuda")
+    length, pos = torch.empty(n, dtype=torch.int32, device="cuda"), torch.empty(max(nmatches, 1), dtype=torch.int32, device="cuda")
+    d_lit = torch.frombuffer(bytearray(lit), dtype=torch.uint8).cuda()
+    calls["list_spans"] = lambda: rr._check(L.rrx_group_spans_list_extents(g._h, 0, ptr(dev), ptr(off), n, 1, ptr(first), ptr(start), ptr(end), ptr(marks), words,
+                                                                           ptr(ref_start), ptr(ref_end), s))
+    calls["list_spans"]()
+    stage_off, stage_out = {}, {}
+
+    def prefix(key):
+        stage_off[key] = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+        torch.cumsum(length.to(torch.int64), dim=0, out=stage_off[key][1:])
+        stage_out[key] = torch.empty(int(stage_off[key][-1]), dtype=torch.uint8, device="cuda")
+    calls["sizes_parent_literal"] = lambda: rr._check(L.rrx_replace_matches_sizes(0, ptr(off), n, 1, ptr(first), ptr(start), ptr(end), len(lit), ptr(length), ptr(pos), s))
+    calls["sizes_parent_literal"]()
+    prefix("parent_literal")
+    pos_lit = pos.clone()
+    calls["fill_parent_literal"] = lambda: rr._check(L.rrx_replace_matches_fill(0, ptr(dev), ptr(off), n, 1, ptr(first), ptr(end), ptr(pos_lit), ptr(d_lit), len(lit),
+                                                                                ptr(stage_off["parent_literal"]), ptr(stage_out["parent_literal"]), s))
+    for k in ("literal", "group"):
+        tpl = templates[k]
+        sizes = (lambda tpl=tpl: rr._check(L.rrx_replace_template_sizes(0, ptr(off), n, 1, ptr(first), ptr(start), ptr(end), tpl._h, ptr(ref_start), ptr(ref_end),
+                                                                        max(nmatches, 1), ptr(length), ptr(pos), s)))
+        sizes()
+        prefix(k)
+        pos_k = pos.clone()
+        calls["sizes_" + k] = sizes
+        calls["fill_" + k] = (lambda tpl=tpl, k=k, pos_k=pos_k: rr._check(L.rrx_replace_template_fill(
+            0, ptr(dev), ptr(off), n, 1, ptr(first), ptr(start), ptr(end), ptr(pos_k), tpl._h, ptr(ref_start), ptr(ref_end), max(nmatches, 1), ptr(stage_off[k]),
+            ptr(stage_out[k]), s)))
+    for _ in range(3):
+        for call in calls.values():
+            call()
+    torch.cuda.synchronize()
+    assert torch.equal(stage_out["literal"], stage_out["parent_literal"]) and torch.equal(stage_off["literal"], stage_off["parent_literal"]), \
+        "the template literal and the literal entries differ"
+    assert int(stage_off["group"][-1]) == totals["group"]
+    ms = {k: [] for k in calls}
+    for _ in range(launches):
+        for k, call in calls.items():                   # alternating: every call has the parent's literal path right beside it
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); call(); b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    line = {"config": kind, "entry": "replace_groups", "bytes": nbytes, "items": n, "matches": nmatches, "out_bytes": totals}
+    for k in calls:
+        line[k + "_ms"] = round(med[k], 4)
+        line[k + "_spread"] = round((max(ms[k]) - min(ms[k])) / med[k], 4)
+    line["one_call_group_over_parent_literal"] = round(med["one_call_group"] / med["one_call_parent_literal"], 4)
+    line["one_call_template_literal_over_parent_literal"] = round(med["one_call_literal"] / med["one_call_parent_literal"], 4)
+    line["fill_group_GB/s"] = round(totals["group"] / med["fill_group"] / 1e6, 1)
+    line["fill_parent_literal_GB/s"] = round(totals["parent_literal"] / med["fill_parent_literal"] / 1e6, 1)
+    print(json.dumps(line), flush=True)
 
 
 def pieces_child(rr, r, kind, dev, off, launches, skew):
@@ -417,6 +516,26 @@ def replace_main(a):
             f.write(json.dumps(x) + "\n")
 
 
+def replace_groups_main(a):
+    """One child on the e-mail text (the one text whose pattern has a group put in), this tree alone; the line to a.out."""
+    kind, pkey, nbytes = next(c for c in CONFIGS if c[1] in GROUPED)
+    n = int(nbytes * a.scale) // 4096 * 4096
+    env = dict(os.environ)
+    env.pop("RRX_LIB", None)
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", "replace_groups", "--launches", str(a.launches), "--child", ROOT, kind, pkey, str(n)],
+                       env=env, timeout=600, stdout=subprocess.PIPE, text=True)
+    sys.stdout.write(p.stdout)
+    sys.stdout.flush()
+    if p.returncode:                           # a fault or a time limit: nothing more is started on the device
+        raise SystemExit("child failed with %d: replace_groups %s" % (p.returncode, kind))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("tools/probe/item_lanes_rate.py --entry replace_groups --launches %d --scale %g: medians of device-event times per call [ms], all\n"
+                "calls alternating in one process; pattern %s, literal %r; *_parent_literal = the literal entries, whose code the\n"
+                "parent commit has unchanged.\n" % (a.launches, a.scale, GROUPED[pkey], REPLACE_GROUPS_LITERAL.decode()))
+        f.write(p.stdout)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entry", choices=ENTRIES, required=True)
@@ -430,13 +549,15 @@ def main():
         tree, kind, pkey, nbytes = a.child
         return child(tree, a.entry, kind, pkey, int(nbytes), max(a.launches, 12))
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", a.entry + "_items_rate.txt")
+        a.out = os.path.join(ROOT, "profiles", ("replace_template" if a.entry == "replace_groups" else a.entry) + "_items_rate.txt")
     if a.entry == "replace":
         return replace_main(a)
     if a.entry == "pieces":
         return pieces_main(a)
     if a.entry == "one_call":
         return one_call_main(a)
+    if a.entry == "replace_groups":
+        return replace_groups_main(a)
     assert os.path.exists(os.path.join(a.old, "roaringregex_amd", "librrx.so")), "build the parent commit under %s first" % a.old
     # a parent that has the entry runs the entry itself: the yardsticks are for the commit that added it
     yardstick = a.entry in YARDSTICK and NEWER[a.entry] not in open(os.path.join(a.old, "roaringregex_amd", "__init__.py")).read()
