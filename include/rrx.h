@@ -657,6 +657,56 @@ int rrx_replace_groups_longest_extents(const rrx_group *const *groups, size_t ng
 int rrx_replace_groups_longest_items(const rrx_group *const *groups, size_t ngroups, const rrx_template *tpl, const rrx_items *items,
                                      uint64_t *d_out_off, void *d_out, size_t cap, size_t *total, void *stream);
 
+/* A SET OF PATTERNS ON A STRING COLUMN: which of up to 32 patterns does each item contain (log classification, rule lists,
+ * CASE WHEN col RLIKE p1 ... WHEN col RLIKE pK) - one walk over the column instead of one per pattern.
+ * THE RULE: for the set p_0 .. p_{K-1}, 1 <= K <= 32, bit k of d_mask[i] is set exactly when rrx_contains_extents on p_k sets bit i
+ * of its bitmap for the same batch and trim.  All else follows: '\n', NUL and bytes >= 0x80 are ordinary text inside an item; the
+ * bit of a pattern that accepts the empty string is always set, that of the empty language never; the bytes behind an item's trim
+ * are never read; a pattern may occur twice (its two bits agree).  Bits K .. 31 of every mask are 0.
+ * COMPILING: every member goes through the front end to its forward search table ("any bytes, then the pattern": accepting
+ * exactly where a match ends).  RRX_ERR_PATTERN: a member does not parse; RRX_ERR_UNSUPPORTED: a member's forward table does not
+ * determinise within the state budget (16384 states) - rrx_last_error() names the member's index in both cases, and there is no
+ * fallback for such a member.  RRX_ERR_ARG: npatterns == 0 or > 32, a null pointer (the array, a member, out), an engine other
+ * than RRX_ENGINE_AUTO / _DFA / _DFA_GLOBAL.  The members are cut into GROUPS, greedy in set order; a group shares one PRODUCT
+ * table (a row = a tuple of member states, its mask = the bits of the members whose state is accepting; minimised; rows with an
+ * empty mask numbered first), stepped once per byte whatever the number of members.  Member k joins the open group if the
+ * minimised product with it has at most max_rows rows (0: 65535, what 16-bit rows allow; a product is abandoned beyond 65535
+ * tuples, so compile time is bounded) and fits 64 KiB of LDS; otherwise the group closes and k opens the next one.  A member
+ * beyond the LDS budget on its own is a group of its own in HBM/L2; RRX_ENGINE_DFA_GLOBAL leaves every group there and drops the
+ * LDS criterion.  Every set of individually admissible patterns compiles.
+ * rrx_multi_patterns / _groups: K and the number of groups.  rrx_multi_group_mask: the members of group g as a bit mask (the
+ * groups' masks partition the set), _group_states: the rows of its table; 0 for a group that is not there.
+ * rrx_multi_program_words(m, group, out, cap): the table of a group as words, the number of words returned (cap = 0 sizes it):
+ *   [nstates, ncls, start row, first_hit, full], cls[256] (byte -> class), next[nstates][ncls], mask[nstates]
+ * Rows below first_hit have an empty mask, rows from first_hit on a non-empty one; full = the OR of all masks.  The answer for an
+ * item: m = mask[start]; for every byte c: s = next[s][cls[c]], m |= mask[s]; the item's mask is the OR of m over the groups.
+ * THE ENTRIES: item i = d_bytes[d_off[i] .. d_off[i+1] - trim), as in rrx_contains_extents; d_mask: nitems 32-bit words, every
+ * one of them written (the first group's launch stores, the others OR - the lane owns its word: no atomics, nothing to clear
+ * beforehand), none beyond.  A lane stops reading its item once it holds every bit its group can give.  One launch per group; a
+ * set of empty languages only costs one memset.  Tables are uploaded once per device at the first call there; from then on the
+ * entries are asynchronous on `stream` and can be captured into a graph.  nitems == 0 writes nothing and returns RRX_OK;
+ * RRX_ERR_ARG for null arguments, checked before any device call.  The _items form uses the handle's bytes, offsets, item count,
+ * trim and device only.
+ * rrx_multi_counts: d_counts[k] (32 uint64 counters in device memory, zeroed here on `stream`) = the items among the first
+ * nitems whose mask has bit k.  rrx_multi_plane: bit `pattern` (< 32, RRX_ERR_ARG otherwise) of every mask as a bitmap in the
+ * layout of rrx_contains_extents - ceil(nitems / 32) whole words, the bits beyond nitems 0 - so that rrx_bitmap_count and
+ * rrx_bitmap_to_bytes apply.  Both take any column of masks and no handle.
+ * Not here: a '\n'-corpus form, stripe-wise or stride-2 forms, more than 32 patterns per handle.                                 */
+typedef struct rrx_multi rrx_multi;
+int rrx_multi_compile(const char *const *patterns, size_t npatterns, rrx_multi **out);
+int rrx_multi_compile_ex(const char *const *patterns, size_t npatterns, int engine, uint32_t max_rows, rrx_multi **out);
+void rrx_multi_free(rrx_multi *m);
+size_t rrx_multi_patterns(const rrx_multi *m);
+size_t rrx_multi_groups(const rrx_multi *m);
+uint32_t rrx_multi_group_mask(const rrx_multi *m, size_t group);
+uint32_t rrx_multi_group_states(const rrx_multi *m, size_t group);
+size_t rrx_multi_program_words(const rrx_multi *m, size_t group, uint32_t *out, size_t cap);
+int rrx_multi_contains_extents(const rrx_multi *m, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
+                               uint32_t *d_mask, void *stream);
+int rrx_multi_contains_items(const rrx_multi *m, const rrx_items *items, uint32_t *d_mask, void *stream);
+int rrx_multi_counts(int device, const uint32_t *d_mask, size_t nitems, uint64_t *d_counts, void *stream);
+int rrx_multi_plane(int device, const uint32_t *d_mask, size_t nitems, uint32_t pattern, uint32_t *d_bits, void *stream);
+
 /* ONE device-resident string of any length (regex.h:156-159: operator++ consumes the whole string; '\n' and every
  * other byte are ordinary, a NUL or a byte >= 0x80 rejects).  d_accept[0] = 1 iff accepted.  Strings of 32 KiB and
  * more are split into chunks that are stepped in parallel from every table state (automata with <= 254 table

@@ -62,6 +62,8 @@ ABI_SYMBOLS = (
     "rrx_group_spans_list_extents", "rrx_group_spans_list_items",
     "rrx_template_compile", "rrx_template_free", "rrx_template_refs", "rrx_template_segments",
     "rrx_replace_template_sizes", "rrx_replace_template_fill", "rrx_replace_groups_longest_extents", "rrx_replace_groups_longest_items",
+    "rrx_multi_compile", "rrx_multi_compile_ex", "rrx_multi_free", "rrx_multi_patterns", "rrx_multi_groups", "rrx_multi_group_mask",
+    "rrx_multi_group_states", "rrx_multi_program_words", "rrx_multi_contains_extents", "rrx_multi_contains_items", "rrx_multi_counts", "rrx_multi_plane",
 )
 
 
@@ -184,6 +186,18 @@ def _load():
         "rrx_replace_template_fill": (i32, [i32, vp, vp, sz, u32, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
         "rrx_replace_groups_longest_extents": (i32, [vp, sz, vp, i32, vp, vp, sz, u32, vp, vp, sz, C.POINTER(sz), vp]),
         "rrx_replace_groups_longest_items": (i32, [vp, sz, vp, vp, vp, vp, sz, C.POINTER(sz), vp]),
+        "rrx_multi_compile": (i32, [vp, sz, C.POINTER(vp)]),
+        "rrx_multi_compile_ex": (i32, [vp, sz, i32, u32, C.POINTER(vp)]),
+        "rrx_multi_free": (None, [vp]),
+        "rrx_multi_patterns": (sz, [vp]),
+        "rrx_multi_groups": (sz, [vp]),
+        "rrx_multi_group_mask": (u32, [vp, sz]),
+        "rrx_multi_group_states": (u32, [vp, sz]),
+        "rrx_multi_program_words": (sz, [vp, sz, vp, sz]),
+        "rrx_multi_contains_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp]),
+        "rrx_multi_contains_items": (i32, [vp, vp, vp, vp]),
+        "rrx_multi_counts": (i32, [i32, vp, sz, vp, vp]),
+        "rrx_multi_plane": (i32, [i32, vp, sz, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1334,3 +1348,99 @@ def replace_groups_longest_items(groups, template, items, cap=None, stream=None)
         s = _stream_ptr(stream)
         return RRegex._replace_one_call(None, items.data.device, items.num_items, int(cap) if cap is not None else items.data.numel(),
                                         lambda f, out, cp, tot: _L.rrx_replace_groups_longest_items(h, len(groups), tpl._h, items._h, f, out, cp, tot, s))
+
+
+class RMulti:
+    """A set of 1 to 32 patterns on a string column (rrx_multi): which of them does each item contain, in one walk over the column.
+    Bit k of an item's mask is set exactly when RRegex(patterns[k]).contains_extents says 1 for that item.  The members are cut
+    into groups that share one product table each (greedy in set order: `max_rows` rows per table at most, 0 = 65535, and 64 KiB
+    of LDS); engine=ENGINE_DFA_GLOBAL leaves every table in HBM/L2.  RRegexError names the index of a member that does not
+    parse or whose forward search automaton does not determinise."""
+
+    def __init__(self, patterns, engine=None, max_rows=0, device=0):
+        pats = [p.encode("latin-1") if isinstance(p, str) else bytes(p) for p in patterns]
+        self.patterns, self.device = pats, device
+        self._h = C.c_void_p()
+        arr = (C.c_char_p * max(len(pats), 1))(*pats)
+        _check(_L.rrx_multi_compile_ex(C.cast(arr, C.c_void_p), len(pats), ENGINE_AUTO if engine is None else engine, max_rows, C.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _L is not None:
+            _L.rrx_multi_free(self._h)
+            self._h = None
+
+    def __len__(self):
+        return _L.rrx_multi_patterns(self._h)
+
+    @property
+    def groups(self):
+        """The number of groups, i.e. of launches per call."""
+        return _L.rrx_multi_groups(self._h)
+
+    def group_mask(self, g):
+        """The members of group g as a bit mask; the groups' masks partition the set."""
+        return _L.rrx_multi_group_mask(self._h, g)
+
+    def group_states(self, g):
+        """The rows of group g's product table."""
+        return _L.rrx_multi_group_states(self._h, g)
+
+    def program(self, g):
+        """Group g's table as words (numpy uint32): [nstates, ncls, start, first_hit, full], cls[256], next[nstates][ncls],
+        mask[nstates]; None for a group that is not there."""
+        import numpy as np
+        n = _L.rrx_multi_program_words(self._h, g, None, 0)
+        if not n:
+            return None
+        out = np.zeros(n, dtype=np.uint32)
+        _L.rrx_multi_program_words(self._h, g, C.c_void_p(out.ctypes.data), n)
+        return out
+
+    @staticmethod
+    def _masks(n, device, out):
+        import torch
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=device)
+        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n
+        return out[:n]
+
+    def contains_extents(self, data, offsets, trim=0, out=None, stream=None):
+        """Item i = data[offsets[i] : offsets[i+1] - trim] -> an int32 tensor of n masks, bit k = the item contains a match of
+        patterns[k] (rrx_multi_contains_extents).  Every word is written.  Asynchronous on `stream`."""
+        n, d, b, o = _batch(data, offsets)
+        with _on(d, stream):
+            out = self._masks(n, data.device, out)
+            _check(_L.rrx_multi_contains_extents(self._h, d, b, o, n, trim, _ptr(out), _stream_ptr(stream)))
+        return out
+
+    def contains_items(self, items, out=None, stream=None):
+        """The same for an indexed batch (rrx_multi_contains_items)."""
+        with _on(items.device, stream):
+            out = self._masks(items.num_items, items.data.device, out)
+            _check(_L.rrx_multi_contains_items(self._h, items._h, _ptr(out), _stream_ptr(stream)))
+        return out
+
+    def counts(self, masks, stream=None):
+        """Per pattern, the number of masks that have its bit (rrx_multi_counts) -> an int64 device tensor of len(self) totals.
+        Asynchronous on `stream`."""
+        import torch
+        assert masks.is_cuda and masks.dtype == torch.int32 and masks.is_contiguous()
+        with _on(masks.device.index, stream):
+            counts = torch.empty(32, dtype=torch.int64, device=masks.device)
+            _check(_L.rrx_multi_counts(masks.device.index, _ptr(masks), masks.numel(), _ptr(counts), _stream_ptr(stream)))
+        return counts[:len(self)]
+
+    def plane(self, masks, k, out=None, stream=None):
+        """Bit k of every mask as a bitmap in the layout of RRegex.contains_extents_bits (rrx_multi_plane): ceil(n / 32) int32
+        words, so that bitmap_count applies.  Asynchronous on `stream`."""
+        import torch
+        assert masks.is_cuda and masks.dtype == torch.int32 and masks.is_contiguous()
+        n = masks.numel()
+        nw = (n + 31) // 32
+        with _on(masks.device.index, stream):
+            if out is None:
+                out = torch.empty(nw, dtype=torch.int32, device=masks.device)
+            assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= nw
+            out = out[:nw]
+            _check(_L.rrx_multi_plane(masks.device.index, _ptr(masks), n, k, _ptr(out), _stream_ptr(stream)))
+        return out

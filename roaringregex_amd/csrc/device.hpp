@@ -268,6 +268,29 @@ int contains_extents_dfa(const DfaDevice &p, bool in_global, uint32_t found, con
 // the first ceil(nitems / 32) words of a stripe-wise result bitmap into `bits`, the last one masked to nitems
 int copy_result_bits(const uint32_t *result, size_t nitems, uint32_t *bits, void *stream);
 
+// ---- which patterns of a set each explicit item contains, a lane per item: kernels_multi_items.hip
+// The product table of a group of members (lower.hpp: MultiProgram): rows below first_hit carry no mask, `full` is the OR of all masks.
+struct MultiDevice {
+    uint32_t nstates = 0, ncls = 0, start = 0, first_hit = 0, full = 0;
+    const uint8_t *cls = nullptr;                // [256]
+    const uint16_t *next = nullptr;              // [nstates][ncls]
+    const uint32_t *mask = nullptr;              // [nstates]
+};
+// The table's LDS form: next, the class map, the masks, each from a 16-byte boundary (plan.cpp groups the members by it)
+inline size_t multi_lds_bytes(uint32_t nstates, uint32_t ncls) {
+    return (((size_t)nstates * ncls * 2 + 15) & ~(size_t)15) + 256 + (((size_t)nstates * 4 + 15) & ~(size_t)15);
+}
+// Item i = bytes[off[i] .. off[i+1] - trim): m = the OR of the masks of the start row and of every row the item's bytes lead
+// through; a lane stops reading once m == p.full.  first: out[i] = m, else out[i] |= m - plain loads and stores of the lane's own
+// word, every one of the nitems words written, nothing to clear beforehand.  in_global: leave the table in HBM/L2 (the class map in
+// LDS) whatever its size; it stays there anyway beyond kPlainDfaLdsBudget.
+int multi_contains_extents(const MultiDevice &p, bool in_global, bool first, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
+                           uint32_t *out, void *stream);
+// counts[k] += the items among the first nitems whose mask has bit k, k = 0 .. 31 (the caller zeroes the 32 counters)
+int multi_counts(const uint32_t *mask, size_t nitems, unsigned long long *counts, void *stream);
+// bit `pattern` of every mask as a bitmap in contains_extents_dfa's layout: ceil(nitems / 32) whole words, plain stores
+int multi_plane(const uint32_t *mask, size_t nitems, uint32_t pattern, uint32_t *bits, void *stream);
+
 // ---- first match per explicit item, a lane per item: kernels_search_items.hip
 // The two search tables in their plain form, one image: fwd = "any bytes, then the pattern" (accepting exactly where a match ends),
 // rev = the pattern right to left (accepting, walking back from a match end, exactly where a match starts; row 0 dead and absorbing:

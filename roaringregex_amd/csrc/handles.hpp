@@ -3,7 +3,8 @@
 // program dumps, table order and sampled table, its tables on the device), corpus.cpp (rrx_corpus, the batch entries, the one-shot
 // entry, the host pipeline), search.cpp, the units of explicit items - items.cpp (batches, match and contains), item_search.cpp
 // (where the matches are), item_columns.cpp (replace and pieces); what they share is items.hpp -, strings.cpp (single strings),
-// group.cpp (rrx_group: a pattern split at a capture group, with a handle of its own).  What a pattern compiles to and which table
+// group.cpp (rrx_group: a pattern split at a capture group, with a handle of its own), multi.cpp (rrx_multi: a set of patterns on
+// product tables, with a handle of its own).  What a pattern compiles to and which table
 // forms it gets is decided in plan.cpp, the life of a sampled table in sampled.cpp.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -3,7 +3,7 @@
 // kernels_table.hip and kernels_nfa.inc (match_extents_kernel), kernels_contains_items.hip, kernels_search_items.hip,
 // kernels_search_all_items.hip, kernels_search_longest_items.hip, kernels_search_all_longest_items.hip, kernels_replace_items.hip,
 // kernels_replace_template_items.hip, kernels_pieces_items.hip (no walk in these three: their kernels take the span, the loop and the
-// launcher) and kernels_group_items.hip.
+// launcher), kernels_group_items.hip and kernels_multi_items.hip (contains_extents_kernel's walk on a product table).
 //
 // THE WALK, described here once.  A lane reads its item [b, e) straight from HBM/L2, forwards or backwards, in three stretches:
 // single bytes up to a 16-byte boundary, one uint4 per 16 bytes (forwards the low byte first, backwards the high byte), single

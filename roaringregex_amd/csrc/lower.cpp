@@ -841,13 +841,16 @@ bool lower_nfa(const Reduced &red, uint32_t max_bits, NfaProgram &p, bool allow_
 }
 
 // ------------------------------------------------------------------------------------------ DFA lowering
-// Minimisation (Hopcroft's partition refinement) of a complete table over K classes and its renumbering.  kind[i]: 0 = rejecting,
-// 1 = accepting, 2 = the ESCAPE state of a sampled table (kept apart from the dead state it would otherwise merge with).
-// State 0 is the dead state, state 1 the start.  (The "recompute every signature until nothing splits" form took one round per
-// state on a chain - a{1,n} is n rounds over n states: 0.45 s at n = 2400, minutes at 16000.)
-static bool minimise_into(const std::vector<uint32_t> &nxt, const std::vector<uint8_t> &kind, const uint32_t K, DfaProgram &d) {
+// Hopcroft's partition refinement, shared by minimise_into and multi_product: the coarsest partition of the D states of the complete
+// table nxt[D][K] that refines their labels (values below `nlabels`) and is stable under every class.  block[i] = the block of
+// state i; returns the number of blocks.  The partition starts as the labels present, in label order.  (The "recompute every
+// signature until nothing splits" form took one round per state on a chain - a{1,n} is n rounds over n states: 0.45 s at
+// n = 2400, minutes at 16000.)
+template <class Label>
+static uint32_t refine_partition(const std::vector<uint32_t> &nxt, const std::vector<Label> &kind, const uint32_t nlabels, const uint32_t K,
+                                 std::vector<uint32_t> &block) {
     const uint32_t D = (uint32_t)kind.size();
-    std::vector<uint32_t> block(D);
+    block.assign(D, 0);
     uint32_t count = 0;
     {
         // inverse transitions per class, CSR: inv[k][first[k][t] .. first[k][t + 1]) = the states that go to t on class k
@@ -862,10 +865,10 @@ static bool minimise_into(const std::vector<uint32_t> &nxt, const std::vector<ui
         // the partition: elems holds the states block by block; a block is elems[lo[b] .. hi[b]).  It starts as the kinds present.
         std::vector<uint32_t> elems(D), loc(D), lo, hi, marked;
         {
-            uint32_t n_of[3] = {0, 0, 0}, at[3];
+            std::vector<uint32_t> n_of(nlabels, 0), at(nlabels, 0);
             for (uint32_t i = 0; i < D; i++) n_of[kind[i]]++;
-            at[0] = 0; at[1] = n_of[0]; at[2] = n_of[0] + n_of[1];
-            for (int q = 0; q < 3; q++) if (n_of[q]) { lo.push_back(at[q]); hi.push_back(at[q] + n_of[q]); }
+            for (uint32_t q = 1; q < nlabels; q++) at[q] = at[q - 1] + n_of[q - 1];
+            for (uint32_t q = 0; q < nlabels; q++) if (n_of[q]) { lo.push_back(at[q]); hi.push_back(at[q] + n_of[q]); }
             for (uint32_t i = 0; i < D; i++) { const uint32_t p = at[kind[i]]++; elems[p] = i; loc[i] = p; }
             for (uint32_t b = 0; b < lo.size(); b++) for (uint32_t q = lo[b]; q < hi[b]; q++) block[elems[q]] = b;
         }
@@ -914,6 +917,14 @@ static bool minimise_into(const std::vector<uint32_t> &nxt, const std::vector<ui
         }
         count = (uint32_t)lo.size();
     }
+    return count;
+}
+// Minimisation of a complete table over K classes and its renumbering.  kind[i]: 0 = rejecting, 1 = accepting, 2 = the ESCAPE state
+// of a sampled table (kept apart from the dead state it would otherwise merge with).  State 0 is the dead state, state 1 the start.
+static bool minimise_into(const std::vector<uint32_t> &nxt, const std::vector<uint8_t> &kind, const uint32_t K, DfaProgram &d) {
+    const uint32_t D = (uint32_t)kind.size();
+    std::vector<uint32_t> block;
+    const uint32_t count = refine_partition(nxt, kind, 3, K, block);
     // renumber: the dead block -> 0, the others in breadth-first order from the start state, classes ascending - a numbering
     // that depends on the language and its byte classes only, not on which equivalent automaton the subset construction saw
     std::vector<int64_t> id(count, -1);
@@ -1153,6 +1164,86 @@ bool contains_dfa(const DfaProgram &fwd, DfaProgram &out) {
         for (uint32_t k = 0; k < K; k++) nxt[(size_t)s * K + k] = fwd.accepting[s] ? s : fwd.next[(size_t)s * K + k];
     }
     return minimise_into(nxt, kind, K, out);
+}
+
+bool search_fwd_dfa(const Reduced &r, uint32_t max_states, DfaProgram &fwd) { return subset_construct(r, max_states, true, fwd); }
+
+// ------------------------------------------------------------------------------------------ pattern sets
+MultiProgram multi_unit() {
+    MultiProgram u;
+    u.nstates = 1; u.ncls = 1;
+    std::memset(u.cls, 0, sizeof u.cls);
+    u.next = {0};
+    u.mask = {0};
+    return u;
+}
+
+bool multi_product(const MultiProgram &a, const DfaProgram &b, uint32_t bit, MultiProgram &o) {
+    o = MultiProgram();
+    // the common byte classes: one per pair (class of a, class of b) that some byte has
+    std::vector<uint32_t> ca, cb;                       // the pair of a common class
+    {
+        std::vector<int32_t> id((size_t)a.ncls * b.ncls, -1);
+        for (int c = 0; c < 256; c++) {
+            const size_t key = (size_t)a.cls[c] * b.ncls + b.cls[c];
+            if (id[key] < 0) { id[key] = (int32_t)ca.size(); ca.push_back(a.cls[c]); cb.push_back(b.cls[c]); }
+            o.cls[c] = (uint8_t)id[key];
+        }
+    }
+    const uint32_t K = (uint32_t)ca.size();
+    // breadth first over the reachable tuples
+    std::unordered_map<uint64_t, uint32_t> ids;
+    std::vector<std::pair<uint32_t, uint32_t>> tuples;
+    auto intern = [&](uint32_t sa, uint32_t sb) {
+        auto it = ids.emplace(((uint64_t)sa << 32) | sb, (uint32_t)tuples.size());
+        if (it.second) tuples.emplace_back(sa, sb);
+        return it.first->second;
+    };
+    intern(a.start, b.start);
+    std::vector<uint32_t> nxt;
+    for (uint32_t cur = 0; cur < tuples.size(); cur++) {
+        const auto [sa, sb] = tuples[cur];
+        for (uint32_t k = 0; k < K; k++)
+            nxt.push_back(intern(a.next[(size_t)sa * a.ncls + ca[k]], b.next[(size_t)sb * b.ncls + cb[k]]));
+        if (tuples.size() > kMultiMaxRows) return false;
+    }
+    const uint32_t D = (uint32_t)tuples.size();
+    // the masks, and the partition they seed: label = the rank of the mask among the masks present
+    std::vector<uint32_t> mask(D), label(D);
+    {
+        std::map<uint32_t, uint32_t> rank;
+        for (uint32_t i = 0; i < D; i++) rank.emplace(mask[i] = a.mask[tuples[i].first] | (b.accepting[tuples[i].second] ? bit : 0u), 0u);
+        uint32_t n = 0;
+        for (auto &kv : rank) kv.second = n++;
+        for (uint32_t i = 0; i < D; i++) label[i] = rank[mask[i]];
+        std::vector<uint32_t> block;
+        const uint32_t count = refine_partition(nxt, label, n, K, block);
+        // number the blocks breadth first from the start's, classes ascending, then the rows without a mask first
+        std::vector<uint32_t> rep(count, UINT32_MAX), order, seen(count, 0);
+        for (uint32_t i = 0; i < D; i++) if (rep[block[i]] == UINT32_MAX) rep[block[i]] = i;
+        order.push_back(block[0]);
+        seen[block[0]] = 1;
+        for (size_t h = 0; h < order.size(); h++)
+            for (uint32_t k = 0; k < K; k++) {
+                const uint32_t nb = block[nxt[(size_t)rep[order[h]] * K + k]];
+                if (!seen[nb]) { seen[nb] = 1; order.push_back(nb); }
+            }
+        std::stable_partition(order.begin(), order.end(), [&](uint32_t b2) { return mask[rep[b2]] == 0; });
+        std::vector<uint32_t> id(count);
+        for (uint32_t r = 0; r < count; r++) id[order[r]] = r;
+        o.nstates = count; o.ncls = K; o.start = id[block[0]];
+        o.next.assign((size_t)count * K, 0);
+        o.mask.assign(count, 0);
+        o.first_hit = count;
+        for (uint32_t r = 0; r < count; r++) {
+            const uint32_t i = rep[order[r]];
+            o.mask[r] = mask[i];
+            o.full |= mask[i];
+            if (mask[i] && o.first_hit == count) o.first_hit = r;
+            for (uint32_t k = 0; k < K; k++) o.next[(size_t)r * K + k] = (uint16_t)id[block[nxt[(size_t)i * K + k]]];
+        }
+    }
+    return true;
 }
 
 // Line-mode search table: the product of the sticky forward table (where does the first match END) and the anchored table

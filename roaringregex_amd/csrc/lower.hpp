@@ -180,6 +180,33 @@ bool search_longest_dfas(const Reduced &r, uint32_t max_states, DfaProgram &star
 // >= 0x80, bytes the pattern does not mention) is a live column: it leads where `fwd` says.  Steps like any DfaProgram in line
 // mode: start state at a line start, verdict of the state at the line end.
 bool contains_dfa(const DfaProgram &fwd, DfaProgram &out);
+// search_dfas' fwd alone (a pattern set needs no reverse table: rrx_multi)
+bool search_fwd_dfa(const Reduced &r, uint32_t max_states, DfaProgram &fwd);
+
+// "Which of the patterns of a set does the item contain" (rrx_multi): the PRODUCT of the members' forward search tables ("any
+// bytes, then the pattern": accepting exactly where a match ends), minimised.  A row is a tuple of member states; mask[row] = the OR
+// of the set-wide bit of every member whose component is accepting.  A walk ORs the masks of the rows it passes: what an item
+// contains is kept by the walk, not by the table - were the accepting states folded into absorbing ones, as the contains table of
+// one pattern has them, the rows would have to remember every subset of members found so far (K keywords: 2^K rows instead of
+// the sum of their lengths).  The per-byte cost does not depend on how many members the table holds.  Byte classes: the common
+// refinement of the members' maps; '\n', NUL and bytes >= 0x80 are ordinary bytes of their class.  Rows are 16-bit: at most
+// kMultiMaxRows of them.
+constexpr uint32_t kMultiMaxRows = 65535;
+struct MultiProgram {
+    uint32_t nstates = 0, ncls = 0, start = 0;
+    uint32_t first_hit = 0;                 // rows below it have an empty mask, rows from it on a non-empty one
+    uint32_t full = 0;                      // the OR of every row's mask: all that a walk on this table can ever find
+    uint8_t cls[256];
+    std::vector<uint16_t> next;             // [nstates][ncls]
+    std::vector<uint32_t> mask;             // [nstates]
+};
+MultiProgram multi_unit();                  // the table of no member at all: one row, one class, no mask
+// `a` with one member more: `b` (a forward search table, search_fwd_dfa; its dead row 0, which nothing reaches, is left behind)
+// under the set-wide bit `bit`.  Breadth first over the reachable pairs (row of a, state of b), abandoned beyond
+// kMultiMaxRows pairs (false: compile time stays bounded); then partition refinement seeded by the masks, and the rows numbered
+// breadth first from the start row, those with an empty mask first.  Minimising after every member yields the same table as
+// minimising the product of all the members' tables at once, and never walks more pairs.
+bool multi_product(const MultiProgram &a, const DfaProgram &b, uint32_t bit, MultiProgram &out);
 
 // Line-mode search table (stripe-wise search kernel): rows = reachable pairs (anchored state, sticky forward state) + the
 // SKIP row, columns = byte classes + '\n'.  Entry = next row | flags: kSearchNewline (the byte was '\n': next row = start),

@@ -173,6 +173,13 @@ bool pack_group(const DfaProgram &a, const DfaProgram &rev_bc, const DfaProgram 
     return true;
 }
 
+void pack_multi(const MultiProgram &p, Image &img, dev::MultiDevice &d) {
+    img.put(d.cls, p.cls, 256);
+    img.put(d.next, p.next.data(), p.next.size() * 2);
+    img.put(d.mask, p.mask.data(), p.mask.size() * 4);
+    d.nstates = p.nstates; d.ncls = p.ncls; d.start = p.start; d.first_hit = p.first_hit; d.full = p.full;
+}
+
 void pack_lane_nfa(const NfaProgram &nfa, Image &img, dev::NfaDevice &d) {
     const uint32_t W = nfa.W, WP = (uint32_t)instantiated_width(W);
     std::vector<uint32_t> B((size_t)256 * WP, 0), X((size_t)nfa.nbits * WP, 0);

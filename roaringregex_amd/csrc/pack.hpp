@@ -68,5 +68,7 @@ bool pack_search_longest(const DfaProgram &starts, const DfaProgram &anchored, I
 // The four tables of a pattern split at a capture group (device.hpp: GroupDevice) in the plain form, one image; a table without
 // states is an absent part and stays empty.  false where some table's row 0 is not its dead row, or B has no table.
 bool pack_group(const DfaProgram &a, const DfaProgram &rev_bc, const DfaProgram &b, const DfaProgram &rev_c, Image &img, dev::GroupDevice &d);
+// The product table of one group of a pattern set (device.hpp: MultiDevice): cls, next and the masks, with first_hit and full.
+void pack_multi(const MultiProgram &p, Image &img, dev::MultiDevice &d);
 
 }  // namespace rrx

@@ -119,6 +119,42 @@ bool plan_search_longest(const Reduced &red, bool accepts_empty, SearchLongestPl
     return true;
 }
 
+bool lower_multi_member(const std::string &pattern, DfaProgram &out) {
+    return search_fwd_dfa(reduce(trim(build_reference_automaton(pattern))), kMaxSubsetStates, out);
+}
+
+void plan_multi(const std::vector<DfaProgram> &members, bool force_global, uint32_t max_rows, MultiPlan &out) {
+    out = MultiPlan();
+    if (!max_rows || max_rows > kMultiMaxRows) max_rows = kMultiMaxRows;
+    auto in_lds = [](const MultiProgram &t) { return dev::multi_lds_bytes(t.nstates, t.ncls) <= dev::kPlainDfaLdsBudget; };
+    auto close = [&](MultiGroup &g) {
+        g.in_global = force_global || !in_lds(g.table);
+        out.groups.push_back(std::move(g));
+        g = MultiGroup();
+    };
+    MultiGroup open;
+    for (uint32_t k = 0; k < members.size(); k++) {
+        const uint32_t bit = 1u << k;
+        MultiProgram with;
+        if (open.members && multi_product(open.table, members[k], bit, with) && with.nstates <= max_rows && (force_global || in_lds(with))) {
+            open.table = std::move(with);
+            open.members |= bit;
+            continue;
+        }
+        if (open.members) close(open);
+        (void)multi_product(multi_unit(), members[k], bit, open.table);      // (a member alone: at most kMaxSubsetStates pairs)
+        open.members = bit;
+    }
+    if (open.members) close(open);
+}
+
+void append_words(std::vector<uint32_t> &w, const MultiProgram &d) {
+    w.insert(w.end(), {d.nstates, d.ncls, d.start, d.first_hit, d.full});
+    w.insert(w.end(), d.cls, d.cls + 256);
+    w.insert(w.end(), d.next.begin(), d.next.end());
+    w.insert(w.end(), d.mask.begin(), d.mask.end());
+}
+
 void append_words(std::vector<uint32_t> &w, const NfaProgram &p, bool csr) {
     w.insert(w.end(), {p.W, p.nbits, p.n_exc, p.accepts_empty ? 1u : 0u});
     for (auto *v : {&p.init, &p.fin, &p.chain, &p.self, &p.excm, &p.cgrp, &p.ctgt, &p.B}) w.insert(w.end(), v->begin(), v->end());

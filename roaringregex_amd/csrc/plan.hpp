@@ -95,11 +95,31 @@ struct SearchLongestPlan {
 // false: one of the two tables does not determinise within kMaxSubsetStates (both stay empty).
 bool plan_search_longest(const Reduced &red, bool accepts_empty, SearchLongestPlan &out);
 
+// A pattern set (rrx_multi): its members' forward search tables in set order, cut into GROUPS of members that share one product table.
+constexpr uint32_t kMultiMaxPatterns = 32;
+struct MultiGroup {
+    MultiProgram table;
+    uint32_t members = 0;        // bit k: member k of the set is in this group (= what table.full can reach, and the empty languages)
+    bool in_global = false;      // the table stays in HBM/L2: asked for, or one member alone is beyond the LDS budget
+};
+struct MultiPlan {
+    std::vector<MultiGroup> groups;
+};
+// The table of one member from its pattern: the front end, then the forward search table ("any bytes, then the pattern").  Throws
+// what the front end and the lowering throw; false where the forward table does not determinise within kMaxSubsetStates.
+bool lower_multi_member(const std::string &pattern, DfaProgram &out);
+// Greedy in set order: member k joins the open group if the minimised product with it has at most max_rows rows (0: kMultiMaxRows)
+// and - unless force_global - its LDS form fits kPlainDfaLdsBudget; else the group closes and k opens the next one.  A member is
+// always admitted to a group of its own, so every set of members compiles.
+void plan_multi(const std::vector<DfaProgram> &members, bool force_global, uint32_t max_rows, MultiPlan &out);
+
 // rrx_program_words: the word layouts that tests/program_replay.py reads.
 void append_words(std::vector<uint32_t> &w, const NfaProgram &p, bool csr);                   // csr: xoff / xtgt in the place of X
 void append_words(std::vector<uint32_t> &w, const DfaProgram &d, bool escaped = false);       // escaped: then the escaped flag per state
 void append_words(std::vector<uint32_t> &w, const Dfa2Program &d, bool pair_dim = false);     // pair_dim: a fifth header word
 void append_words(std::vector<uint32_t> &w, const SearchLineProgram &d, const DfaProgram &fwd);
 void append_words(std::vector<uint32_t> &w, const SearchLine2Program &d, const dev::SearchChunkDevice &layout);
+// rrx_multi_program_words: [nstates, ncls, start, first_hit, full], cls[256], next[nstates][ncls], mask[nstates]
+void append_words(std::vector<uint32_t> &w, const MultiProgram &d);
 
 }  // namespace rrx

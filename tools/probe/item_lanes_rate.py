@@ -51,6 +51,12 @@ items (offsets = the line starts, trim 1: the '\\n' is the separator):
                   and with \\1, and rrx_group_spans_list_extents; all alternating inside one process.  One child, this tree alone;
                   the lines and a summary (what a group reference costs over the literal path) go to `--out` as well.
 
+  multi_contains  which of K keywords every line of the keyword-log text contains (kernels_multi_items.hip), K = 1, 4, 16 and 32:
+                  rrx_multi_contains_items on a set of K keywords beside what the parent commit offers for the same question - K calls
+                  of rrx_contains_items, one per keyword, on the same indexed batch (its code untouched in this tree) -, the two
+                  alternating inside one process, the masks checked against the K bitmaps bit for bit.  One child, this tree alone;
+                  the lines and a summary (the smallest K at which the set wins, if any) go to `--out` as well.
+
 A yardstick stands in only for a parent that lacks the entry (its wrapper shows it): a later parent runs the entry itself, and both
 sides must find the same.
 
@@ -65,6 +71,7 @@ between its two medians and its own spread - and whether each of the tree's medi
     python tools/probe/item_lanes_rate.py --entry pieces [--launches 15] [--scale 1.0] [--out profiles/pieces_items_rate.txt]
     python tools/probe/item_lanes_rate.py --entry one_call [--old .oldtree] [--launches 15] [--out profiles/one_call_items_rate.txt]
     python tools/probe/item_lanes_rate.py --entry replace_groups [--launches 15] [--scale 1.0] [--out profiles/replace_template_items_rate.txt]
+    python tools/probe/item_lanes_rate.py --entry multi_contains [--launches 15] [--scale 1.0] [--out profiles/multi_contains_items_rate.txt]
 """
 import argparse
 import json
@@ -75,7 +82,10 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CONFIGS = (("url", "U2", 1 << 30), ("email", "EMAIL", 1 << 30), ("kwlog", "K1000C", 1 << 30))
-ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "extract_group", "replace", "pieces", "one_call", "replace_groups")
+ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "extract_group", "replace", "pieces", "one_call", "replace_groups",
+           "multi_contains")
+MULTI_KS = (1, 4, 16, 32)                      # --entry multi_contains: the sizes of the keyword sets
+MULTI_KEYWORDS = ["k%d" % (61 * j + 17) for j in range(32)]     # k17, k78, ... k1908: the text's tokens are k1 .. k2000
 GROUPED = {"EMAIL": r"[A-Za-z0-9._]+@([A-Za-z0-9.]+)"}      # --entry extract_group: the patterns that need a group put in; group 1 everywhere
 SKEW_ITEMS, SKEW_ITEM_BYTES = 64, 16 << 20     # the skewed batch of --entry pieces: its first 64 items are merged lines of 16 MiB or more
 YARDSTICK = {"search_all_longest": "search_all", "extract_group": "search_longest"}   # entries the parent lacks: what its side runs instead
@@ -118,6 +128,8 @@ def child(tree, entry, kind, pkey, nbytes, launches):
         return one_call_child(rr, r, kind, dev, off, launches)
     if entry == "replace_groups":
         return replace_groups_child(rr, r, kind, dev, off, n, launches)
+    if entry == "multi_contains":
+        return multi_contains_child(rr, kind, dev, off, n, launches)
 
     if entry in ("match", "contains"):
         slices = [off[k:k + SLICE + 1] for k in range(0, n, SLICE)]
@@ -292,6 +304,46 @@ def replace_groups_child(rr, g, kind, dev, off, n, launches):
     line["fill_group_GB/s"] = round(totals["group"] / med["fill_group"] / 1e6, 1)
     line["fill_parent_literal_GB/s"] = round(totals["parent_literal"] / med["fill_parent_literal"] / 1e6, 1)
     print(json.dumps(line), flush=True)
+
+
+def multi_contains_child(rr, kind, dev, off, n, launches):
+    """Per K the set's one call and the K single-pattern calls on one indexed batch, alternating; one JSON line per K."""
+    import torch
+    nbytes = int(dev.numel())
+    items = rr.Items(dev, off, trim=1)
+    regs = [rr.RRegex(p) for p in MULTI_KEYWORDS]
+    bits = [torch.empty((n + 31) // 32, dtype=torch.int32, device="cuda") for _ in regs]
+    masks = torch.empty(n, dtype=torch.int32, device="cuda")
+    for k_set in MULTI_KS:
+        m = rr.RMulti(MULTI_KEYWORDS[:k_set])
+
+        def singles(k_set=k_set):
+            for r, b in zip(regs[:k_set], bits):
+                r.contains_items_bits(items, out=b)
+        calls = {"multi": lambda m=m: m.contains_items(items, out=masks), "singles": singles}
+        for _ in range(3):
+            for call in calls.values():
+                call()
+        torch.cuda.synchronize()
+        for k in range(k_set):
+            assert torch.equal(m.plane(masks, k), bits[k]), "the set and keyword %d differ" % k
+        counts = m.counts(masks).cpu().tolist()
+        ms = {k: [] for k in calls}
+        for _ in range(launches):
+            for k, call in calls.items():                   # alternating: every call of the set has the K single calls right beside it
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(); call(); b.record()
+                b.synchronize()
+                ms[k].append(a.elapsed_time(b))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        line = {"config": kind, "entry": "multi_contains", "K": k_set, "bytes": nbytes, "items": n, "groups": m.groups,
+                "rows": [m.group_states(g) for g in range(m.groups)], "stripe_wise_singles": bool(items.stripe_wise), "found": sum(counts)}
+        for k in calls:
+            line[k + "_ms"] = round(med[k], 4)
+            line[k + "_spread"] = round((max(ms[k]) - min(ms[k])) / med[k], 4)
+            line[k + "_TB/s"] = round(nbytes / med[k] / 1e9, 3)            # bytes of the column per second of the whole question
+        line["multi_over_singles"] = round(med["multi"] / med["singles"], 4)
+        print(json.dumps(line), flush=True)
 
 
 def pieces_child(rr, r, kind, dev, off, launches, skew):
@@ -536,6 +588,34 @@ def replace_groups_main(a):
         f.write(p.stdout)
 
 
+def multi_contains_main(a):
+    """One child on the keyword-log text, this tree alone; the lines and the break-even K to a.out."""
+    kind, pkey, nbytes = next(c for c in CONFIGS if c[0] == "kwlog")
+    n = int(nbytes * a.scale) // 4096 * 4096
+    env = dict(os.environ)
+    env.pop("RRX_LIB", None)
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", "multi_contains", "--launches", str(a.launches), "--child", ROOT, kind, pkey, str(n)],
+                       env=env, timeout=600, stdout=subprocess.PIPE, text=True)
+    sys.stdout.write(p.stdout)
+    sys.stdout.flush()
+    if p.returncode:                           # a fault or a time limit: nothing more is started on the device
+        raise SystemExit("child failed with %d: multi_contains %s" % (p.returncode, kind))
+    lines = [json.loads(x) for x in p.stdout.strip().splitlines()]
+    wins = [x["K"] for x in lines if x["multi_ms"] < x["singles_ms"]]
+    summary = {"entry": "multi_contains", "launches": max(a.launches, 12), "scale": a.scale, "K": [x["K"] for x in lines],
+               "multi_over_singles": [x["multi_over_singles"] for x in lines], "break_even_K": min(wins) if wins else None}
+    print(json.dumps(summary), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("tools/probe/item_lanes_rate.py --entry multi_contains --launches %d --scale %g: medians of device-event times per call [ms] on the\n"
+                "keyword-log text as items (trim 1), one indexed batch; multi = one rrx_multi_contains_items on K keywords (%s ...), singles = K\n"
+                "calls of rrx_contains_items, the two alternating in one process; TB/s = bytes of the column per second of the whole question;\n"
+                "break_even_K = the smallest measured K at which the set is the faster of the two (null: none).\n"
+                % (max(a.launches, 12), a.scale, ", ".join(MULTI_KEYWORDS[:4])))
+        for x in lines + [summary]:
+            f.write(json.dumps(x) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entry", choices=ENTRIES, required=True)
@@ -558,6 +638,8 @@ def main():
         return one_call_main(a)
     if a.entry == "replace_groups":
         return replace_groups_main(a)
+    if a.entry == "multi_contains":
+        return multi_contains_main(a)
     assert os.path.exists(os.path.join(a.old, "roaringregex_amd", "librrx.so")), "build the parent commit under %s first" % a.old
     # a parent that has the entry runs the entry itself: the yardsticks are for the commit that added it
     yardstick = a.entry in YARDSTICK and NEWER[a.entry] not in open(os.path.join(a.old, "roaringregex_amd", "__init__.py")).read()
