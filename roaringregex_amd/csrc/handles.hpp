@@ -22,6 +22,7 @@
 #include "pack.hpp"
 #include "plan.hpp"
 #include "sampled.hpp"
+#include "table_order.hpp"
 #include "template.hpp"
 
 // ---- errors: the calling thread's text behind rrx_last_error (regex.cpp)

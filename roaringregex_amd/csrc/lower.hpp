@@ -18,13 +18,19 @@
 // Every rewrite here (trim, NUL removal, in-label split, bisimulation quotients, subset construction) keeps
 // the accepted language of the reference automaton; tests/test_lowering.py replays the programs on the CPU
 // and compares with the oracle.
+//
+// Where things live:
+//   lower_trim.cpp     trim (the useful part of the reference automaton, dominated edges dropped)
+//   lower_reduce.cpp   reduce: the position graph, its bisimulation quotients, the two prunes, the twin merge
+//   lower_nfa.cpp      lower_nfa and its path cover
+//   lower_dfa.cpp      everything that needs partition refinement: lower_dfa, lower_dfa_sampled, the search, longest-search and
+//                      contains tables, the pattern-set product
+//   lower_tables.cpp   the table forms the kernels read: lower_search_line, lower_search_line2, lower_dfa2
+//   lower_internal.hpp what those units share; nothing else includes it
+//   table_order.hpp    the order of the stride-2 table in LDS (order_dfa2, TableOrderSearch); once_task.hpp: OnceTask (header only)
 #pragma once
-#include <atomic>
 #include <cstdint>
-#include <functional>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "frontend.hpp"
@@ -37,7 +43,7 @@ struct Trimmed {
     uint32_t initial = 0;
     std::vector<uint8_t> is_final;
     std::vector<std::vector<Edge>> out;     // labels never contain NUL (it cannot occur inside a string); dominated edges
-                                            //   dropped (lower.cpp: trim) - every state keeps its language
+                                            //   dropped (lower_trim.cpp: trim) - every state keeps its language
     std::vector<uint32_t> ref_id;           // state id in the reference numbering
     uint32_t ncls = 1;                      // byte classes; class 0 = bytes on which nothing moves
     uint8_t cls[256];                       // byte -> class (0x00 and >= 0x80 are class 0)
@@ -92,44 +98,6 @@ struct Dfa2Program {
 // value is an ordinary symbol of the pattern - '\n' too -, what ends a line is the code 128, which the kernel puts in the place
 // of the bytes the item index marks.
 bool lower_dfa2(const DfaProgram &d, uint32_t max_cols, Dfa2Program &out, bool items = false);
-// Profile-guided ORDER of the stride-2 table's rows and columns in LDS.  The table's entry for (state s, pair column c) sits at
-// word row_slot[s] * (ncols | 1) + col_slot[c], i.e. in LDS bank (row_slot[s] * (ncols | 1) + col_slot[c]) mod 32: the order
-// costs no memory and decides which entries collide when the 32 lanes of a half-wave look up 32 different (state, column)
-// pairs.  `sample` = the first `bytes_per_lane` bytes of `lanes` consecutive-by-32 stripes of the corpus (lane-major): the
-// lanes of a group are stepped in lockstep, as the kernel steps them, from the dead state (a stripe begins inside somebody's
-// line), and the hottest rows and columns are moved, one swap at a time, to the slots that lower the mean of the worst
-// bank's distinct entries per half-wave.  Returns that mean before and after.  State 0 (dead) keeps slot 0.
-struct Dfa2OrderStats { double before = 0, after = 0; uint32_t half_waves = 0, evaluations = 0; };
-Dfa2OrderStats order_dfa2(const Dfa2Program &d, const uint8_t *sample, uint32_t lanes, uint32_t bytes_per_lane,
-                          std::vector<uint32_t> &row_slot, std::vector<uint32_t> &col_slot);
-
-// A piece of host work that is decided ONCE per object and may run beside the caller (host only: no device call in here).
-// start() or skip() moves kIdle on, everything else only READS the atomic state - the std::thread is touched by its owner
-// alone (start under `mu_`, wait()).  The job runs in the deciding caller's thread or in a thread of its own (joined by
-// wait() / the destructor); the state becomes kDone when it returns.
-class OnceTask {
-public:
-    enum State { kIdle = 0, kRunning = 1, kDone = 2, kSkipped = 3 };
-    OnceTask() = default;
-    OnceTask(const OnceTask &) = delete;
-    OnceTask &operator=(const OnceTask &) = delete;
-    ~OnceTask() { wait(); }
-    State state() const { return (State)state_.load(std::memory_order_acquire); }
-    bool decided() const { return state() != kIdle; }
-    bool start(std::function<void()> job, bool background);       // false: decided before (by another caller)
-    bool skip();                // kIdle -> kSkipped; false: decided before
-    void wait();                // returns when no job of this object is running in a thread of its own any more
-private:
-    std::atomic<int> state_{kIdle};
-    std::mutex mu_;             // guards thread_
-    std::thread thread_;
-};
-// The order search of the stride-2 table (order_dfa2) as such a task: `d` must outlive it; `apply` runs in the searching thread.
-class TableOrderSearch : public OnceTask {
-public:
-    using Apply = std::function<void(std::vector<uint32_t> &&row_slot, std::vector<uint32_t> &&col_slot, const Dfa2OrderStats &)>;
-    bool start(const Dfa2Program &d, std::vector<uint8_t> sample, uint32_t lanes, uint32_t bytes_per_lane, bool background, Apply apply);
-};
 
 // The trimmed automaton re-expressed over "positions" (a state split by the character set it is entered on; node 0
 // = the initial state before any input), shrunk by bisimulation quotients and pruning of dominated edges.

@@ -3,6 +3,7 @@
 #include <cstdio>
 
 #include "handles.hpp"
+#include "table_order.hpp"
 
 using namespace rrx;
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "lower.hpp"
+#include "once_task.hpp"
 #include "plan.hpp"
 
 namespace rrx {

@@ -6,7 +6,7 @@
 //     of every row are zero, and P8 lies inside the image at a 16-byte boundary; elsewhere the descriptor holds no P8.
 // Then the rule itself on synthetic programs at the bound (64 and 65 columns unreplicated, 32 / 33 and 16 / 17 with copies), and
 // pack_dfa2 refusing a byte-wide table that does not fit.  Built by tests/test_dfa2_byte_pairs_lowering.py with
-// -fsanitize=address,undefined from csrc/frontend.cpp + lower.cpp + pack.cpp + plan.cpp: no HIP involved.  A mismatch aborts.
+// -fsanitize=address,undefined from the host pipeline's units (csrc/host_sources.mk: HOST_SRCS): no HIP involved.  A mismatch aborts.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>

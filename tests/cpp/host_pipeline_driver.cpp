@@ -1,7 +1,7 @@
 // host_pipeline_driver.cpp — runs the host compile pipeline (pattern -> reference-numbered automaton -> trim ->
 // reduce -> NFA / DFA / stride-2 programs) over the patterns given on stdin, one per line.  Built by
 // tests/test_lowering.py with -fsanitize=address,undefined (sanitizers run on the CPU build only) from
-// csrc/frontend.cpp + csrc/lower.cpp + csrc/pack.cpp + csrc/plan.cpp: no HIP involved.  Prints one summary line per pattern.
+// the host pipeline's units (csrc/host_sources.mk: HOST_SRCS): no HIP involved.  Prints one summary line per pattern.
 //
 // Every device image whose preconditions the programs meet - by the library's own fit rules (csrc/plan.hpp) - is packed
 // (csrc/pack.hpp), copied, bound to the copy and decoded back here - independently of the packer - against the program it was

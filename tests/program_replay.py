@@ -1,7 +1,21 @@
 """Test-side interpreters of the serialised device programs (rrx_program_words; layout in DESIGN.md
 "Device programs").  They restate what kernels.hip's engines do per byte, in numpy/python ints, so that the
 host lowering can be checked against the oracle on the CPU.  Test infrastructure only."""
+import os
+import re
+
 import numpy as np
+
+
+def host_pipeline_sources():
+    """The HIP-free host pipeline's translation units (csrc/host_sources.mk: HOST_SRCS) as paths, for the tests that build a driver
+    of their own from them."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "roaringregex_amd", "csrc")
+    defs = dict(re.findall(r"^(\w+) *= *(.*)$", open(os.path.join(csrc, "host_sources.mk")).read(), re.M))
+
+    def expand(text):
+        return re.sub(r"\$\((\w+)\)", lambda m: expand(defs[m.group(1)]), text)
+    return [os.path.join(csrc, f) for f in expand(defs["HOST_SRCS"]).split()]
 
 
 class NfaReplay:

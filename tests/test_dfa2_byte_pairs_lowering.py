@@ -8,6 +8,7 @@ import subprocess
 import bench
 import roaringregex_amd as rr
 from patterns import EMAIL, K1000, K1000_CONTAINS, KAT, U2
+from program_replay import host_pipeline_sources
 
 
 def test_byte_wide_pair_table_equals_the_u16_table(tmp_path):
@@ -15,8 +16,8 @@ def test_byte_wide_pair_table_equals_the_u16_table(tmp_path):
     csrc = os.path.join(root, "roaringregex_amd", "csrc")
     exe = str(tmp_path / "dfa2_byte_pairs_asan")
     # (the translation units are compiled side by side, unoptimised: the driver runs for a second or two, the compiler is the cost)
-    flags = ["g++", "-std=c++17", "-O0", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc]
-    srcs = [os.path.join(root, "tests", "cpp", "dfa2_byte_pairs_driver.cpp")] + [os.path.join(csrc, f) for f in ("frontend.cpp", "lower.cpp", "pack.cpp", "plan.cpp")]
+    flags = ["g++", "-std=c++17", "-O0", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread", "-I", csrc]
+    srcs = [os.path.join(root, "tests", "cpp", "dfa2_byte_pairs_driver.cpp")] + host_pipeline_sources()
     objs = [str(tmp_path / (os.path.basename(f) + ".o")) for f in srcs]
     jobs = [subprocess.Popen(flags + ["-c", f, "-o", o]) for f, o in zip(srcs, objs)]
     assert all(j.wait() == 0 for j in jobs)

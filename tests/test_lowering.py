@@ -8,7 +8,7 @@ import pytest
 
 import roaringregex_amd as rr
 from patterns import EMAIL, K1000, K1000_CONTAINS, KAT, U2, random_pattern, strings_near
-from program_replay import Dfa2ItemsReplay, Dfa2Replay, DfaReplay, NfaReplay, SampledReplay
+from program_replay import Dfa2ItemsReplay, Dfa2Replay, DfaReplay, NfaReplay, SampledReplay, host_pipeline_sources
 from pyoracle import OracleError, OracleRegex
 
 
@@ -146,7 +146,7 @@ def test_block_program_beyond_4096_positions():
 
 
 def test_profiled_order_of_the_stride2_table():
-    """order_dfa2 (lower.cpp) through its host-side entry: on a sample of URL text - 256 lanes, 32 consecutive ones 4 KiB apart
+    """order_dfa2 (table_order.cpp) through its host-side entry: on a sample of URL text - 256 lanes, 32 consecutive ones 4 KiB apart
     as a half-wave's stripes are - the search must return two permutations (state 0 stays in slot 0), must not raise the
     conflict figure it minimises, and must lower it on this text; the logical program (and so every replay) is untouched.
     A second call, or a call after the order was decided, is refused."""
@@ -353,9 +353,8 @@ def test_host_pipeline_is_clean_under_asan_and_ubsan(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "roaringregex_amd", "csrc")
     exe = str(tmp_path / "host_pipeline_asan")
-    subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc,
-                           os.path.join(root, "tests", "cpp", "host_pipeline_driver.cpp"), os.path.join(csrc, "frontend.cpp"),
-                           os.path.join(csrc, "lower.cpp"), os.path.join(csrc, "pack.cpp"), os.path.join(csrc, "plan.cpp"), "-o", exe])
+    subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread", "-I", csrc,
+                           os.path.join(root, "tests", "cpp", "host_pipeline_driver.cpp")] + host_pipeline_sources() + ["-o", exe])
     rng = random.Random(2024)
     pats = [k["pattern"] for k in KAT["kat"]] + [b["pattern"] for b in KAT["big_states"]]
     pats += [EMAIL, U2, "a{1,300}", "(a|b)*a(a|b){12}", "(a|b)*a(a|b){40}", K1000_CONTAINS]

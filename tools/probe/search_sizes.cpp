@@ -1,6 +1,7 @@
 // Sizes of the search tables (host only): rows x columns of the line-mode product table, what a Mealy minimisation of it
 // leaves, and the number of distinct pair columns of its stride-2 form.
-// build + run: g++ -std=c++17 -O2 -o /tmp/search_sizes tools/probe/search_sizes.cpp roaringregex_amd/csrc/frontend.cpp roaringregex_amd/csrc/lower.cpp -pthread && /tmp/search_sizes
+// build + run, in roaringregex_amd/csrc, with HOST_SRCS as host_sources.mk there lists them:
+//   g++ -std=c++17 -O2 -o /tmp/search_sizes ../../tools/probe/search_sizes.cpp $HOST_SRCS -pthread && /tmp/search_sizes
 #include <cstdio>
 #include <map>
 #include <string>

@@ -8,6 +8,7 @@
 
 #include "../../roaringregex_amd/csrc/frontend.hpp"
 #include "../../roaringregex_amd/csrc/lower.hpp"
+#include "../../roaringregex_amd/csrc/table_order.hpp"
 
 using namespace rrx;
 

@@ -1,4 +1,4 @@
-// The background order search's state machine (lower.hpp: TableOrderSearch) under ThreadSanitizer (CPU only; GPU sanitizers
+// The background order search's state machine (table_order.hpp: TableOrderSearch) under ThreadSanitizer (CPU only; GPU sanitizers
 // are not available on this pool): several threads race to start the search of one regex (rrx_match_corpus's first call and
 // rrx_order_table), others poll its state the way rrx_table_order does and read the "descriptor" under the owner's mutex the way
 // a launch does, and the owner is destroyed while the search may still run.  build + run: make -C tools/sanitize tsan
@@ -11,6 +11,7 @@
 
 #include "../../roaringregex_amd/csrc/frontend.hpp"
 #include "../../roaringregex_amd/csrc/lower.hpp"
+#include "../../roaringregex_amd/csrc/table_order.hpp"
 
 using namespace rrx;
 
