@@ -691,7 +691,20 @@ int rrx_replace_groups_longest_items(const rrx_group *const *groups, size_t ngro
  * nitems whose mask has bit k.  rrx_multi_plane: bit `pattern` (< 32, RRX_ERR_ARG otherwise) of every mask as a bitmap in the
  * layout of rrx_contains_extents - ceil(nitems / 32) whole words, the bits beyond nitems 0 - so that rrx_bitmap_count and
  * rrx_bitmap_to_bytes apply.  Both take any column of masks and no handle.
- * Not here: a '\n'-corpus form, stripe-wise or stride-2 forms, more than 32 patterns per handle.                                 */
+ * THE '\n'-CORPUS FORM, rrx_multi_contains_corpus: d_mask holds rrx_corpus_num_lines(c) 32-bit words, and word i is exactly what
+ * rrx_multi_contains_extents writes for an item made of the bytes of line i without its terminator - bit k is set exactly when
+ * member k is contained in line i.  All else follows: NUL and bytes >= 0x80 are ordinary text; a final fragment without '\n' is a
+ * line; an empty line gets the bits of the members that accept the empty string; bits K .. 31 are 0; a match never spans a '\n'
+ * ("ab" '\n' "c" does not contain ab+c), and a member whose pattern holds a '\n' can match only through its '\n'-free words.  For
+ * the members without '\n' in their pattern, bit k of word i also equals bit i of rrx_contains_corpus on member k.  A lane per
+ * stripe of the corpus, which reads its text in consecutive 16-byte loads and finds its line numbers through the corpus' index, in
+ * the place of a lane per item; one launch per group as above.  Every one of the words is written (the lane that owns a line owns
+ * its word: no atomics, nothing to clear beforehand), none beyond; a corpus of zero lines writes nothing and returns RRX_OK.
+ * Tables are uploaded at the first call on the device; from then on the entry is asynchronous on `stream` and can be captured
+ * into a graph: no read-back, no scratch, no event.  RRX_ERR_ARG for a null m, c or d_mask, checked before any device call.
+ * rrx_multi_counts and rrx_multi_plane apply to its output with nitems = the number of lines; the plane then has the layout of
+ * rrx_contains_corpus' bitmap.
+ * Not here: a stride-2 form of the product table, more than 32 patterns per handle.                                              */
 typedef struct rrx_multi rrx_multi;
 int rrx_multi_compile(const char *const *patterns, size_t npatterns, rrx_multi **out);
 int rrx_multi_compile_ex(const char *const *patterns, size_t npatterns, int engine, uint32_t max_rows, rrx_multi **out);
@@ -704,6 +717,7 @@ size_t rrx_multi_program_words(const rrx_multi *m, size_t group, uint32_t *out, 
 int rrx_multi_contains_extents(const rrx_multi *m, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                                uint32_t *d_mask, void *stream);
 int rrx_multi_contains_items(const rrx_multi *m, const rrx_items *items, uint32_t *d_mask, void *stream);
+int rrx_multi_contains_corpus(const rrx_multi *m, const rrx_corpus *c, uint32_t *d_mask, void *stream);
 int rrx_multi_counts(int device, const uint32_t *d_mask, size_t nitems, uint64_t *d_counts, void *stream);
 int rrx_multi_plane(int device, const uint32_t *d_mask, size_t nitems, uint32_t pattern, uint32_t *d_bits, void *stream);
 

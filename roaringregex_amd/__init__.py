@@ -63,7 +63,8 @@ ABI_SYMBOLS = (
     "rrx_template_compile", "rrx_template_free", "rrx_template_refs", "rrx_template_segments",
     "rrx_replace_template_sizes", "rrx_replace_template_fill", "rrx_replace_groups_longest_extents", "rrx_replace_groups_longest_items",
     "rrx_multi_compile", "rrx_multi_compile_ex", "rrx_multi_free", "rrx_multi_patterns", "rrx_multi_groups", "rrx_multi_group_mask",
-    "rrx_multi_group_states", "rrx_multi_program_words", "rrx_multi_contains_extents", "rrx_multi_contains_items", "rrx_multi_counts", "rrx_multi_plane",
+    "rrx_multi_group_states", "rrx_multi_program_words", "rrx_multi_contains_extents", "rrx_multi_contains_items", "rrx_multi_contains_corpus",
+    "rrx_multi_counts", "rrx_multi_plane",
 )
 
 
@@ -196,6 +197,7 @@ def _load():
         "rrx_multi_program_words": (sz, [vp, sz, vp, sz]),
         "rrx_multi_contains_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp]),
         "rrx_multi_contains_items": (i32, [vp, vp, vp, vp]),
+        "rrx_multi_contains_corpus": (i32, [vp, vp, vp, vp]),
         "rrx_multi_counts": (i32, [i32, vp, sz, vp, vp]),
         "rrx_multi_plane": (i32, [i32, vp, sz, u32, vp, vp]),
     }
@@ -1418,6 +1420,16 @@ class RMulti:
         with _on(items.device, stream):
             out = self._masks(items.num_items, items.data.device, out)
             _check(_L.rrx_multi_contains_items(self._h, items._h, _ptr(out), _stream_ptr(stream)))
+        return out
+
+    def contains_corpus(self, corpus, out=None, stream=None):
+        """Line i of the corpus, without its '\\n', as the item -> an int32 tensor of corpus.num_lines masks, bit k = the line contains
+        a match of patterns[k] (rrx_multi_contains_corpus: a lane per stripe of the text).  Every word is written.  counts() and
+        plane() apply; a plane has the layout of RRegex.contains_corpus_bits.  Asynchronous on `stream`."""
+        with _on(corpus.device, stream):
+            out = self._masks(corpus.num_lines, corpus.data.device, out)
+            if out.numel():                        # (a corpus without lines: no word to write, and the entry refuses a null d_mask)
+                _check(_L.rrx_multi_contains_corpus(self._h, corpus._h, _ptr(out), _stream_ptr(stream)))
         return out
 
     def counts(self, masks, stream=None):

@@ -291,6 +291,15 @@ int multi_counts(const uint32_t *mask, size_t nitems, unsigned long long *counts
 // bit `pattern` of every mask as a bitmap in contains_extents_dfa's layout: ceil(nitems / 32) whole words, plain stores
 int multi_plane(const uint32_t *mask, size_t nitems, uint32_t pattern, uint32_t *bits, void *stream);
 
+// ---- which patterns of a set each line of a '\n'-corpus contains, a lane per stripe: kernels_multi_corpus.hip
+// The same table and the same answer per item, the items being the corpus' lines without their '\n' (a last fragment without one
+// is a line; '\n' never reaches the table): out[i] = (first ? 0 : out[i]) | the mask of line i, for every line of the corpus and no
+// word beyond - the lane that owns the stripe a line STARTS in owns its word: plain stores, nothing to clear beforehand.  bytes,
+// nbytes, stripe, stripe_base[nstripes + 1], nstripes: the corpus and its index (count_newlines_per_stripe, scan_counts); bytes is
+// 16-byte aligned, no byte at or beyond nbytes is read.  Placement (in_global) as for multi_contains_extents.
+int multi_contains_corpus(const MultiDevice &p, bool in_global, bool first, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                          size_t nstripes, uint32_t *out, void *stream);
+
 // ---- first match per explicit item, a lane per item: kernels_search_items.hip
 // The two search tables in their plain form, one image: fwd = "any bytes, then the pattern" (accepting exactly where a match ends),
 // rev = the pattern right to left (accepting, walking back from a match end, exactly where a match starts; row 0 dead and absorbing:

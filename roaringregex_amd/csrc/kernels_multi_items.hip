@@ -2,45 +2,11 @@
 // lane-per-item kernel on the product table of a group of members (lower.hpp: MultiProgram), and the two small kernels that read a
 // column of masks: per-pattern totals (rrx_multi_counts) and one pattern's bit as a bitmap (rrx_multi_plane).
 #include "item_lanes.hpp"
+#include "multi_engines.hpp"
 
 namespace rrx {
 namespace dev {
 namespace {
-
-// The product table in LDS: the plain DFA engine's layout with a 32-bit mask per row in the place of its accept byte.
-struct MultiLdsEngine {
-    const uint8_t *cls;      // LDS [256]
-    const uint16_t *next;    // LDS [nstates][ncls]
-    const uint32_t *mask;    // LDS [nstates]
-    uint32_t ncls;
-
-    static size_t lds_bytes(const MultiDevice &p) { return multi_lds_bytes(p.nstates, p.ncls); }
-    __device__ void load(const MultiDevice &p, uint8_t *lds) {
-        const size_t tb = ((size_t)p.nstates * p.ncls * 2 + 15) & ~(size_t)15;
-        uint16_t *n = reinterpret_cast<uint16_t *>(lds);
-        uint8_t *c = lds + tb;
-        uint32_t *m = reinterpret_cast<uint32_t *>(c + 256);
-        for (int i = threadIdx.x; i < (int)(p.nstates * p.ncls); i += blockDim.x) n[i] = p.next[i];
-        for (int i = threadIdx.x; i < 256; i += blockDim.x) c[i] = p.cls[i];
-        for (int i = threadIdx.x; i < (int)p.nstates; i += blockDim.x) m[i] = p.mask[i];
-        next = n; cls = c; mask = m; ncls = p.ncls;
-    }
-    __device__ __forceinline__ uint32_t step(uint32_t s, uint32_t c) const { return next[s * ncls + cls[c]]; }
-};
-// The same table left in HBM/L2 (a group beyond the LDS budget, a set compiled for the global form): the class map in LDS.
-struct MultiGlobalEngine {
-    const uint8_t *cls;                   // LDS [256]
-    const uint16_t *__restrict__ next;    // HBM / L2
-    const uint32_t *__restrict__ mask;    // HBM / L2
-    uint32_t ncls;
-
-    static size_t lds_bytes(const MultiDevice &) { return 256; }
-    __device__ void load(const MultiDevice &p, uint8_t *lds) {
-        for (int i = threadIdx.x; i < 256; i += blockDim.x) lds[i] = p.cls[i];
-        cls = lds; next = p.next; mask = p.mask; ncls = p.ncls;
-    }
-    __device__ __forceinline__ uint32_t step(uint32_t s, uint32_t c) const { return next[(size_t)s * ncls + cls[c]]; }
-};
 
 // One lane per item: contains_extents_kernel's walk (item_lanes.hpp: aligned on the offset, nothing kills), with a mask in the place
 // of the verdict.  Per byte the row steps and, on the rows that carry a mask (s >= first_hit) only, the mask is ORed in - that read

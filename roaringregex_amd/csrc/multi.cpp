@@ -1,6 +1,7 @@
 // multi.cpp — rrx_multi: a set of up to 32 patterns, its members cut into groups that share one product table each (plan.hpp:
 // plan_multi), and the entries that say which of the patterns every item of a batch contains (rrx_multi_contains_extents /
-// _items: kernels_multi_items.hip, one launch per group), with the two readers of a mask column (rrx_multi_counts, rrx_multi_plane).
+// _items: kernels_multi_items.hip, one launch per group) or every line of a '\n'-corpus (rrx_multi_contains_corpus:
+// kernels_multi_corpus.hip, the same launches stripe-wise), with the two readers of a mask column (rrx_multi_counts, rrx_multi_plane).
 #include "items.hpp"
 
 using namespace rrx;
@@ -32,10 +33,10 @@ struct rrx_multi {
 namespace {
 
 // One launch per group that can find anything: the first one stores the masks, the others OR theirs in.  No such group - every
-// member the empty language -: the masks are cleared.
-int multi_contains(const rrx_multi *m, const ItemBatch &b, uint32_t *d_mask, void *stream) {
-    const auto &[device, bytes, off, nitems, trim] = b;
-    if (!nitems) return RRX_OK;
+// member the empty language -: the masks are cleared.  launch(table, in_global, first): a dev:: launcher on the nmasks items.
+template <class Launch>
+int multi_launches(const rrx_multi *m, int device, size_t nmasks, uint32_t *d_mask, void *stream, Launch launch) {
+    if (!nmasks) return RRX_OK;
     const std::vector<dev::MultiDevice> *t = nullptr;
     const int rc = m->tables(device, &t);
     if (rc) return rc;
@@ -43,13 +44,17 @@ int multi_contains(const rrx_multi *m, const ItemBatch &b, uint32_t *d_mask, voi
     bool first = true;
     for (size_t g = 0; g < t->size(); g++) {
         if (!(*t)[g].full) continue;
-        const int lrc = launched(dev::multi_contains_extents((*t)[g], m->plan.groups[g].in_global, first, bytes, off, nitems, trim, d_mask, stream),
-                                 "multi contains launch");
+        const int lrc = launched(launch((*t)[g], m->plan.groups[g].in_global, first), "multi contains launch");
         if (lrc) return lrc;
         first = false;
     }
-    if (first) HIP_TRY(hipMemsetAsync(d_mask, 0, nitems * sizeof(uint32_t), (hipStream_t)stream));
+    if (first) HIP_TRY(hipMemsetAsync(d_mask, 0, nmasks * sizeof(uint32_t), (hipStream_t)stream));
     return RRX_OK;
+}
+int multi_contains(const rrx_multi *m, const ItemBatch &b, uint32_t *d_mask, void *stream) {
+    return multi_launches(m, b.device, b.nitems, d_mask, stream, [&](const dev::MultiDevice &t, bool in_global, bool first) {
+        return dev::multi_contains_extents(t, in_global, first, b.bytes, b.off, b.nitems, b.trim, d_mask, stream);
+    });
 }
 
 }  // namespace
@@ -107,6 +112,13 @@ int rrx_multi_contains_extents(const rrx_multi *m, int device, const void *d_byt
 int rrx_multi_contains_items(const rrx_multi *m, const rrx_items *it, uint32_t *d_mask, void *stream) {
     if (!it || !batch_args_ok(m, batch_of(it), {d_mask})) return fail(RRX_ERR_ARG, "null argument");
     return multi_contains(m, batch_of(it), d_mask, stream);
+}
+
+int rrx_multi_contains_corpus(const rrx_multi *m, const rrx_corpus *c, uint32_t *d_mask, void *stream) {
+    if (!m || !c || !d_mask) return fail(RRX_ERR_ARG, "null argument");
+    return multi_launches(m, c->device, c->nlines, d_mask, stream, [&](const dev::MultiDevice &t, bool in_global, bool first) {
+        return dev::multi_contains_corpus(t, in_global, first, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_mask, stream);
+    });
 }
 
 int rrx_multi_counts(int device, const uint32_t *d_mask, size_t nitems, uint64_t *d_counts, void *stream) {

@@ -57,6 +57,13 @@ items (offsets = the line starts, trim 1: the '\\n' is the separator):
                   alternating inside one process, the masks checked against the K bitmaps bit for bit.  One child, this tree alone;
                   the lines and a summary (the smallest K at which the set wins, if any) go to `--out` as well.
 
+  multi_contains_corpus  the same question about the LINES of the keyword-log text held as an rrx_corpus (kernels_multi_corpus.hip, a
+                  lane per stripe), K = 1, 4, 16 and 32, three ways: (a) corpus = one rrx_multi_contains_corpus, (b) singles = K calls
+                  of rrx_contains_corpus, (c) items = rrx_multi_contains_items on an indexed batch over the same lines - the only
+                  one-walk way the parent commit offers -, the three alternating inside one process; (a)'s masks must equal (c)'s
+                  word for word and their planes (b)'s bitmaps.  A difference of two medians counts only beyond the sum of the two
+                  spreads [ms].  One child, this tree alone; the lines and a summary go to `--out` as well.
+
 A yardstick stands in only for a parent that lacks the entry (its wrapper shows it): a later parent runs the entry itself, and both
 sides must find the same.
 
@@ -72,6 +79,7 @@ between its two medians and its own spread - and whether each of the tree's medi
     python tools/probe/item_lanes_rate.py --entry one_call [--old .oldtree] [--launches 15] [--out profiles/one_call_items_rate.txt]
     python tools/probe/item_lanes_rate.py --entry replace_groups [--launches 15] [--scale 1.0] [--out profiles/replace_template_items_rate.txt]
     python tools/probe/item_lanes_rate.py --entry multi_contains [--launches 15] [--scale 1.0] [--out profiles/multi_contains_items_rate.txt]
+    python tools/probe/item_lanes_rate.py --entry multi_contains_corpus [--launches 15] [--scale 1.0] [--out profiles/multi_contains_corpus_rate.txt]
 """
 import argparse
 import json
@@ -83,7 +91,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CONFIGS = (("url", "U2", 1 << 30), ("email", "EMAIL", 1 << 30), ("kwlog", "K1000C", 1 << 30))
 ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "extract_group", "replace", "pieces", "one_call", "replace_groups",
-           "multi_contains")
+           "multi_contains", "multi_contains_corpus")
 MULTI_KS = (1, 4, 16, 32)                      # --entry multi_contains: the sizes of the keyword sets
 MULTI_KEYWORDS = ["k%d" % (61 * j + 17) for j in range(32)]     # k17, k78, ... k1908: the text's tokens are k1 .. k2000
 GROUPED = {"EMAIL": r"[A-Za-z0-9._]+@([A-Za-z0-9.]+)"}      # --entry extract_group: the patterns that need a group put in; group 1 everywhere
@@ -130,6 +138,8 @@ def child(tree, entry, kind, pkey, nbytes, launches):
         return replace_groups_child(rr, r, kind, dev, off, n, launches)
     if entry == "multi_contains":
         return multi_contains_child(rr, kind, dev, off, n, launches)
+    if entry == "multi_contains_corpus":
+        return multi_contains_corpus_child(rr, kind, dev, off, n, launches)
 
     if entry in ("match", "contains"):
         slices = [off[k:k + SLICE + 1] for k in range(0, n, SLICE)]
@@ -343,6 +353,57 @@ def multi_contains_child(rr, kind, dev, off, n, launches):
             line[k + "_spread"] = round((max(ms[k]) - min(ms[k])) / med[k], 4)
             line[k + "_TB/s"] = round(nbytes / med[k] / 1e9, 3)            # bytes of the column per second of the whole question
         line["multi_over_singles"] = round(med["multi"] / med["singles"], 4)
+        print(json.dumps(line), flush=True)
+
+
+def multi_contains_corpus_child(rr, kind, dev, off, n, launches):
+    """Per K the set's one call on the corpus, the K single-pattern calls on the corpus and the set's call on the indexed batch of the
+    same lines, alternating; one JSON line per K."""
+    import torch
+    nbytes = int(dev.numel())
+    corpus = rr.Corpus(dev)
+    assert corpus.num_lines == n
+    items = rr.Items(dev, off, trim=1)
+    regs = [rr.RRegex(p) for p in MULTI_KEYWORDS]
+    bits = [torch.empty((n + 31) // 32, dtype=torch.int32, device="cuda") for _ in regs]
+    masks, item_masks = torch.empty(n, dtype=torch.int32, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda")
+    for k_set in MULTI_KS:
+        m = rr.RMulti(MULTI_KEYWORDS[:k_set])
+
+        def singles(k_set=k_set):
+            for r, b in zip(regs[:k_set], bits):
+                r.contains_corpus_bits(corpus, out=b)
+        calls = {"corpus": lambda m=m: m.contains_corpus(corpus, out=masks), "singles": singles, "items": lambda m=m: m.contains_items(items, out=item_masks)}
+        masks.fill_(0x5A5A5A5A)
+        for _ in range(3):
+            for call in calls.values():
+                call()
+        torch.cuda.synchronize()
+        assert torch.equal(masks, item_masks), "the corpus form and the items form differ"
+        for k in range(k_set):
+            assert torch.equal(m.plane(masks, k), bits[k]), "the set and keyword %d differ" % k
+        counts = m.counts(masks).cpu().tolist()
+        ms = {k: [] for k in calls}
+        for _ in range(launches):
+            for k, call in calls.items():                   # alternating: every call has the other two right beside it
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(); call(); b.record()
+                b.synchronize()
+                ms[k].append(a.elapsed_time(b))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        spread = {k: max(v) - min(v) for k, v in ms.items()}
+        line = {"config": kind, "entry": "multi_contains_corpus", "K": k_set, "bytes": nbytes, "lines": n, "stripe": corpus.stripe, "groups": m.groups,
+                "rows": [m.group_states(g) for g in range(m.groups)], "stripe_wise_items": bool(items.stripe_wise), "found": sum(counts)}
+        for k in calls:
+            line[k + "_ms"] = round(med[k], 4)
+            line[k + "_spread"] = round(spread[k] / med[k], 4)
+            line[k + "_spread_ms"] = round(spread[k], 4)
+            line[k + "_TB/s"] = round(nbytes / med[k] / 1e9, 3)            # bytes of the text per second of the whole question
+        line["corpus_over_items"] = round(med["corpus"] / med["items"], 4)
+        line["corpus_over_singles"] = round(med["corpus"] / med["singles"], 4)
+        for other in ("items", "singles"):                  # a difference counts only beyond the sum of the two spreads
+            line["corpus_beats_" + other] = bool(med[other] - med["corpus"] > spread[other] + spread["corpus"])
+            line[other + "_beats_corpus"] = bool(med["corpus"] - med[other] > spread[other] + spread["corpus"])
         print(json.dumps(line), flush=True)
 
 
@@ -616,6 +677,38 @@ def multi_contains_main(a):
             f.write(json.dumps(x) + "\n")
 
 
+def multi_contains_corpus_main(a):
+    """One child on the keyword-log text, this tree alone; the lines and the break-even K against the single calls to a.out."""
+    kind, pkey, nbytes = next(c for c in CONFIGS if c[0] == "kwlog")
+    n = int(nbytes * a.scale) // 4096 * 4096
+    env = dict(os.environ)
+    env.pop("RRX_LIB", None)
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", "multi_contains_corpus", "--launches", str(a.launches), "--child", ROOT, kind, pkey,
+                        str(n)], env=env, timeout=600, stdout=subprocess.PIPE, text=True)
+    sys.stdout.write(p.stdout)
+    sys.stdout.flush()
+    if p.returncode:                           # a fault or a time limit: nothing more is started on the device
+        raise SystemExit("child failed with %d: multi_contains_corpus %s" % (p.returncode, kind))
+    lines = [json.loads(x) for x in p.stdout.strip().splitlines()]
+    wins = [x["K"] for x in lines if x["corpus_beats_singles"]]
+    summary = {"entry": "multi_contains_corpus", "launches": max(a.launches, 12), "scale": a.scale, "K": [x["K"] for x in lines],
+               "corpus_over_items": [x["corpus_over_items"] for x in lines], "corpus_over_singles": [x["corpus_over_singles"] for x in lines],
+               "corpus_beats_items": [x["corpus_beats_items"] for x in lines], "items_beats_corpus": [x["items_beats_corpus"] for x in lines],
+               "break_even_K": min(wins) if wins else None}
+    print(json.dumps(summary), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("tools/probe/item_lanes_rate.py --entry multi_contains_corpus --launches %d --scale %g: medians of device-event times per call [ms] on the\n"
+                "keyword-log text; corpus = one rrx_multi_contains_corpus on K keywords (%s ...) over the text as an rrx_corpus, singles = K calls\n"
+                "of rrx_contains_corpus on it, items = one rrx_multi_contains_items on an indexed batch over the same lines (trim 1), the three\n"
+                "alternating in one process; spread = (max - min) / median, spread_ms = max - min; TB/s = bytes of the text per second of the whole\n"
+                "question; x_beats_y = the medians differ by more than the sum of the two spreads [ms]; break_even_K = the smallest measured K\n"
+                "at which corpus beats singles (null: none).\n"
+                % (max(a.launches, 12), a.scale, ", ".join(MULTI_KEYWORDS[:4])))
+        for x in lines + [summary]:
+            f.write(json.dumps(x) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entry", choices=ENTRIES, required=True)
@@ -629,7 +722,8 @@ def main():
         tree, kind, pkey, nbytes = a.child
         return child(tree, a.entry, kind, pkey, int(nbytes), max(a.launches, 12))
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", ("replace_template" if a.entry == "replace_groups" else a.entry) + "_items_rate.txt")
+        stem = {"replace_groups": "replace_template_items", "multi_contains_corpus": "multi_contains_corpus"}.get(a.entry, a.entry + "_items")
+        a.out = os.path.join(ROOT, "profiles", stem + "_rate.txt")
     if a.entry == "replace":
         return replace_main(a)
     if a.entry == "pieces":
@@ -640,6 +734,8 @@ def main():
         return replace_groups_main(a)
     if a.entry == "multi_contains":
         return multi_contains_main(a)
+    if a.entry == "multi_contains_corpus":
+        return multi_contains_corpus_main(a)
     assert os.path.exists(os.path.join(a.old, "roaringregex_amd", "librrx.so")), "build the parent commit under %s first" % a.old
     # a parent that has the entry runs the entry itself: the yardsticks are for the commit that added it
     yardstick = a.entry in YARDSTICK and NEWER[a.entry] not in open(os.path.join(a.old, "roaringregex_amd", "__init__.py")).read()
