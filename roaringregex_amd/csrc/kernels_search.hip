@@ -693,7 +693,7 @@ __global__ __launch_bounds__(kSearchWaves * 64) __attribute__((amdgpu_waves_per_
         // round trips otherwise), stepped like the forward pass
         // kTurnWords text words per turn: four, or one in the passes that place every match (kFill, the second pass of kAll:
         // where every byte is a match - all matches of a{1,300} - the sixteen-byte turn measured 38 % SLOWER, 22.5 against 16.3 ms
-        // per GiB in the fill pass; tools/probe/search_ablate/follow_ab.sh)
+        // per GiB in the fill pass; profiles/r04_search_ablation.txt)
         constexpr int kTurnWords = kFollowTurnWords;
         auto follow_step = [&](uint32_t &acc, uint32_t &wrel) {   // -> the events of the bytes stepped (2 bits per byte, the first byte in bits 31..30)
             const size_t fpos = fbyte & ~(size_t)15;
@@ -965,26 +965,34 @@ __global__ __launch_bounds__(kSearchWaves * 64) __attribute__((amdgpu_waves_per_
 }  // namespace
 
 size_t search_chunk_bytes() { return kSearchChunk; }
-// forward tables (LDS form: pair table, gap, table; global form: pair table) + reverse table + class map + the waves' job pools
-static size_t search_table_bytes(const SearchChunkDevice &p) {
+// The LDS of a workgroup as the HOST sizes it, in one place (the kernel's prologue lays the same regions out in the same order - tab_end, R,
+// C, pool_all, stage - with its own arithmetic, so that its code stays what it was): forward tables (LDS form: pair table, gap, table up to
+// (base_row + nrows) * row_bytes; global form: pair table), reverse table, class map (64 words), the waves' job pools: fixed_bytes; then
+// [wave][arrays][stage_lines] staged entries.  arrays: packed results or counts; kFill / kAll: + the lines' slot bases.  stage_lines: what
+// the rest leaves of the budget (the whole LDS of a CU), a multiple of 64, kMaxStageLines at most; 0: not even 128 fit.
+struct SearchLdsLayout { size_t fixed_bytes, total_bytes; uint32_t arrays, stage_lines; };
+static SearchLdsLayout search_lds_layout(const SearchChunkDevice &p, int mode) {
+    SearchLdsLayout L;
     const size_t fwd = p.in_global ? (size_t)kSearchP16Bytes : ((size_t)p.base_row + p.nrows) * p.row_bytes;
-    return fwd + ((size_t)(p.nr * p.ncls + 1) / 2 + 64 + (size_t)kSearchWaves * kPoolWords) * 4;
+    L.fixed_bytes = fwd + ((size_t)(p.nr * p.ncls + 1) / 2 + 64 + (size_t)kSearchWaves * kPoolWords) * 4;
+    L.arrays = (mode == kFill || mode == kAll) ? 2u : 1u;
+    const size_t per = (size_t)kSearchWaves * 4 * L.arrays;       // bytes a staged line takes, over the waves
+    const size_t n = L.fixed_bytes + per * 128 > kSearchChunkLdsBudget ? 0 : (kSearchChunkLdsBudget - L.fixed_bytes) / per / 64 * 64;
+    L.stage_lines = (uint32_t)(n > kMaxStageLines ? kMaxStageLines : n);
+    L.total_bytes = L.fixed_bytes + per * L.stage_lines;
+    return L;
 }
-// staged entries per wave: what the tables and the job pools leave of the budget (the whole LDS of a CU), a multiple of 64, 128 at least
-// (one array of packed results or counts; the fill pass also keeps the lines' slot bases)
+// staged entries per wave (SearchLdsLayout::stage_lines) of a program the kernel can take; 0: it cannot
 static uint32_t search_stage_lines(const SearchChunkDevice &p, int mode) {
-    const size_t tb = search_table_bytes(p), per = (size_t)kSearchWaves * 4 * ((mode == kFill || mode == kAll) ? 2 : 1);
-    if (tb + per * 128 > kSearchChunkLdsBudget) return 0;
+    const SearchLdsLayout L = search_lds_layout(p, mode);
+    if (!L.stage_lines) return 0;
     if ((size_t)p.nr * p.ncls * 2 > 65534 || p.ncls > 128) return 0;      // reverse rows are addressed by 16-bit byte offsets, classes doubled in a byte
     if (!p.in_global && (p.base_row + p.nrows > 4096 || p.ncols2 > 127 || (p.row_bytes & 3) || p.base_row * p.row_bytes < kSearchP8Bytes)) return 0;
     if (p.in_global && ((size_t)p.nrows * p.ncols2 * 4 >= ((size_t)1 << 28) || p.ncols2 > 16383)) return 0;
-    size_t n = (kSearchChunkLdsBudget - tb) / per;
-    n = n / 64 * 64;
-    return (uint32_t)(n > kMaxStageLines ? kMaxStageLines : n);
+    return L.stage_lines;
 }
 size_t search_chunks_lds_bytes(const SearchChunkDevice &p) {          // of the most demanding mode (fill)
-    const uint32_t n = search_stage_lines(p, kFill);
-    return n ? search_table_bytes(p) + (size_t)kSearchWaves * 8 * n : (size_t)kSearchChunkLdsBudget + 1;
+    return search_stage_lines(p, kFill) ? search_lds_layout(p, kFill).total_bytes : (size_t)kSearchChunkLdsBudget + 1;
 }
 template <int MODE, int FORM, bool MULTI = false>
 static int launch_search_chunks_form(const SearchChunkDevice &p, bool clean, const uint8_t *bytes, size_t nbytes, const uint64_t *chunk_base, size_t nchunks,
@@ -992,7 +1000,7 @@ static int launch_search_chunks_form(const SearchChunkDevice &p, bool clean, con
     if (!nchunks) return 0;
     const uint32_t lines = search_stage_lines(p, MODE);
     if (!lines) return (int)hipErrorInvalidValue;
-    const size_t lds = search_table_bytes(p) + (size_t)kSearchWaves * 4 * ((MODE == kFill || MODE == kAll) ? 2 : 1) * lines;
+    const size_t lds = search_lds_layout(p, MODE).total_bytes;
     static LdsAttr attr;
     hipError_t e = ensure_dynamic_lds(attr, reinterpret_cast<const void *>(search_chunks_kernel<MODE, FORM, MULTI>), lds, /*at_zero=*/true);
     if (e != hipSuccess) return (int)e;
@@ -1013,21 +1021,18 @@ static int launch_search_chunks_form(const SearchChunkDevice &p, bool clean, con
                        nbytes, chunk_base, nchunks, first, out0, out1, lines, all);
     return (int)hipGetLastError();
 }
-template <int MODE>
+template <int MODE, bool MULTI = false>
 static int launch_search_chunks(const SearchChunkDevice &p, bool clean, const uint8_t *bytes, size_t nbytes, const uint64_t *chunk_base, size_t nchunks,
                                 const uint64_t *first, uint32_t *out0, uint32_t *out1, void *stream, SearchAllArgs all = SearchAllArgs()) {
-    return p.in_global ? launch_search_chunks_form<MODE, kGlobalForm>(p, clean, bytes, nbytes, chunk_base, nchunks, first, out0, out1, stream, all)
-                       : launch_search_chunks_form<MODE, kLdsForm>(p, clean, bytes, nbytes, chunk_base, nchunks, first, out0, out1, stream, all);
+    return p.in_global ? launch_search_chunks_form<MODE, kGlobalForm, MULTI>(p, clean, bytes, nbytes, chunk_base, nchunks, first, out0, out1, stream, all)
+                       : launch_search_chunks_form<MODE, kLdsForm, MULTI>(p, clean, bytes, nbytes, chunk_base, nchunks, first, out0, out1, stream, all);
 }
 int search_chunks(const SearchChunkDevice &p, bool clean, const uint8_t *bytes, size_t nbytes, const uint64_t *chunk_base, size_t nchunks, size_t nlines,
                   uint32_t *match_start, uint32_t *match_end, void *stream) {
     // a corpus whose chunks hold more lines than the staging array (on average, with a margin): the build that takes them in windows
     const uint32_t staged = search_stage_lines(p, kFirst);
-    if (nchunks && staged && (double)nlines / (double)nchunks > 0.8 * staged) {
-        SearchAllArgs none;
-        return p.in_global ? launch_search_chunks_form<kFirst, kGlobalForm, true>(p, clean, bytes, nbytes, chunk_base, nchunks, nullptr, match_start, match_end, stream, none)
-                           : launch_search_chunks_form<kFirst, kLdsForm, true>(p, clean, bytes, nbytes, chunk_base, nchunks, nullptr, match_start, match_end, stream, none);
-    }
+    if (nchunks && staged && (double)nlines / (double)nchunks > 0.8 * staged)
+        return launch_search_chunks<kFirst, true>(p, clean, bytes, nbytes, chunk_base, nchunks, nullptr, match_start, match_end, stream);
     return launch_search_chunks<kFirst>(p, clean, bytes, nbytes, chunk_base, nchunks, nullptr, match_start, match_end, stream);
 }
 int search_chunks_count(const SearchChunkDevice &p, bool clean, const uint8_t *bytes, size_t nbytes, const uint64_t *chunk_base, size_t nchunks,
