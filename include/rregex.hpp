@@ -132,6 +132,12 @@ public:
         auto *f = static_cast<DeviceIterFactory *>(iter_factory.get());
         if (rrx_contains_corpus(f->handle(), corpus, d_bits, stream) != RRX_OK) throw std::runtime_error(rrx_last_error());
     }
+    // the LEFTMOST-LONGEST match of every string (rrx_search_longest_corpus): d_start[i] the smallest start, d_end[i] the largest end
+    // from there, relative to the string; 0xFFFFFFFF in both = none.  What regexp_extract, find and grep -o mean.
+    void search_longest_corpus(const rrx_corpus *corpus, uint32_t *d_start, uint32_t *d_end, void *stream = nullptr) {
+        auto *f = static_cast<DeviceIterFactory *>(iter_factory.get());
+        if (rrx_search_longest_corpus(f->handle(), corpus, d_start, d_end, stream) != RRX_OK) throw std::runtime_error(rrx_last_error());
+    }
     // the same for a device buffer that has no rrx_corpus yet: ONE pass over the text (no index pass); returns the number
     // of strings; d_accept_bits holds cap_words words.  Synchronous.
     size_t match_device(const void *d_bytes, size_t nbytes, uint32_t *d_accept_bits, size_t cap_words, void *stream = nullptr) {

@@ -325,6 +325,21 @@ int rrx_search_longest_extents(const rrx_regex *re, int device, const void *d_by
                                uint32_t *d_start, uint32_t *d_end, void *stream);
 int rrx_search_longest_items(const rrx_regex *re, const rrx_items *items, uint32_t *d_start, uint32_t *d_end, void *stream);
 
+/* The LEFTMOST-LONGEST match of every LINE of a '\n'-corpus: what grep -o prints first on each line.  ONE RULE: d_start and d_end hold
+ * rrx_corpus_num_lines(c) words each, and words i are exactly what rrx_search_longest_extents writes for an item made of the bytes
+ * of line i without its '\n'.  So: offsets are relative to the line's first byte and 0xFFFFFFFF in both words means no match;
+ * leftmost beats longer; NUL and bytes >= 0x80 are text that no pattern takes; a final fragment without '\n' is a line; no match
+ * spans a '\n' - the byte never reaches a table - and a pattern that holds '\n' matches only through its '\n'-free words; a pattern
+ * that accepts the empty string gives d_start[i] = 0 and d_end[i] = the longest accepted prefix on every line, [0, 0) on an empty
+ * one; an empty-language pattern gives 0xFFFFFFFF everywhere (two fills, no table, no pass over the text); a line longer than
+ * 0xFFFFFFFE bytes is searched as if it ended at its offset 0xFFFFFFFE.  Every one of the 2 x lines words is written on `stream`,
+ * whatever it held, and nothing behind them; a corpus of zero lines writes nothing and returns RRX_OK - an unsupported regex is
+ * still reported.  A lane per stripe of the text on the corpus' own stripe index: no offsets array is built or used.  FULLY
+ * asynchronous on `stream` and capturable into a graph once the tables are uploaded (the first call on a device uploads them): no
+ * read-back, no scratch, no event.  Tables, their placement and RRX_ERR_UNSUPPORTED as for rrx_search_longest_extents; RRX_ERR_ARG
+ * for a null re, c, d_start or d_end, before any device call.                                                                 */
+int rrx_search_longest_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_start, uint32_t *d_end, void *stream);
+
 /* EVERY match of every item, left to right: rrx_search_all* for explicit items (what regexp_count, regexp_extract_all,
  * regexp_replace and split need of a string column).  Item i is d_bytes[d_off[i] .. d_off[i+1] - trim), as in rrx_search_extents.
  * The matches of an item are those of rrx_search_extents applied repeatedly TO THE REST OF THE ITEM behind the previous match:

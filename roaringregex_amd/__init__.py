@@ -50,7 +50,7 @@ ABI_SYMBOLS = (
     "rrx_search_extents", "rrx_search_items",
     "rrx_search_all_extents_count", "rrx_search_all_extents_fill", "rrx_search_all_extents",
     "rrx_search_all_items_count", "rrx_search_all_items_fill", "rrx_search_all_items",
-    "rrx_search_longest_extents", "rrx_search_longest_items",
+    "rrx_search_longest_extents", "rrx_search_longest_items", "rrx_search_longest_corpus",
     "rrx_search_all_longest_marks_words",
     "rrx_search_all_longest_extents_count", "rrx_search_all_longest_extents_fill", "rrx_search_all_longest_extents",
     "rrx_search_all_longest_items_count", "rrx_search_all_longest_items_fill", "rrx_search_all_longest_items",
@@ -150,6 +150,7 @@ def _load():
         "rrx_search_all_items": (i32, [vp, vp, vp, vp, vp, sz, C.POINTER(sz), vp]),
         "rrx_search_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, vp]),
         "rrx_search_longest_items": (i32, [vp, vp, vp, vp, vp]),
+        "rrx_search_longest_corpus": (i32, [vp, vp, vp, vp, vp]),
         "rrx_search_all_longest_marks_words": (sz, [sz, sz]),
         "rrx_search_all_longest_extents_count": (i32, [vp, i32, vp, vp, sz, u32, vp, sz, vp, vp]),
         "rrx_search_all_longest_extents_fill": (i32, [vp, i32, vp, vp, sz, u32, vp, sz, vp, vp, vp, vp]),
@@ -633,6 +634,16 @@ class RRegex:
             start, end = _span_pair(corpus.num_lines, corpus.data.device)
             _check(_L.rrx_search_corpus(self._h, corpus._h, _ptr(start), _ptr(end), _stream_ptr(stream)))
         return start, end
+
+    def search_longest_corpus(self, corpus, stream=None):
+        """Per string the LEFTMOST-LONGEST match [start, end) (rrx_search_longest_corpus): the smallest start, then the largest end
+        from there, as two int32 tensors of offsets relative to the start of the string; (-1, -1) where nothing is accepted.  Exactly
+        what search_longest_extents gives for the strings as items; '\\n' never takes part in a match."""
+        with _on(corpus.device, stream):
+            n = corpus.num_lines                   # (a word at least: the entry refuses a null array, and reports an unsupported regex for no line too)
+            start, end = _span_pair(max(n, 1), corpus.data.device)
+            _check(_L.rrx_search_longest_corpus(self._h, corpus._h, _ptr(start), _ptr(end), _stream_ptr(stream)))
+        return start[:n], end[:n]
 
     def search_all(self, corpus, stream=None):
         """ALL lazy matches of every string, left to right -> (count[n] int32, first[n] int64, start[total] int32,

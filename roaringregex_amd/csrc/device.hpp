@@ -343,6 +343,16 @@ struct SearchLongestDevice {
 int search_longest_extents_dfa(const SearchLongestDevice &p, bool in_global, bool nullable, const uint8_t *bytes, const uint64_t *off, size_t nitems,
                                uint32_t trim, uint32_t *match_start, uint32_t *match_end, void *stream);
 
+// ---- leftmost-longest match per line of a '\n'-corpus, a lane per stripe: kernels_search_longest_corpus.hip
+// The same two tables and the same answer per item, the items being the corpus' lines without their '\n' (a last fragment without
+// one is a line; '\n' never reaches a table): match_start[i], match_end[i] for every line i of the corpus and no word beyond - the
+// lane that owns the stripe a line ENDS in owns its two words: plain stores, nothing to clear beforehand (between the kernel's two
+// phases a line's words hold its start and its length).  bytes, nbytes, stripe, stripe_base[nstripes + 1], nstripes: the corpus and
+// its index as for multi_contains_corpus; bytes is 16-byte aligned, no byte below offset 0 or at or beyond nbytes is read.
+// nullable, in_global and lines beyond 0xFFFFFFFE bytes as for search_longest_extents_dfa.
+int search_longest_corpus_dfa(const SearchLongestDevice &p, bool in_global, bool nullable, const uint8_t *bytes, size_t nbytes, uint32_t stripe,
+                              const uint64_t *stripe_base, size_t nstripes, uint32_t *match_start, uint32_t *match_end, void *stream);
+
 // ---- all leftmost-longest matches per explicit item, a lane per item: kernels_search_all_longest_items.hip
 // The matches of item i are those of search_longest_extents_dfa applied again and again to the rest of the item behind the previous
 // match (one byte further after an empty match).  first == nullptr (COUNT): the backward walk on starts leaves a MARK bit in `marks`

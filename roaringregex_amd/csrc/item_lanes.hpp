@@ -3,7 +3,9 @@
 // kernels_table.hip and kernels_nfa.inc (match_extents_kernel), kernels_contains_items.hip, kernels_search_items.hip,
 // kernels_search_all_items.hip, kernels_search_longest_items.hip, kernels_search_all_longest_items.hip, kernels_replace_items.hip,
 // kernels_replace_template_items.hip, kernels_pieces_items.hip (no walk in these three: their kernels take the span, the loop and the
-// launcher), kernels_group_items.hip and kernels_multi_items.hip (contains_extents_kernel's walk on a product table).
+// launcher), kernels_group_items.hip and kernels_multi_items.hip (contains_extents_kernel's walk on a product table) - and by
+// kernels_search_longest_corpus.hip, a lane-per-STRIPE kernel, for the launcher, the result constants and the placement rule of the
+// two plain tables alone.
 //
 // THE WALK, described here once.  A lane reads its item [b, e) straight from HBM/L2, forwards or backwards, in three stretches:
 // single bytes up to a 16-byte boundary, one uint4 per 16 bytes (forwards the low byte first, backwards the high byte), single

@@ -41,6 +41,12 @@ __device__ __forceinline__ uint64_t line_of(uint64_t base) { return base & ~kFre
 // (measured -47 %, profiles/r01_v7_result_path_probes.txt).
 __device__ __forceinline__ uint4 load_text(const uint4 *p) { return *p; }
 
+// exact: a 0x80 flag per byte of w that equals '\n'
+__device__ __forceinline__ uint32_t newline_flags(uint32_t w) {
+    const uint32_t t = w ^ 0x0a0a0a0au;
+    return ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) & 0x80808080u;
+}
+
 // Workgroup copy of a device table into LDS, 16 bytes per lane per access and kBatch accesses in flight per lane
 // (instead of one dword per trip of a `for (i = tid; i < n; i += blockDim.x)` loop).  Measured neutral on the stride-2
 // engine, same box, old against new build (profiles/r02_headline_ab.txt): the table copy is not where a launch's fixed
@@ -69,7 +75,8 @@ __device__ __forceinline__ void copy_table_to_lds(void *dst_lds, const void *src
 }
 
 // One round of a lane's text: N 16-byte slots requested as ONE burst (they merge into one request per 128-byte line)
-// and consumed in order.  The slots are members reached through compile-time recursion, never an indexed array: an
+// and consumed in order (for_each_slot_down: from the highest address down, for a kernel that walks right to left).
+// The slots are members reached through compile-time recursion, never an indexed array: an
 // engine whose step contains a loop keeps the compiler from unrolling a slot loop, and an indexed buffer then lives in
 // scratch memory (measured on the first NFA engine: 144 bytes of scratch per lane, 18 ms per GiB).
 template <int N>
@@ -78,12 +85,14 @@ struct TextRound {
     TextRound<N - 1> rest;
     __device__ __forceinline__ void load(const uint4 *p) { head = load_text(p); rest.load(p + 1); }
     template <class F> __device__ __forceinline__ void for_each_slot(F &&f) const { f(head); rest.for_each_slot(f); }
+    template <class F> __device__ __forceinline__ void for_each_slot_down(F &&f) const { rest.for_each_slot_down(f); f(head); }
     template <class F> __device__ __forceinline__ void for_each_slot_mut(F &&f) { f(head); rest.for_each_slot_mut(f); }
 };
 template <>
 struct TextRound<0> {
     __device__ __forceinline__ void load(const uint4 *) {}
     template <class F> __device__ __forceinline__ void for_each_slot(F &&) const {}
+    template <class F> __device__ __forceinline__ void for_each_slot_down(F &&) const {}
     template <class F> __device__ __forceinline__ void for_each_slot_mut(F &&) {}
 };
 

@@ -6,12 +6,6 @@ namespace rrx {
 namespace dev {
 namespace {
 
-// exact: a 0x80 flag per byte of w that equals '\n'
-__device__ __forceinline__ uint32_t newline_flags(uint32_t w) {
-    const uint32_t t = w ^ 0x0a0a0a0au;
-    return ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) & 0x80808080u;
-}
-
 // Lane g owns the lines that START in stripe g - lines lo .. past - 1, from the corpus' stripe index exactly as recheck_escaped_kernel
 // takes them - and walks from the stripe's first byte: a stripe that begins inside somebody else's line is skipped to behind its
 // first '\n', and the last line is followed past the end of the stripe to its '\n' or to the end of the data.  A lane without a

@@ -74,6 +74,23 @@ int rrx_search_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_star
     return launched(dev::search_chunks(*ct, c->has_high, c->d_bytes, c->nbytes, c->d_chunk_base, c->nchunks, c->nlines, d_start, d_end, stream), "search_chunks launch");
 }
 
+// The LEFTMOST-LONGEST match of every line: rrx_search_longest_extents' tables, answer and shortcuts (item_search.cpp) with the
+// corpus' lines as the items, a lane per stripe on the corpus' own stripe index - no line offsets, no chunk index, nothing read back.
+int rrx_search_longest_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_start, uint32_t *d_end, void *stream) {
+    if (!re || !c || !d_start || !d_end) return fail(RRX_ERR_ARG, "null argument");
+    const dev::SearchLongestDevice *t;
+    const int rc = tables_on(re, c->device, &rrx_regex::search_longest_tables, &t);
+    if (rc || !c->nlines) return rc;
+    if (!t) {                                                        // the empty language matches nowhere: two fills, no table, no text
+        HIP_TRY(hipMemsetAsync(d_start, 0xff, c->nlines * sizeof(uint32_t), (hipStream_t)stream));
+        HIP_TRY(hipMemsetAsync(d_end, 0xff, c->nlines * sizeof(uint32_t), (hipStream_t)stream));
+        return RRX_OK;
+    }
+    return launched(dev::search_longest_corpus_dfa(*t, re->requested == RRX_ENGINE_DFA_GLOBAL, re->search_longest.nullable, c->d_bytes, c->nbytes, c->stripe,
+                                                   c->d_base, c->nstripes, d_start, d_end, stream),
+                    "search_longest_corpus launch");
+}
+
 int rrx_search_all_count(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_count, void *stream) {
     if (!re || !c || (c->nlines && !d_count)) return fail(RRX_ERR_ARG, "null argument");
     const dev::SearchChunkDevice *ct;

@@ -64,6 +64,14 @@ items (offsets = the line starts, trim 1: the '\\n' is the separator):
                   word for word and their planes (b)'s bitmaps.  A difference of two medians counts only beyond the sum of the two
                   spreads [ms].  One child, this tree alone; the lines and a summary go to `--out` as well.
 
+  search_longest_corpus  the leftmost-longest match of every LINE of the keyword-log and the e-mail text held as an rrx_corpus
+                  (kernels_search_longest_corpus.hip, a lane per stripe), three ways alternating inside one process: (a) corpus =
+                  rrx_search_longest_corpus, (b) items = rrx_search_longest_items on an indexed batch over the same lines - the
+                  parent commit's code and the nearest thing it has -, (c) first = rrx_search_corpus, the other question on the
+                  same shape, a yardstick for what the two passes cost; (a) must equal (b) word for word before anything is timed.
+                  A difference of two medians counts only beyond the sum of the two spreads [ms].  One child per text, this tree
+                  alone; the lines go to `--out` as well.
+
 A yardstick stands in only for a parent that lacks the entry (its wrapper shows it): a later parent runs the entry itself, and both
 sides must find the same.
 
@@ -80,6 +88,7 @@ between its two medians and its own spread - and whether each of the tree's medi
     python tools/probe/item_lanes_rate.py --entry replace_groups [--launches 15] [--scale 1.0] [--out profiles/replace_template_items_rate.txt]
     python tools/probe/item_lanes_rate.py --entry multi_contains [--launches 15] [--scale 1.0] [--out profiles/multi_contains_items_rate.txt]
     python tools/probe/item_lanes_rate.py --entry multi_contains_corpus [--launches 15] [--scale 1.0] [--out profiles/multi_contains_corpus_rate.txt]
+    python tools/probe/item_lanes_rate.py --entry search_longest_corpus [--launches 15] [--scale 1.0] [--out profiles/search_longest_corpus_rate.txt]
 """
 import argparse
 import json
@@ -91,7 +100,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CONFIGS = (("url", "U2", 1 << 30), ("email", "EMAIL", 1 << 30), ("kwlog", "K1000C", 1 << 30))
 ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "extract_group", "replace", "pieces", "one_call", "replace_groups",
-           "multi_contains", "multi_contains_corpus")
+           "multi_contains", "multi_contains_corpus", "search_longest_corpus")
 MULTI_KS = (1, 4, 16, 32)                      # --entry multi_contains: the sizes of the keyword sets
 MULTI_KEYWORDS = ["k%d" % (61 * j + 17) for j in range(32)]     # k17, k78, ... k1908: the text's tokens are k1 .. k2000
 GROUPED = {"EMAIL": r"[A-Za-z0-9._]+@([A-Za-z0-9.]+)"}      # --entry extract_group: the patterns that need a group put in; group 1 everywhere
@@ -140,6 +149,8 @@ def child(tree, entry, kind, pkey, nbytes, launches):
         return multi_contains_child(rr, kind, dev, off, n, launches)
     if entry == "multi_contains_corpus":
         return multi_contains_corpus_child(rr, kind, dev, off, n, launches)
+    if entry == "search_longest_corpus":
+        return search_longest_corpus_child(rr, r, kind, dev, off, n, launches)
 
     if entry in ("match", "contains"):
         slices = [off[k:k + SLICE + 1] for k in range(0, n, SLICE)]
@@ -405,6 +416,53 @@ def multi_contains_corpus_child(rr, kind, dev, off, n, launches):
             line["corpus_beats_" + other] = bool(med[other] - med["corpus"] > spread[other] + spread["corpus"])
             line[other + "_beats_corpus"] = bool(med["corpus"] - med[other] > spread[other] + spread["corpus"])
         print(json.dumps(line), flush=True)
+
+
+def search_longest_corpus_child(rr, r, kind, dev, off, n, launches):
+    """The leftmost-longest search of every line three ways, alternating: (a) corpus = rrx_search_longest_corpus on the text as an
+    rrx_corpus, (b) items = rrx_search_longest_items on an indexed batch over the same lines (trim 1), (c) first = rrx_search_corpus,
+    the other question on the same corpus; one JSON line."""
+    import torch
+    nbytes = int(dev.numel())
+    corpus = rr.Corpus(dev)
+    assert corpus.num_lines == n
+    items = rr.Items(dev, off, trim=1)
+    out = {k: (torch.empty(n, dtype=torch.int32, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda")) for k in ("corpus", "items", "first")}
+    stream = rr._stream_ptr(None)
+    ptrs = {k: (s.data_ptr(), e.data_ptr()) for k, (s, e) in out.items()}
+    calls = {"corpus": lambda: rr._check(rr._L.rrx_search_longest_corpus(r._h, corpus._h, *ptrs["corpus"], stream)),
+             "items": lambda: rr._check(rr._L.rrx_search_longest_items(r._h, items._h, *ptrs["items"], stream)),
+             "first": lambda: rr._check(rr._L.rrx_search_corpus(r._h, corpus._h, *ptrs["first"], stream))}
+    for t in out["corpus"]:
+        t.fill_(0x5A5A5A5A)
+    for _ in range(3):
+        for call in calls.values():
+            call()
+    torch.cuda.synchronize()
+    assert torch.equal(out["corpus"][0], out["items"][0]) and torch.equal(out["corpus"][1], out["items"][1]), "the corpus form and the items form differ"
+    found = out["corpus"][1] >= 0
+    assert torch.equal(out["first"][1] >= 0, found), "the leftmost-longest search and the first-match search find different lines"
+    ms = {k: [] for k in calls}
+    for _ in range(launches):
+        for k, call in calls.items():                       # alternating: every call has the other two right beside it
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); call(); b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    spread = {k: max(v) - min(v) for k, v in ms.items()}
+    line = {"config": kind, "entry": "search_longest_corpus", "bytes": nbytes, "lines": n, "stripe": corpus.stripe, "found": int(found.sum()),
+            "matched_bytes": int((out["corpus"][1] - out["corpus"][0])[found].sum())}
+    for k in calls:
+        line[k + "_ms"] = round(med[k], 4)
+        line[k + "_spread"] = round(spread[k] / med[k], 4)
+        line[k + "_spread_ms"] = round(spread[k], 4)
+        line[k + "_TB/s"] = round(nbytes / med[k] / 1e9, 3)
+    line["corpus_over_items"] = round(med["corpus"] / med["items"], 4)
+    line["corpus_over_first"] = round(med["corpus"] / med["first"], 4)
+    line["corpus_beats_items"] = bool(med["items"] - med["corpus"] > spread["items"] + spread["corpus"])     # beyond the sum of the two spreads
+    line["items_beats_corpus"] = bool(med["corpus"] - med["items"] > spread["items"] + spread["corpus"])
+    print(json.dumps(line), flush=True)
 
 
 def pieces_child(rr, r, kind, dev, off, launches, skew):
@@ -709,6 +767,32 @@ def multi_contains_corpus_main(a):
             f.write(json.dumps(x) + "\n")
 
 
+def search_longest_corpus_main(a):
+    """One child per text - the keyword log and the e-mail text -, this tree alone; the lines to a.out."""
+    lines = []
+    for kind, pkey, nbytes in (c for c in CONFIGS if c[0] in ("kwlog", "email")):
+        n = int(nbytes * a.scale) // 4096 * 4096
+        env = dict(os.environ)
+        env.pop("RRX_LIB", None)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", "search_longest_corpus", "--launches", str(a.launches), "--child", ROOT, kind,
+                            pkey, str(n)], env=env, timeout=600, stdout=subprocess.PIPE, text=True)
+        sys.stdout.write(p.stdout)
+        sys.stdout.flush()
+        if p.returncode:                       # a fault or a time limit: nothing more is started on the device
+            raise SystemExit("child failed with %d: search_longest_corpus %s" % (p.returncode, kind))
+        lines.append(json.loads(p.stdout.strip().splitlines()[-1]))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("tools/probe/item_lanes_rate.py --entry search_longest_corpus --launches %d --scale %g: medians of device-event times per call [ms];\n"
+                "corpus = rrx_search_longest_corpus on the text as an rrx_corpus, items = rrx_search_longest_items on an indexed batch over the same\n"
+                "lines (trim 1; its offsets array is built beforehand and not timed), first = rrx_search_corpus on the same corpus - another question,\n"
+                "the yardstick for what two passes cost; the three alternating in one process, corpus == items word for word before timing; spread =\n"
+                "(max - min) / median, spread_ms = max - min; TB/s = bytes of the text per second; x_beats_y = the medians differ by more than the\n"
+                "sum of the two spreads [ms].\n" % (max(a.launches, 12), a.scale))
+        for x in lines:
+            f.write(json.dumps(x) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entry", choices=ENTRIES, required=True)
@@ -722,7 +806,8 @@ def main():
         tree, kind, pkey, nbytes = a.child
         return child(tree, a.entry, kind, pkey, int(nbytes), max(a.launches, 12))
     if a.out is None:
-        stem = {"replace_groups": "replace_template_items", "multi_contains_corpus": "multi_contains_corpus"}.get(a.entry, a.entry + "_items")
+        stem = {"replace_groups": "replace_template_items", "multi_contains_corpus": "multi_contains_corpus",
+                "search_longest_corpus": "search_longest_corpus"}.get(a.entry, a.entry + "_items")
         a.out = os.path.join(ROOT, "profiles", stem + "_rate.txt")
     if a.entry == "replace":
         return replace_main(a)
@@ -736,6 +821,8 @@ def main():
         return multi_contains_main(a)
     if a.entry == "multi_contains_corpus":
         return multi_contains_corpus_main(a)
+    if a.entry == "search_longest_corpus":
+        return search_longest_corpus_main(a)
     assert os.path.exists(os.path.join(a.old, "roaringregex_amd", "librrx.so")), "build the parent commit under %s first" % a.old
     # a parent that has the entry runs the entry itself: the yardsticks are for the commit that added it
     yardstick = a.entry in YARDSTICK and NEWER[a.entry] not in open(os.path.join(a.old, "roaringregex_amd", "__init__.py")).read()
