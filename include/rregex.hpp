@@ -138,6 +138,17 @@ public:
         auto *f = static_cast<DeviceIterFactory *>(iter_factory.get());
         if (rrx_search_longest_corpus(f->handle(), corpus, d_start, d_end, stream) != RRX_OK) throw std::runtime_error(rrx_last_error());
     }
+    // the LEFTMOST-LONGEST match inside ONE device-resident string of any length (rrx_search_longest_string): d_span[0], d_span[1] = its
+    // start and end (device memory, two u64), ~0ull in both = none; '\n' is ordinary text.  Synchronous.
+    void search_longest_string(const void *d_bytes, size_t nbytes, uint64_t *d_span, void *stream = nullptr) {
+        auto *f = static_cast<DeviceIterFactory *>(iter_factory.get());
+        if (rrx_search_longest_string(f->handle(), f->device(), d_bytes, nbytes, d_span, stream) != RRX_OK) throw std::runtime_error(rrx_last_error());
+    }
+    // whether ONE device-resident string contains a match (rrx_contains_string): d_found[0] = 1 or 0.  Synchronous.
+    void contains_string(const void *d_bytes, size_t nbytes, uint8_t *d_found, void *stream = nullptr) {
+        auto *f = static_cast<DeviceIterFactory *>(iter_factory.get());
+        if (rrx_contains_string(f->handle(), f->device(), d_bytes, nbytes, d_found, stream) != RRX_OK) throw std::runtime_error(rrx_last_error());
+    }
     // the same for a device buffer that has no rrx_corpus yet: ONE pass over the text (no index pass); returns the number
     // of strings; d_accept_bits holds cap_words words.  Synchronous.
     size_t match_device(const void *d_bytes, size_t nbytes, uint32_t *d_accept_bits, size_t cap_words, void *stream = nullptr) {

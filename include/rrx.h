@@ -743,6 +743,24 @@ int rrx_multi_plane(int device, const uint32_t *d_mask, size_t nitems, uint32_t 
  * (a chunk that does not start on a 16-byte boundary is read byte by byte instead of sixteen bytes per load).    */
 int rrx_match_string(const rrx_regex *re, int device, const void *d_bytes, size_t nbytes, uint8_t *d_accept, void *stream);
 
+/* WHERE the leftmost-longest match inside ONE device-resident string of any length is.  One rule: d_span[0] and d_span[1] (device
+ * memory, two u64) are the start and the end that rrx_search_longest_extents writes for the one-item batch off = {0, nbytes},
+ * trim = 0 over the same bytes, widened to 64 bits - ~0ull in both for no match - without that entry's cap at offset 0xFFFFFFFE.
+ * So: the smallest start, then the largest end from there; '\n', NUL and bytes >= 0x80 are ordinary text of their class; a pattern
+ * that accepts the empty string gives start 0 and the longest accepted prefix; the empty string gives [0, 0) or none; the empty
+ * language gives none without a kernel.  rrx_contains_string: d_found[0] = 1 exactly when d_span[0] != ~0ull (the backward pass
+ * alone).  d_bytes needs no alignment.
+ * Strings of 2 KiB and more are cut into chunks that are walked in parallel (both search tables of at most 254 states): backwards
+ * over the whole string on the starts table, then forwards from the start found on the anchored table in windows that grow (256
+ * bytes, then 15 times what has been walked), until the table is dead or the string ends - a short match costs a short forward
+ * walk.  Shorter strings, larger tables and RRX_ENGINE_DFA_GLOBAL go through rrx_search_longest_extents as one item; on that path
+ * a string beyond 0xFFFFFFFE bytes is refused with RRX_ERR_UNSUPPORTED (it is never answered short).
+ * Both entries are synchronous with respect to `stream` (one small read-back per pass and forward window) and take the handle's
+ * scratch (concurrent callers of one regex take turns), as rrx_match_string does.  RRX_ERR_ARG for a null re, d_span / d_found,
+ * or a null d_bytes with nbytes > 0, before any device call; RRX_ERR_UNSUPPORTED where rrx_search_longest_extents reports it.  */
+int rrx_search_longest_string(const rrx_regex *re, int device, const void *d_bytes, size_t nbytes, uint64_t *d_span, void *stream);
+int rrx_contains_string(const rrx_regex *re, int device, const void *d_bytes, size_t nbytes, uint8_t *d_found, void *stream);
+
 /* ---- host-buffer conveniences (PCIe inclusive; synchronous) ------------------------------------------ */
 /* bytes/accept are HOST pointers; *nlines receives the number of strings; at most cap results are written */
 int rrx_match_host(const rrx_regex *re, int device, const void *bytes, size_t nbytes, uint8_t *accept, size_t cap,

@@ -44,7 +44,7 @@ ABI_SYMBOLS = (
     "rrx_corpus_one_launch", "rrx_match_flush_slots",
     "rrx_match_corpus", "rrx_match_device", "rrx_search_corpus", "rrx_search_all_count", "rrx_search_all_fill", "rrx_search_all", "rrx_bitmap_to_bytes",
     "rrx_match_extents", "rrx_items_create", "rrx_items_count", "rrx_items_stripe_wise", "rrx_items_free", "rrx_match_items",
-    "rrx_match_string", "rrx_match_host", "rrx_match_cstr",
+    "rrx_match_string", "rrx_match_host", "rrx_match_cstr", "rrx_search_longest_string", "rrx_contains_string",
     "rrx_contains_corpus", "rrx_contains_engine_name", "rrx_contains_states", "rrx_bitmap_count",
     "rrx_contains_extents", "rrx_contains_items",
     "rrx_search_extents", "rrx_search_items",
@@ -128,6 +128,8 @@ def _load():
         "rrx_items_free": (None, [vp]),
         "rrx_match_items": (i32, [vp, vp, vp, vp]),
         "rrx_match_string": (i32, [vp, i32, vp, sz, vp, vp]),
+        "rrx_search_longest_string": (i32, [vp, i32, vp, sz, vp, vp]),
+        "rrx_contains_string": (i32, [vp, i32, vp, sz, vp, vp]),
         "rrx_search_corpus": (i32, [vp, vp, vp, vp, vp]),
         "rrx_search_all_count": (i32, [vp, vp, vp, vp]),
         "rrx_search_all_fill": (i32, [vp, vp, vp, vp, vp, vp]),
@@ -1006,6 +1008,27 @@ class RRegex:
             out = torch.zeros(1, dtype=torch.uint8, device=data.device)
             _check(_L.rrx_match_string(self._h, data.device.index, _ptr(data), data.numel(),
                                        C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+        return bool(out.item())
+
+    def search_longest_string(self, data, stream=None):
+        """The LEFTMOST-LONGEST match inside ONE device-resident string of any length (rrx_search_longest_string): what
+        search_longest_extents gives for the whole string as one item, without its 32-bit cap; '\n' is an ordinary character.
+        -> (start, end) as ints, (-1, -1) for none"""
+        import torch
+        assert data.is_cuda and data.dtype == torch.uint8
+        with _on(data.device.index, stream):
+            out = torch.zeros(2, dtype=torch.int64, device=data.device)
+            _check(_L.rrx_search_longest_string(self._h, data.device.index, _ptr(data), data.numel(), _ptr(out), _stream_ptr(stream)))
+        start, end = out.tolist()
+        return start, end
+
+    def contains_string(self, data, stream=None):
+        """Whether ONE device-resident string of any length contains a match (rrx_contains_string).  -> bool"""
+        import torch
+        assert data.is_cuda and data.dtype == torch.uint8
+        with _on(data.device.index, stream):
+            out = torch.zeros(1, dtype=torch.uint8, device=data.device)
+            _check(_L.rrx_contains_string(self._h, data.device.index, _ptr(data), data.numel(), _ptr(out), _stream_ptr(stream)))
         return bool(out.item())
 
     def match_host(self, data):

@@ -457,9 +457,44 @@ int pieces_fill(const uint8_t *bytes, const uint64_t *piece_src, const uint64_t 
 // one state -> state map per chunk; maps are then composed in groups until one is left.  `scratch` holds the maps.
 constexpr uint32_t kLongMaxStates = 254;         // row offsets state * 129 stay 16-bit
 constexpr uint32_t kLongGroup = 128;             // maps composed per workgroup and level
+// short strings: 256-byte chunks (a string of a few KiB is a handful of short launches, not one long sequential lane);
+// from 256 KiB on chunks of 1 KiB or more, at most 65536 of them
+inline uint32_t long_chunk(size_t nbytes) {
+    uint32_t chunk = 256;
+    while (((nbytes + chunk - 1) / chunk) > (chunk < 1024 ? 1024u : 65536u)) chunk <<= 1;
+    return chunk;
+}
 size_t long_scratch_bytes(uint32_t nstates, size_t nbytes, uint32_t *chunk);
 int match_long_dfa(const DfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t chunk, void *scratch, uint8_t *accept,
                    void *stream);
+
+// ---- a directional run over one long string on a plain DFA: kernels_long_search.hip
+// The table p (at most kLongMaxStates states) stepped over bytes[0, nbytes), nbytes > 0, forwards (from byte 0 up) or backwards
+// (from byte nbytes - 1 down), from the state held in the device word *start_state, in chunks of long_chunk(nbytes) bytes counted
+// in WALKING order (chunk 0 is walked first; backwards the chunks are counted from the string's end):
+//   1  the chunk maps in walking order (kernels_long.hpp: the four-step build, the backward walk where `backward`);
+//   2  up-sweep: groups of kLongGroup maps composed level by level until a level has at most kLongGroup maps, EVERY level kept;
+//   3  down-sweep (long_entries_kernel): from that level down to the chunks, a workgroup per group stages the group's maps in LDS
+//      and walks them in order from the group's entry state: the state every child is entered in;
+//   4  extreme offset (long_extreme_kernel): a lane per chunk walks its chunk again from its entry state and keeps the LAST offset
+//      in walking order at which the table is in an accepting state after a byte, and the chunk's exit state; long_reduce_kernel
+//      takes the extreme of the chunks and the last chunk's exit state.
+// out->extreme: forwards the LARGEST p + 1 such that the table accepts after the byte at offset p, backwards the SMALLEST p such
+// that it accepts after the byte at p; ~0ull where it never accepts.  out->exit_state: the state after the whole run.  (The start
+// state itself is not an event: no byte has been taken.)  row0_dead: row 0 of p is dead and absorbing (the anchored table of
+// pack_search_longest) - lanes entered in it, or arriving there, stop.  A single chunk skips steps 1 to 3.  bytes needs no
+// alignment.  Everything is written with plain vector stores, nothing needs clearing beforehand; `scratch` holds
+// long_run_scratch_bytes(p.nstates, N) bytes for any N >= nbytes; out and start_state are device memory outside it (they may
+// be the same record of two consecutive runs' hand-over: start_state is read before out is written).
+struct LongRunResult {
+    uint64_t extreme;
+    uint32_t exit_state, pad;
+};
+size_t long_run_scratch_bytes(uint32_t nstates, size_t nbytes);
+int long_run_dfa(const DfaDevice &p, bool backward, bool row0_dead, const uint8_t *bytes, size_t nbytes, const uint32_t *start_state, void *scratch,
+                 LongRunResult *out, void *stream);
+// *word = value, on the stream (the start state of a first run)
+int long_set_word(uint32_t *word, uint32_t value, void *stream);
 
 // ---- search: kernels_search.hip
 // Search (the reference has acceptance only).  Per line: the match [s, e) with the smallest e, then the smallest s.
