@@ -91,8 +91,21 @@ int         rrx_order_table(rrx_regex *re, const void *sample, uint32_t lanes, u
  * rrx_match_items, trim 1) are stepped two bytes per lookup by a stride-2 table of their own - every byte value an ordinary
  * symbol, '\n' too, the separator a 129th - where the regex has a stride-2 table; 0 keeps them on the byte-stride items kernel
  * (which serves trim 0 either way).  Same results.                                                                         */
+/* RRX_OPT_CONTAINS_NFA (default 0): which engine rrx_contains_corpus, rrx_contains_extents and rrx_contains_items run on.
+ * 0: the contains table alone - a pattern without one, (a|b)*a(a|b){40}, is RRX_ERR_UNSUPPORTED.  1: where the regex has no contains
+ * table (its forward search automaton does not determinise within the state budget, or the table passes 2^24 entries) the three
+ * entries run on the shift-and NFA lane engine, the engine of rrx_match_corpus for such patterns, on a program of its own
+ * (RRX_PROGRAM_CONTAINS_NFA), built at the first use whatever engine the regex was compiled for; this needs a lane program of at
+ * most 16 words (512 positions after reduction) - beyond that RRX_ERR_UNSUPPORTED stays, its text naming both reasons.  2: the NFA
+ * lane engine always, also where a table exists (tests, A/B measurements).  Same results on every route, exactly those written at
+ * the three entries.  The NFA route is bound by the VALU and in another speed class than the tables, which is why a caller opts in.
+ * On it rrx_contains_corpus is one hipMemsetAsync and one kernel (it can be captured into a graph once the program is uploaded:
+ * after a first call), the items entries are a lane per item at every size - no extent bound, nothing read back, no scratch, no
+ * event -, and a pattern that accepts the empty string or has an empty language is answered with a fill, no kernel.
+ * rrx_contains_engine_name then says "nfa-shift-and"; rrx_contains_states keeps reporting the table's states (0: none).  May be set
+ * at any time; any other value: RRX_ERR_ARG.                                                                                  */
 enum { RRX_OPT_BACKGROUND_ORDER = 1, RRX_OPT_UNITS_PER_WORKGROUP = 2, RRX_OPT_SAMPLED_TABLE = 3, RRX_OPT_FLUSH_SLOTS = 4, RRX_OPT_SEARCH_ANCHORED = 5,
-       RRX_OPT_ITEMS_STRIDE2 = 6 };
+       RRX_OPT_ITEMS_STRIDE2 = 6, RRX_OPT_CONTAINS_NFA = 7 };
 int         rrx_set_option(rrx_regex *re, int option, int64_t value);
 /* The SAMPLED TABLE (an automaton that does not determinise - AUTO leaves it on the NFA lane engine - over text whose live sets
  * are few, README.md:18-21): the state sets a text sample reaches are interned into a table, every transition the sample and a
@@ -150,6 +163,11 @@ int         rrx_accepts_empty(const rrx_regex *re); /* Processor::operator*() on
 #define RRX_PROGRAM_SEARCH_ANCHORED 20 /* ... and the pattern's own DFA, DFA layout: state 0 dead and absorbing, class 0 leads there - stepped
                                          forwards from a match start, accepting where a match from there ends.  Both: 0 words where one
                                          of the two does not determinise within the state budget                                          */
+#define RRX_PROGRAM_CONTAINS_NFA 25    /* the program of contains on the NFA lane engine (RRX_OPT_CONTAINS_NFA; dumped whatever the option says),
+                                         RRX_ENGINE_NFA layout, with the B rows as its kernels see them: position 0 (bit 0 of word 0) in every
+                                         row, the rows of 0x00 and 0x80 ... 0xFF exactly {position 0}, the '\n' row the pattern's own plus
+                                         position 0 (the items kernel steps it; the corpus kernel puts {position 0} in its place).  0 words
+                                         where the pattern has no lane program of at most 16 words                                       */
 size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t cap);
 
 /* ---- batch of strings: the replacement for calling get_acceptance_iter(line)++ per string ------------ *

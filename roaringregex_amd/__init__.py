@@ -33,6 +33,8 @@ OPT_SAMPLED_TABLE = 3
 OPT_FLUSH_SLOTS = 4
 OPT_SEARCH_ANCHORED = 5
 OPT_ITEMS_STRIDE2 = 6
+OPT_CONTAINS_NFA = 7                                    # contains on the NFA lane engine: 0 never, 1 where there is no table, 2 always
+PROGRAM_CONTAINS_NFA = 25                               # the program it runs: the lane program with the contains B rows (NFA layout)
 
 # every symbol include/rrx.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = (
@@ -1155,6 +1157,12 @@ class RRegex:
         """rrx_set_option(RRX_OPT_ITEMS_STRIDE2): False keeps large batches of explicit items with separators (trim 1) on the
         byte-stride items kernel instead of the stride-2 table of their own."""
         _check(_L.rrx_set_option(self._h, OPT_ITEMS_STRIDE2, 1 if enabled else 0))
+
+    def set_contains_nfa(self, mode):
+        """rrx_set_option(RRX_OPT_CONTAINS_NFA): 0 keeps the three contains entries on the contains table (a pattern without one
+        raises), 1 runs them on the shift-and NFA lane engine where the pattern has no table, 2 always (tests, A/B measurements).
+        Same results; the NFA route is bound by the VALU, in another speed class than the tables.  Any other value raises."""
+        _check(_L.rrx_set_option(self._h, OPT_CONTAINS_NFA, int(mode)))
 
     def set_units_per_workgroup(self, units):
         """rrx_set_option(RRX_OPT_UNITS_PER_WORKGROUP): accepted and ignored - the kernel that handed its stripes out in units

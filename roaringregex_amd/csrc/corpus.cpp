@@ -255,8 +255,20 @@ int rrx_match_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_accep
 // bytes >= 0x80 the stride-2 table keeps its kernel - the instantiation that steps such bytes as 0x00, which is their class.
 int rrx_contains_corpus(const rrx_regex *re, const rrx_corpus *c, uint32_t *d_bits, void *stream) {
     if (!re || !c || (c->nlines && !d_bits)) return fail(RRX_ERR_ARG, "null argument");
+    // RRX_OPT_CONTAINS_NFA: the line engine with a sticky `found` on the program with the contains B rows - a clear and one kernel
+    bool on_nfa = false, fill = false;
+    const dev::NfaDevice *nfa = nullptr;
+    int rc = re->contains_nfa_tables(c->device, &on_nfa, &nfa, &fill);
+    if (rc) return rc;
+    if (on_nfa) {
+        HIP_TRY(hipSetDevice(c->device));
+        if (!c->nlines) return RRX_OK;
+        rc = fill_bitmap(d_bits, c->nlines, fill, stream);                  // (the kernels merge words with atomic OR)
+        if (rc || !nfa) return rc;
+        return launched(dev::contains_stripes_nfa(*nfa, c->d_bytes, c->nbytes, c->stripe, c->d_base, c->nstripes, d_bits, stream), "contains_stripes launch");
+    }
     const DeviceTables *t;
-    int rc = re->contains_tables(c->device, &t);
+    rc = re->contains_tables(c->device, &t);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (!c->nlines) return RRX_OK;

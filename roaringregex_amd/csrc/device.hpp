@@ -553,6 +553,13 @@ int recheck_escaped_nfa(const NfaDevice &p, const uint8_t *bytes, size_t nbytes,
                         uint32_t *accept_bits, void *stream);
 int match_extents_nfa(const NfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim,
                       uint8_t *accept, void *stream);
+// "Contains a match" on the lane program with the contains B rows (pack.hpp: contains_b_rows): the line engine with a sticky
+// `found` over the stripes of a corpus (the bitmap cleared by the caller: words are merged with atomic OR), and a lane per item
+// (every word of the bitmap written: nothing to clear).
+int contains_stripes_nfa(const NfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                         size_t nstripes, uint32_t *bits, void *stream);
+int contains_extents_nfa(const NfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim, uint32_t *bits,
+                         void *stream);
 // One long string on the NFA lane engines: per chunk the rows "positions reached from position p" (lane = (chunk, p)), then
 // the relations applied in order to {initial}.  `scratch` holds the rows (long_nfa_scratch_bytes).
 size_t long_nfa_scratch_bytes(const NfaDevice &p, size_t nbytes, uint32_t *chunk, uint32_t *nchunks);

@@ -32,6 +32,15 @@ inline int hip_fail(hipError_t e, const char *what) { return fail(RRX_ERR_HIP, s
 inline int launched(int e, const char *what) { return e ? hip_fail((hipError_t)e, what) : RRX_OK; }     // (what a dev:: launcher returned)
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(e_, #expr); } while (0)
 
+// A result bitmap of n bits filled on `stream` without a kernel: all clear, or - ones - the first n bits set and the rest of the
+// last word clear (contains on the NFA lane engine: the bitmap before the kernel; a nullable pattern; the empty language)
+inline int fill_bitmap(uint32_t *d_bits, size_t n, bool ones, void *stream) {
+    const size_t whole = ones ? n / 32 : (n + 31) / 32;
+    if (whole) HIP_TRY(hipMemsetAsync(d_bits, ones ? 0xff : 0, whole * sizeof(uint32_t), (hipStream_t)stream));
+    if (ones && (n & 31)) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_bits + whole), (int)((1u << (n & 31)) - 1u), 1, (hipStream_t)stream));
+    return RRX_OK;
+}
+
 // ---- owners
 // One device allocation, freed on its own device.
 struct DeviceAlloc {
@@ -135,6 +144,7 @@ struct rrx_regex : rrx::Programs {                       // (plan.hpp: the progr
     std::atomic<int> opt_sampled_table{1};               // RRX_OPT_SAMPLED_TABLE
     std::atomic<int> opt_flush_slots{0};                 // RRX_OPT_FLUSH_SLOTS (0: from the corpus' mean line length)
     std::atomic<int> items_stride2{1};                   // RRX_OPT_ITEMS_STRIDE2 (0: the byte-stride items kernel for trim 1 as well)
+    std::atomic<int> opt_contains_nfa{0};                // RRX_OPT_CONTAINS_NFA (0: tables only, 1: the NFA where there is no table, 2: always)
     mutable std::mutex mu;
     ~rrx_regex();                                        // waits for what may still use the members (threads, queued copies)
 
@@ -161,6 +171,19 @@ struct rrx_regex : rrx::Programs {                       // (plan.hpp: the progr
     bool built(const TableSet &set) const { return &set == &match_set || build_contains() == RRX_OK; }      // (call with `mu` held)
     const rrx::dev::Dfa2Device *items2_table(TableSet &set, int device) const;
     const rrx::dev::LineDfaDevice *items_table(TableSet &set, int device) const;
+    // ---- contains on the NFA lane engine (RRX_OPT_CONTAINS_NFA): the lane program with the contains B rows (plan.hpp:
+    // plan_contains_nfa), built at its first use whatever engine the regex was compiled for, uploaded once per device
+    mutable int contains_nfa_state = 0;  // 0 = not built, 1 = built, -1 = no lane program
+    mutable rrx::NfaProgram contains_nfa;
+    mutable std::map<int, OnDevice<rrx::dev::NfaDevice>> contains_nfa_on_device;
+    bool build_contains_nfa() const;     // host side (call with `mu` held); false: no lane program
+    // THE ROUTE of the three contains entries and of rrx_contains_engine_name, decided here and nowhere else (call with `mu` held):
+    // *nfa = the entry runs on the NFA lane engine - option 2, or option 1 where build_contains fails.  RRX_ERR_UNSUPPORTED where
+    // it should and the pattern has no lane program (the text names both reasons), and, on the table route, what build_contains says.
+    int contains_route(bool *nfa) const;
+    // The route, and on the NFA route the program on `device`: *out = nullptr where no kernel is needed - a pattern that accepts the
+    // empty string (every bit: *fill = true) and the empty language (no bit).  On the table route *nfa = false and nothing else is set.
+    int contains_nfa_tables(int device, bool *nfa, const rrx::dev::NfaDevice **out, bool *fill) const;
 
     // ---- search (built on first use; plan.hpp: plan_search)
     mutable int search_state = 0;        // 0 = not built, 1 = built, -1 = does not fit

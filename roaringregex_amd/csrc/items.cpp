@@ -171,11 +171,28 @@ int rrx_match_items(const rrx_regex *re, const rrx_items *it, uint8_t *d_accept,
 // "Which items contain a match": the same two paths on the contains set - stripe-wise wherever the contains table has an items form,
 // whatever the regex' MATCH engine is and at any alignment of the bitmap (the stripe-wise kernels write into scratch, the caller's
 // bitmap receives a masked copy).  An empty batch still reports a regex without a contains table.
+// RRX_OPT_CONTAINS_NFA: the route of both entries.  *taken: the batch is answered here, on the NFA lane engine - always a lane per
+// item (kernels_nfa.inc: contains_extents_nfa_kernel), which writes every word of the bitmap: no extent bound, nothing read back,
+// no scratch, no event; a pattern that accepts the empty string and the empty language: a fill, no kernel.
+static int contains_on_nfa(const rrx_regex *re, int device, const uint8_t *b, const uint64_t *d_off, size_t nitems, uint32_t trim, uint32_t *d_bits,
+                           void *stream, bool *taken) {
+    bool fill = false;
+    const dev::NfaDevice *nfa = nullptr;
+    const int rc = re->contains_nfa_tables(device, taken, &nfa, &fill);
+    if (rc || !*taken) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if (!nitems) return RRX_OK;
+    if (!nfa) return fill_bitmap(d_bits, nitems, fill, stream);
+    return launched(dev::contains_extents_nfa(*nfa, b, d_off, nitems, trim, d_bits, stream), "contains_extents launch");
+}
 int rrx_contains_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                          uint32_t *d_bits, void *stream) {
     if (!batch_args_ok(re, batch_of(device, d_bytes, d_off, nitems, trim), {d_bits})) return fail(RRX_ERR_ARG, "null argument");
+    bool on_nfa = false;
+    int rc = contains_on_nfa(re, device, static_cast<const uint8_t *>(d_bytes), d_off, nitems, trim, d_bits, stream, &on_nfa);
+    if (rc || on_nfa) return rc;
     const DeviceTables *t;
-    int rc = re->contains_tables(device, &t);
+    rc = re->contains_tables(device, &t);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(device));
     if (!nitems) return RRX_OK;
@@ -183,8 +200,11 @@ int rrx_contains_extents(const rrx_regex *re, int device, const void *d_bytes, c
 }
 int rrx_contains_items(const rrx_regex *re, const rrx_items *it, uint32_t *d_bits, void *stream) {
     if (!it || !batch_args_ok(re, batch_of(it), {d_bits})) return fail(RRX_ERR_ARG, "null argument");
+    bool on_nfa = false;
+    int rc = contains_on_nfa(re, it->device, it->d_bytes, it->d_off, it->nitems, it->trim, d_bits, stream, &on_nfa);
+    if (rc || on_nfa) return rc;
     const DeviceTables *t;
-    int rc = re->contains_tables(it->device, &t);
+    rc = re->contains_tables(it->device, &t);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(it->device));
     if (!it->nitems) return RRX_OK;

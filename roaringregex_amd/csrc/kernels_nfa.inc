@@ -223,6 +223,91 @@ struct LineNfaEngine : NfaCore<W> {
     }
 };
 
+// ---- "which lines contain a match" on the line engine (rrx_contains_corpus under RRX_OPT_CONTAINS_NFA).  The program is the
+// lane program with the contains B rows (pack.cpp: contains_b_rows): position 0 is in EVERY row, so the 1 that the shift injects
+// survives every byte - a match may start anywhere -, and the rows of NUL and of bytes >= 0x80 are exactly {position 0}: such a
+// byte ends every attempt under way and starts the next one.  The step is LineNfaEngine's; behind it one register, `found`,
+// gathers S & FIN (one v_and_or_b32 per word), and under the wave-uniform '\n' branch the verdict is found != 0, after which the
+// '\n' lanes clear it.  A lane that starts inside somebody else's line steps from the empty set and matches on from there: its
+// first result is dropped by ResultsT, and its '\n' clears `found`.
+// Two builds per width: RULES = false has self loops and carry groups compiled in (the one-pass kernels' policy), RULES = true
+// has the exception rows and takes the carry groups under the run-time flag.
+template <int W, bool RULES>
+struct ContainsLineNfaEngine : LineNfaEngine<W, true, RULES, !RULES> {
+    using Line = LineNfaEngine<W, true, RULES, !RULES>;
+    static constexpr bool kStaged = Line::kStaged;
+    static constexpr bool kLdsAtZero = true;
+    static constexpr bool kEightWaves = W == 1 && !RULES;      // 58 registers; at W = 2 `found` is the 65th: the cap of two workgroups
+                                                               //   per CU spilt 12 bytes per lane (profiles/contains_nfa_isa_check.txt)
+    static constexpr int kRoundBytes = Line::kRoundBytes;
+    struct State : NfaCore<W>::State { uint32_t found; };
+    __device__ __forceinline__ State fresh() const {
+        State st;
+#pragma unroll
+        for (int i = 0; i < W; i++) st.s[i] = i == 0 ? 1u : 0u;
+        st.found = 0;
+        return st;
+    }
+    __device__ __forceinline__ State skipping() const {
+        State st;
+#pragma unroll
+        for (int i = 0; i < W; i++) st.s[i] = 0;
+        st.found = 0;
+        return st;
+    }
+    __device__ __forceinline__ void advance_found(State &st, const uint32_t *bc) const {
+        this->advance_row(st, bc);
+#pragma unroll
+        for (int i = 0; i < W; i++) st.found = (st.s[i] & this->m.fin[i]) | st.found;
+    }
+    template <int K>
+    __device__ __forceinline__ void verdict(State &st, uint32_t w, uint32_t &bits) const {
+        uint64_t nlmask;
+        const uint32_t ten = '\n';
+#define RRX_NFA_NL(SEL) asm("v_cmp_eq_u32_sdwa %0, %1, %2 src0_sel:" SEL " src1_sel:DWORD" : "=s"(nlmask) : "v"(w), "v"(ten))
+        if constexpr (K == 0) RRX_NFA_NL("BYTE_0");
+        if constexpr (K == 1) RRX_NFA_NL("BYTE_1");
+        if constexpr (K == 2) RRX_NFA_NL("BYTE_2");
+        if constexpr (K == 3) RRX_NFA_NL("BYTE_3");
+#undef RRX_NFA_NL
+        if (nlmask) {                                             // wave-uniform: some lane ends a line on this byte
+            uint32_t tmp;
+            // bits = (bits << 1) | (found != 0) on the lanes of nlmask - the verdict enters as the carry of bits + bits -, and
+            // those lanes start their next line with found = 0
+            asm volatile("v_cmp_ne_u32_e32 vcc, 0, %1\n\t"
+                         "v_addc_co_u32_e32 %2, vcc, %0, %0, vcc\n\t"
+                         "v_cndmask_b32_e64 %0, %0, %2, %3\n\t"
+                         "v_cndmask_b32_e64 %1, %1, 0, %3"
+                         : "+v"(bits), "+v"(st.found), "=&v"(tmp) : "s"(nlmask) : "vcc");
+        }
+    }
+    __device__ __forceinline__ void consume_word(State &st, uint32_t w, uint32_t &bits) const {
+        using Row = typename Line::Row;
+        if constexpr (W <= 4 && !RULES) {
+            const Row r0 = this->template row_of<0>(w), r1 = this->template row_of<1>(w), r2 = this->template row_of<2>(w), r3 = this->template row_of<3>(w);
+            verdict<0>(st, w, bits); advance_found(st, r0.b);
+            verdict<1>(st, w, bits); advance_found(st, r1.b);
+            verdict<2>(st, w, bits); advance_found(st, r2.b);
+            verdict<3>(st, w, bits); advance_found(st, r3.b);
+        } else {                                                  // wide sets: one row in flight ahead of the step
+            Row r = this->template row_of<0>(w), n = this->template row_of<1>(w);
+            verdict<0>(st, w, bits); advance_found(st, r.b);
+            r = this->template row_of<2>(w);
+            verdict<1>(st, w, bits); advance_found(st, n.b);
+            n = this->template row_of<3>(w);
+            verdict<2>(st, w, bits); advance_found(st, r.b);
+            verdict<3>(st, w, bits); advance_found(st, n.b);
+        }
+    }
+    __device__ __forceinline__ void step(State &st, uint32_t c, uint32_t &nl, uint32_t &acc) const {
+        const bool isnl = c == '\n';
+        nl = isnl ? 1u : 0u;
+        acc = (isnl && st.found) ? 1u : 0u;
+        if (isnl) st.found = 0;
+        advance_found(st, this->B + c * W);
+    }
+};
+
 // ---- plain engines for the extents kernel ('\n' is an ordinary byte) --------------------------------
 template <int W>
 struct PlainNfaEngine : NfaCore<W> {
@@ -237,6 +322,54 @@ struct PlainNfaEngine : NfaCore<W> {
     }
     __device__ __forceinline__ void step(State &st, uint32_t c) const { this->advance(st, c); }
 };
+
+// ---- "which items contain a match" on the NFA (rrx_contains_extents / rrx_contains_items under RRX_OPT_CONTAINS_NFA): one lane per
+// item on the program with the contains B rows, the walk of contains_extents_kernel written out (item_lanes.hpp: aligned on the
+// offset, a 16-byte load only where all its bytes lie inside the item).  The step is NfaCore's with the CHAIN mask, then S |= init:
+// a match may start behind every byte, '\n' is an ordinary byte, and NUL and bytes >= 0x80 need no compare - their rows are
+// {position 0}, which the step never enters, so they leave exactly the initial set.  A lane leaves at its first S & FIN.  One
+// ballot per 64 consecutive items, two plain word stores by lane 0: no atomics, nothing to clear (contains_extents_kernel).
+template <int W>
+__global__ __launch_bounds__(kThreads) void contains_extents_nfa_kernel(NfaDevice prog, const uint8_t *__restrict__ bytes,
+                                                                         const uint64_t *__restrict__ off, size_t nitems, uint32_t trim,
+                                                                         uint32_t *__restrict__ bits) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    NfaCore<W> eng;
+    eng.load(prog, smem);
+    __syncthreads();
+    for_each_wave_pass(nitems, [&](size_t first, uint32_t lane) {
+        const size_t i = first + lane;
+        bool hit = false;
+        if (i < nitems) {
+            const auto [b, e] = item_span(off, i, trim);
+            typename NfaCore<W>::State st;
+#pragma unroll
+            for (int k = 0; k < W; k++) st.s[k] = eng.m.init[k];
+            hit = eng.accepting(st);
+            size_t p = b;
+            auto one = [&](uint32_t c) {
+                eng.advance(st, c);
+#pragma unroll
+                for (int k = 0; k < W; k++) st.s[k] |= eng.m.init[k];
+                hit = eng.accepting(st);
+            };
+            for (; p < e && (p & 15) && !hit; p++) one(bytes[p]);                  // up to 16-byte alignment
+            for (; p + 16 <= e && !hit; p += 16) {                                 // 16 bytes per load
+                const uint4 v = *reinterpret_cast<const uint4 *>(bytes + p);
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 16; k++)
+                    if (!hit) one((w[k >> 2] >> (8 * (k & 3))) & 0xffu);
+            }
+            for (; p < e && !hit; p++) one(bytes[p]);
+        }
+        const uint64_t verdicts = __builtin_amdgcn_ballot_w64(hit);
+        if (lane == 0) {
+            bits[first >> 5] = (uint32_t)verdicts;
+            if (first + 32 < nitems) bits[(first >> 5) + 1] = (uint32_t)(verdicts >> 32);
+        }
+    });
+}
 
 // ---- one long string on an NFA engine (regex.h:156-159 consumes it byte by byte; one lane doing the same manages a few
 // MB/s).  The string is cut into chunks and every chunk is stepped from EVERY position at once - lane = (chunk, start
@@ -564,6 +697,23 @@ int RRX_NFA_NAME(recheck_escaped_nfa)(const NfaDevice &p, const uint8_t *bytes, 
 int RRX_NFA_NAME(match_extents_nfa)(const NfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim, uint8_t *accept,
                                     void *stream) {
 #define CALL(WW) launch_extents<PlainNfaEngine<WW>, NfaDevice>(p, PlainNfaEngine<WW>::lds_bytes(p), bytes, off, nitems, trim, accept, stream)
+    RRX_NFA_DISPATCH(CALL)
+#undef CALL
+}
+// contains on the program with the contains B rows: two builds per width (exception rows / self loops and carry groups) ...
+int RRX_NFA_NAME(contains_stripes_nfa)(const NfaDevice &p, const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base,
+                                       size_t nstripes, uint32_t *bits, void *stream) {
+#define GO(WW, R) launch_stripes<ContainsLineNfaEngine<WW, R>, NfaDevice>(p, ContainsLineNfaEngine<WW, R>::lds_bytes(p), bytes, nbytes, stripe, stripe_base, nstripes, bits, stream)
+#define CALL(WW) (p.any_exc ? GO(WW, true) : GO(WW, false))
+    RRX_NFA_DISPATCH(CALL)
+#undef CALL
+#undef GO
+}
+// ... and a lane per item: every workgroup copies the program into LDS (up to 48 KiB), so the grid is bounded and strides
+int RRX_NFA_NAME(contains_extents_nfa)(const NfaDevice &p, const uint8_t *bytes, const uint64_t *off, size_t nitems, uint32_t trim, uint32_t *bits,
+                                       void *stream) {
+    if (!nitems) return 0;
+#define CALL(WW) launch_item_lanes<contains_extents_nfa_kernel<WW>>(NfaCore<WW>::lds_bytes(p), nitems, kItemLanesMaxBlocks, stream, p, bytes, off, nitems, trim, bits)
     RRX_NFA_DISPATCH(CALL)
 #undef CALL
 }

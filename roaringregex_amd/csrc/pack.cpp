@@ -197,6 +197,15 @@ void pack_lane_nfa(const NfaProgram &nfa, Image &img, dev::NfaDevice &d) {
     }
 }
 
+void contains_b_rows(NfaProgram &nfa) {
+    const uint32_t W = nfa.W;
+    for (uint32_t c = 0; c < 256; c++) {
+        uint32_t *row = &nfa.B[(size_t)c * W];
+        if (c == 0 || c >= 0x80) for (uint32_t w = 0; w < W; w++) row[w] = 0;
+        row[0] |= 1u;
+    }
+}
+
 bool pack_group_nfa(const NfaProgram &nfa, const Trimmed &trimmed, Image &img, dev::GroupNfaDevice &d) {
     // group-cooperative form: G lanes x K words (device.hpp: group_geometry), a B row per byte CLASS
     const uint32_t W = nfa.W, N = nfa.nbits;

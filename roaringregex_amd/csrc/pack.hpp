@@ -49,6 +49,11 @@ bool dfa2_byte_pairs_fit(const Dfa2Program &dfa2);
 // The items table: the plain table, wide, kItemColumns columns (129 = END OF ITEM); false where row offsets pass 16 bits.
 bool pack_items(const DfaProgram &dfa, Image &img, dev::LineDfaDevice &d);
 void pack_lane_nfa(const NfaProgram &nfa, Image &img, dev::NfaDevice &d);
+// The B rows of "contains a match" on a lane program (init = {position 0}, which no row of the lowering holds): position 0 goes
+// into every row - it stays live on every byte, a match may start anywhere - and the rows of 0x00 and 0x80 ... 0xFF become exactly
+// {position 0}: ordinary text that no pattern takes.  The '\n' row is the pattern's own plus position 0 (the items form steps it;
+// the corpus kernel overwrites it in LDS).  Everything else of the program stays: the step is linear in the set.
+void contains_b_rows(NfaProgram &nfa);
 bool pack_group_nfa(const NfaProgram &nfa, const Trimmed &trimmed, Image &img, dev::GroupNfaDevice &d);     // false: no group_geometry
 // WL: wave_words_per_lane, or for the sparse form (rows per byte class too) sparse_rows
 void pack_wave_nfa(const NfaProgram &nfa, const Trimmed &trimmed, uint32_t WL, bool sparse, Image &img, dev::WaveNfaDevice &d);

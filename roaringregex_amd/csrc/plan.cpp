@@ -119,6 +119,13 @@ bool plan_search_longest(const Reduced &red, bool accepts_empty, SearchLongestPl
     return true;
 }
 
+bool plan_contains_nfa(const Programs &p, NfaProgram &out) {
+    if (p.has_nfa) out = p.nfa;
+    else if (!lower_nfa(reduce(p.trimmed), dev::kMaxNfaWords * 32, out, /*allow_carry=*/true, /*gaps=*/true)) return false;
+    contains_b_rows(out);
+    return true;
+}
+
 bool lower_multi_member(const std::string &pattern, DfaProgram &out) {
     return search_fwd_dfa(reduce(trim(build_reference_automaton(pattern))), kMaxSubsetStates, out);
 }

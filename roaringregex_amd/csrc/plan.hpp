@@ -95,6 +95,11 @@ struct SearchLongestPlan {
 // false: one of the two tables does not determinise within kMaxSubsetStates (both stay empty).
 bool plan_search_longest(const Reduced &red, bool accepts_empty, SearchLongestPlan &out);
 
+// The program of contains on the NFA lane engine (RRX_OPT_CONTAINS_NFA; RRX_PROGRAM_CONTAINS_NFA dumps it): the lane program of the
+// pattern - p.nfa where the regex has one, else lowered here with the lane engine's limits, whatever engine the regex was compiled
+// for - with the contains B rows (pack.hpp: contains_b_rows).  false: no lane program (more than kMaxNfaWords * 32 positions).
+bool plan_contains_nfa(const Programs &p, NfaProgram &out);
+
 // A pattern set (rrx_multi): its members' forward search tables in set order, cut into GROUPS of members that share one product table.
 constexpr uint32_t kMultiMaxPatterns = 32;
 struct MultiGroup {

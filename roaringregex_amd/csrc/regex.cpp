@@ -156,6 +156,35 @@ int rrx_regex::contains_tables(int device, const DeviceTables **out) const {
     return rc ? rc : upload_once(contains_set.on_device, device, false, [&](Image &img, DeviceTables &t) { contains_set.lt.pack({}, {}, img, t); return true; }, out);
 }
 
+// ---- contains on the NFA lane engine (RRX_OPT_CONTAINS_NFA)
+bool rrx_regex::build_contains_nfa() const {
+    if (contains_nfa_state == 0) contains_nfa_state = plan_contains_nfa(*this, contains_nfa) ? 1 : -1;
+    return contains_nfa_state == 1;
+}
+int rrx_regex::contains_route(bool *nfa) const {
+    const int mode = opt_contains_nfa.load();
+    *nfa = false;
+    if (mode == 0) return build_contains();
+    if (mode == 1 && build_contains() == RRX_OK) return RRX_OK;
+    if (!build_contains_nfa()) {
+        // (option 2 asks for no table; whether there is one is still the first half of the answer)
+        const std::string table = build_contains() == RRX_OK ? std::string("the contains table is set aside (RRX_OPT_CONTAINS_NFA 2)") : last_error();
+        return fail(RRX_ERR_UNSUPPORTED, table + "; and no lane program for contains on the NFA lane engine: the pattern has more than 512 positions after reduction");
+    }
+    *nfa = true;
+    return RRX_OK;
+}
+int rrx_regex::contains_nfa_tables(int device, bool *nfa, const dev::NfaDevice **out, bool *fill) const {
+    *nfa = false; *out = nullptr; *fill = false;
+    if (!opt_contains_nfa.load()) return RRX_OK;             // (the table route reports its own errors: contains_tables)
+    std::lock_guard<std::mutex> lock(mu);
+    const int rc = contains_route(nfa);
+    if (rc || !*nfa) return rc;
+    if (contains_nfa.accepts_empty) { *fill = true; return RRX_OK; }
+    if (!trimmed.n) return RRX_OK;                           // the empty language
+    return upload_once(contains_nfa_on_device, device, false, [&](Image &img, dev::NfaDevice &t) { pack_lane_nfa(contains_nfa, img, t); return true; }, out);
+}
+
 // ---- the order of the stride-2 table
 bool rrx_regex::t2_order_applies() const {                      // single-copy tables only: interleaved copies already keep lanes apart
     return match.has_dfa2 && dfa2_table_bytes(match.dfa2) * 2 > dev::kDfa2TableBudget;
@@ -353,6 +382,11 @@ int rrx_set_option(rrx_regex *re, int option, int64_t value) {
     }
     if (option == RRX_OPT_SAMPLED_TABLE) { re->opt_sampled_table.store(value ? 1 : 0); return RRX_OK; }
     if (option == RRX_OPT_ITEMS_STRIDE2) { re->items_stride2.store(value ? 1 : 0); return RRX_OK; }
+    if (option == RRX_OPT_CONTAINS_NFA) {
+        if (value < 0 || value > 2) return fail(RRX_ERR_ARG, "contains on the NFA lane engine: 0 (never), 1 (where there is no contains table) or 2 (always)");
+        re->opt_contains_nfa.store((int)value);
+        return RRX_OK;
+    }
     if (option == RRX_OPT_SEARCH_ANCHORED) {
         std::lock_guard<std::mutex> lock(re->mu);
         if (re->search_state != 0) return fail(RRX_ERR_ARG, "the search tables of this regex are built already");
@@ -372,7 +406,9 @@ int rrx_accepts_empty(const rrx_regex *re) { return re->accepts_empty(); }
 const char *rrx_contains_engine_name(const rrx_regex *re) {
     if (!re) { (void)fail(RRX_ERR_ARG, "null argument"); return nullptr; }
     std::lock_guard<std::mutex> lock(re->mu);
-    return re->build_contains() ? nullptr : re->contains_set.lt.name();
+    bool nfa = false;
+    if (re->contains_route(&nfa)) return nullptr;
+    return nfa ? "nfa-shift-and" : re->contains_set.lt.name();
 }
 uint32_t rrx_contains_states(const rrx_regex *re) {
     if (!re) { (void)fail(RRX_ERR_ARG, "null argument"); return 0; }
@@ -408,6 +444,9 @@ size_t rrx_program_words(const rrx_regex *re, int kind, uint32_t *out, size_t ca
         if (re->build_contains()) return 0;
         if (kind == RRX_PROGRAM_CONTAINS_DFA) append_words(w, re->contains_set.lt.dfa);
         else if (re->contains_set.lt.has_dfa2) append_words(w, re->contains_set.lt.dfa2);
+    } else if (kind == RRX_PROGRAM_CONTAINS_NFA) {
+        std::lock_guard<std::mutex> lock(re->mu);
+        if (re->build_contains_nfa()) append_words(w, re->contains_nfa, /*csr=*/false);
     } else if (kind == RRX_PROGRAM_CONTAINS_DFA2_ITEMS || (kind == RRX_PROGRAM_DFA2_ITEMS && re->match.has_dfa2)) {
         TableSet &set = kind == RRX_PROGRAM_DFA2_ITEMS ? re->match_set : re->contains_set;
         std::lock_guard<std::mutex> lock(re->mu);
