@@ -343,7 +343,7 @@ def test_every_alignment_of_item_start_on_the_lane_kernels():
     Expected: the oracle's whole-string acceptance (match) and its brute-force search (contains)."""
     from contains_cases import brute_force
     from pyoracle import OracleRegex
-    from test_search_items_lowering import plain_table_bytes
+    from table_edge_cases import plain_table_bytes
     rng = random.Random(31)
     small = ("ab+c", "abcz", 3, lambda n: b"a" + b"b" * (n - 2) + b"c")
     large = (MATCH_GLOBAL, "abc", 14, lambda n: b"b" * (n - 14) + b"a" + b"b" * 12 + b"c")

@@ -358,6 +358,8 @@ def test_host_pipeline_is_clean_under_asan_and_ubsan(tmp_path):
     rng = random.Random(2024)
     pats = [k["pattern"] for k in KAT["kat"]] + [b["pattern"] for b in KAT["big_states"]]
     pats += [EMAIL, U2, "a{1,300}", "(a|b)*a(a|b){12}", "(a|b)*a(a|b){40}", K1000_CONTAINS]
+    from table_edge_cases import CASES                    # the automata on a table form's limit, and the first ones beyond it
+    pats += sorted({c.pattern for c in CASES if c.side in ("at", "past")})
     pats += ["(", ")", "a)", "(a", "[", "[a", "a{", "a{2", "a{2,", "a{,}", "a{3,2}", "*", "+a", "a||b", "\\", "a\\", "[]", "[^]", "a{0}", "a{0,0}", "()", "(|)", ""]
     pats += [random_pattern(rng) for _ in range(150)]
     pats = [p for p in pats if "\n" not in p]

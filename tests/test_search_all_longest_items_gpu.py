@@ -14,7 +14,7 @@ import roaringregex_amd as rr
 from contains_cases import EXPLODING
 from patterns import EMAIL, K1000_CONTAINS, U2
 from test_contains_items_lowering import NEWLINE_PATTERNS, short_items
-from test_search_items_lowering import plain_table_bytes
+from table_edge_cases import plain_table_bytes
 from test_search_longest_items_lowering import GLOBAL_AUTO, global_auto_items
 from test_search_all_longest_items_lowering import SearchAllLongestReplay, finditer_all, pack, reference_all, want_for
 

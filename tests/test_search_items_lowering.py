@@ -11,6 +11,7 @@ import numpy as np
 import roaringregex_amd as rr
 from contains_cases import EXPLODING, short_line_patterns
 from program_replay import DfaReplay
+from table_edge_cases import plain_table_bytes
 from test_contains_items_lowering import MAX_ITEM, NEWLINE_PATTERNS, as_oracle_sees, oracle_for, short_items
 
 NITEMS = 200
@@ -76,12 +77,6 @@ class SearchItemsReplay:
 
     def search_items(self, items):
         return np.array([self.search(it) for it in items], dtype=np.int32).reshape(len(items), 2)
-
-
-def plain_table_bytes(words):
-    """LDS bytes of a plain table (PlainDfaEngine): next, the byte -> class map, the accept flags."""
-    nstates, ncls = int(words[0]), int(words[1])
-    return nstates * ncls * 2 + 256 + nstates
 
 
 def check(p, items, want, r=None):

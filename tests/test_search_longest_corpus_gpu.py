@@ -17,7 +17,7 @@ import roaringregex_amd as rr
 from contains_cases import EXPLODING, split_lines
 from patterns import EMAIL, K1000_CONTAINS, U2
 from search_longest_corpus_cases import GEOMETRY_PATTERNS, geometry_corpus, geometry_wants, reference_texts
-from test_search_items_lowering import plain_table_bytes
+from table_edge_cases import plain_table_bytes
 from test_search_longest_items_lowering import GLOBAL_AUTO, global_auto_items, want_for
 
 torch = pytest.importorskip("torch")

@@ -12,7 +12,7 @@ import roaringregex_amd as rr
 from contains_cases import EXPLODING
 from patterns import EMAIL, K1000_CONTAINS, U2
 from test_contains_items_lowering import NEWLINE_PATTERNS, short_items
-from test_search_items_lowering import plain_table_bytes
+from table_edge_cases import plain_table_bytes
 from test_search_longest_items_lowering import GLOBAL_AUTO, GREEDY_RE, START_CASES, SearchLongestReplay, global_auto_items, reference_set, want_for
 
 torch = pytest.importorskip("torch")
