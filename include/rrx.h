@@ -554,6 +554,54 @@ int rrx_split_longest_extents(const rrx_regex *re, int device, const void *d_byt
 int rrx_split_longest_items(const rrx_regex *re, const rrx_items *items, uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap,
                             void *d_out, size_t cap, size_t *npieces, size_t *total, void *stream);
 
+/* THE ROWS A RESULT BITMAP SELECTS, WRITTEN AS A NEW COLUMN: SELECT col WHERE col RLIKE p, and what `grep` prints.  From a bitmap in
+ * the result layout - bit i & 31 of word i >> 5 = row i: what rrx_match_corpus, rrx_contains_* and rrx_multi_plane write - to the
+ * surviving rows' numbers, their offsets and their bytes, without a host step.
+ * SELECTION RULE: with invert 0 a row is selected iff its bit is 1, with invert 1 iff its bit is 0 (grep -v).  The bits of the last
+ * word beyond nbits are never selected, whatever they hold and whatever invert is.
+ * rrx_bitmap_rank: d_rank[w] = the number of selected bits in the words in front of word w, for w = 0 .. nwords = ceil(nbits / 32);
+ * d_rank[nwords] is the number of selected rows.  Plain numbers.  d_rank holds rank_words u64 words, rrx_bitmap_rank_words(nbits)
+ * (host only) at least: the nwords + 1 entries and behind them what the scan needs (its chunk sums and the popcount words it sums);
+ * a shorter rank_words is RRX_ERR_ARG.  nbits == 0 writes d_rank[0] = 0.  Plain multi-launch scans: no workgroup waits for another.
+ * rrx_filter_sizes (an offsets column: item i = d_bytes[d_off[i] .. d_off[i+1] - trim)): for the k-th selected item i - k its rank -
+ * d_row[k] = i, d_piece_src[k] = d_off[i], d_piece_len[k] = the item's length after trim (0 where trim exceeds it), saturated at
+ * 0xFFFFFFFF.  Exactly the slots 0 .. nsel - 1 and nothing else; nitems == 0 writes nothing.
+ * rrx_filter_corpus_sizes: the same triples for the LINES of a corpus, from the text and the corpus' own stripe index - no offsets
+ * array is built or used.  A line is what rrx_search_longest_corpus calls a line (a final fragment without '\n' is one);
+ * d_piece_src[k] = the absolute offset of the line's first byte, d_piece_len[k] = its length without the '\n', plus 1 when
+ * keep_newline is set and the line has its '\n' in the text.  With keep_newline = 1 the filled output is again '\n'-delimited text
+ * that rrx_corpus_create accepts (grep p1 | grep p2 without a host step); with keep_newline = 0 it is a column with trim 0.  A lane
+ * of the kernel owns the lines that start in one stripe; one without a selected line reads no text at all.
+ * THE BYTES: the caller prefixes d_piece_len into d_piece_off (nsel + 1 entries) and calls rrx_pieces_fill(device, d_bytes,
+ * d_piece_src, d_piece_off, nsel, d_out, stream): d_piece_off is the new column's offsets array.
+ * These entries are FULLY asynchronous on `stream` and can be captured into a graph: no read-back, no event, no scratch beyond the
+ * caller's arrays.  d_rank must be the rank of the same d_bits, nbits (nitems; the corpus' line count) and invert: the slots come
+ * from it.  RRX_ERR_ARG for null arguments, checked before any device call.
+ * THE ONE-CALL FORMS apply the pattern's CONTAINS bitmap (rrx_contains_extents / _items / _corpus; the _items form keeps the indexed
+ * batch's stripe-wise kernels): synchronous; everything temporary lives in device memory the call allocates and frees.  The cap
+ * protocol of rrx_extract_all_longest_extents: *nrows and *total (the bytes of the new column) are exact either way; d_row (rows_cap
+ * entries) and d_out_off (rows_cap + 1 entries, entry 0 = 0) are written iff *nrows <= rows_cap; d_out holds `cap` bytes and is
+ * written iff additionally *total <= cap - otherwise not a byte of it: call again with the exact sizes.  With zero rows in (nitems
+ * == 0, a corpus of zero lines) or zero rows selected: d_out_off[0] = 0 whatever rows_cap is, both counts 0, nothing else written.
+ * A pattern that accepts the empty string selects every row; the empty language none - all of them with invert.  RRX_ERR_ARG for
+ * null arguments, checked before any device call (d_row may be null when rows_cap == 0, d_out when cap == 0); RRX_ERR_UNSUPPORTED
+ * exactly where the corresponding rrx_contains_* entry returns it (so RRX_OPT_CONTAINS_NFA applies), for an empty input too, and
+ * for a selected row of 2^30 bytes or more (the scan carries 30 bits per length: use the contains entry and the generic entries
+ * with a prefix of the caller's own).                                                                                              */
+size_t rrx_bitmap_rank_words(size_t nbits);
+int rrx_bitmap_rank(int device, const uint32_t *d_bits, size_t nbits, int invert, uint64_t *d_rank, size_t rank_words, void *stream);
+int rrx_filter_sizes(int device, const uint64_t *d_off, size_t nitems, uint32_t trim, const uint32_t *d_bits, int invert, const uint64_t *d_rank,
+                     uint64_t *d_row, uint32_t *d_piece_len, uint64_t *d_piece_src, void *stream);
+int rrx_filter_corpus_sizes(const rrx_corpus *c, const uint32_t *d_bits, int invert, int keep_newline, const uint64_t *d_rank, uint64_t *d_row,
+                            uint32_t *d_piece_len, uint64_t *d_piece_src, void *stream);
+int rrx_filter_contains_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim, int invert,
+                                uint64_t *d_row, uint64_t *d_out_off, size_t rows_cap, void *d_out, size_t cap, size_t *nrows, size_t *total,
+                                void *stream);
+int rrx_filter_contains_items(const rrx_regex *re, const rrx_items *items, int invert, uint64_t *d_row, uint64_t *d_out_off, size_t rows_cap,
+                              void *d_out, size_t cap, size_t *nrows, size_t *total, void *stream);
+int rrx_filter_contains_corpus(const rrx_regex *re, const rrx_corpus *c, int invert, int keep_newline, uint64_t *d_row, uint64_t *d_out_off,
+                               size_t rows_cap, void *d_out, size_t cap, size_t *nrows, size_t *total, void *stream);
+
 /* regexp_extract with a CAPTURE GROUP on a string column: where, inside the leftmost-longest match of every item, does one
  * TOP-LEVEL group of the pattern sit.  The pattern is a concatenation P = A (B) C and the wanted group is (B); A and C may be absent,
  * parentheses inside A, B and C are plain grouping.  regexp_extract(col, 'https?://([^/]+)/.*', 1) is group 1 of that pattern.

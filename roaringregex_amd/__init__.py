@@ -59,6 +59,8 @@ ABI_SYMBOLS = (
     "rrx_replace_matches_sizes", "rrx_replace_matches_fill", "rrx_replace_all_longest_extents", "rrx_replace_all_longest_items",
     "rrx_pieces_sizes", "rrx_pieces_fill", "rrx_extract_all_longest_extents", "rrx_extract_all_longest_items", "rrx_split_longest_extents",
     "rrx_split_longest_items",
+    "rrx_bitmap_rank_words", "rrx_bitmap_rank", "rrx_filter_sizes", "rrx_filter_corpus_sizes",
+    "rrx_filter_contains_extents", "rrx_filter_contains_items", "rrx_filter_contains_corpus",
     "rrx_group_compile", "rrx_group_compile_ex", "rrx_group_free", "rrx_group_regex", "rrx_group_part", "rrx_group_program_words",
     "rrx_group_spans_extents", "rrx_group_spans_items", "rrx_extract_group_longest_extents", "rrx_extract_group_longest_items",
     "rrx_group_spans_list_extents", "rrx_group_spans_list_items",
@@ -172,6 +174,13 @@ def _load():
         "rrx_extract_all_longest_items": (i32, [vp, vp, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
         "rrx_split_longest_extents": (i32, [vp, i32, vp, vp, sz, u32, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
         "rrx_split_longest_items": (i32, [vp, vp, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
+        "rrx_bitmap_rank_words": (sz, [sz]),
+        "rrx_bitmap_rank": (i32, [i32, vp, sz, i32, vp, sz, vp]),
+        "rrx_filter_sizes": (i32, [i32, vp, sz, u32, vp, i32, vp, vp, vp, vp, vp]),
+        "rrx_filter_corpus_sizes": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "rrx_filter_contains_extents": (i32, [vp, i32, vp, vp, sz, u32, i32, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
+        "rrx_filter_contains_items": (i32, [vp, vp, i32, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
+        "rrx_filter_contains_corpus": (i32, [vp, vp, i32, i32, vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
         "rrx_group_compile": (i32, [C.c_char_p, i32, C.POINTER(vp)]),
         "rrx_group_compile_ex": (i32, [C.c_char_p, i32, i32, C.POINTER(vp)]),
         "rrx_group_free": (None, [vp]),
@@ -418,6 +427,49 @@ def pieces_of_matches(data, offsets, first, start, end, gaps=False, trim=0, stre
     return out, piece_off, list_off
 
 
+def _filter_rank(bits, n, invert, dev, s):
+    """rrx_bitmap_rank of the first n bits of a result bitmap -> (the rank array, the number of selected rows).  Waits for the one word."""
+    import torch
+    nw = (n + 31) // 32
+    assert bits.is_cuda and bits.dtype in (torch.int32, torch.uint32) and bits.is_contiguous() and bits.numel() >= nw
+    words = _L.rrx_bitmap_rank_words(n)
+    rank = torch.empty(words, dtype=torch.int64, device=bits.device)
+    _check(_L.rrx_bitmap_rank(dev, _ptr(bits), n, int(bool(invert)), _ptr(rank), words, s))
+    return rank, int(rank[nw].item())
+
+
+def _filter_column(data, nsel, sizes, dev, s):
+    """The selected rows' triples (sizes(rows, length, src): one of the two generic entries), a torch.cumsum and rrx_pieces_fill ->
+    (rows int64[nsel], out_off int64[nsel + 1], out uint8).  Waits for the output's size."""
+    import torch
+    rows = torch.empty(nsel, dtype=torch.int64, device=data.device)
+    out_off = torch.zeros(nsel + 1, dtype=torch.int64, device=data.device)
+    if not nsel:
+        return rows, out_off, torch.empty(0, dtype=torch.uint8, device=data.device)
+    length = torch.empty(nsel, dtype=torch.int32, device=data.device)
+    src = torch.empty(nsel, dtype=torch.int64, device=data.device)
+    _check(sizes(_ptr(rows), _ptr(length), _ptr(src)))
+    torch.cumsum(length.to(torch.int64) & 0xFFFFFFFF, dim=0, out=out_off[1:])
+    out = torch.empty(int(out_off[-1].item()), dtype=torch.uint8, device=data.device)
+    _check(_L.rrx_pieces_fill(dev, _ptr(data), _ptr(src), _ptr(out_off), nsel, _ptr(out), s))
+    return rows, out_off, out
+
+
+def filter_rows(data, offsets, bits, invert=False, trim=0, stream=None):
+    """The items a result bitmap selects, as a new column written on the device (rrx_bitmap_rank, rrx_filter_sizes, a torch.cumsum,
+    rrx_pieces_fill): item i = data[offsets[i] : offsets[i + 1] - trim] is selected iff bit i & 31 of bits[i >> 5] is 1 (invert: 0);
+    `bits` is what contains_extents_bits, contains_items_bits and RMulti.plane return, or any bitmap in that layout - the bits of
+    its last word beyond the last item are ignored.  -> (rows int64[nsel], out_off int64[nsel + 1], out uint8): rows[k] is the
+    number of the k-th selected item and out[out_off[k] : out_off[k + 1]] its bytes; the separators are not copied.  Waits for the
+    number of rows and for the output's size."""
+    n, d = _batch(data, offsets)[:2]
+    with _on(d, stream):
+        s = _stream_ptr(stream)
+        rank, nsel = _filter_rank(bits, n, invert, d, s)
+        return _filter_column(data, nsel, lambda rows, length, src: _L.rrx_filter_sizes(d, _ptr(offsets), n, trim, _ptr(bits), int(bool(invert)), _ptr(rank), rows,
+                                                                                        length, src, s), d, s)
+
+
 class Match:
     """regex.h:100-105: [start, end) into the caller's buffer; here as offsets plus the buffer."""
 
@@ -504,6 +556,20 @@ class Corpus:
         span = C.c_uint32(0)
         _L.rrx_corpus_one_launch(self._h, C.byref(span))
         return span.value
+
+    def filter_lines(self, bits, invert=False, keep_newline=True, stream=None):
+        """The lines a result bitmap selects - what `grep` prints - as a new column written on the device (rrx_bitmap_rank,
+        rrx_filter_corpus_sizes, a torch.cumsum, rrx_pieces_fill): line i is selected iff bit i & 31 of bits[i >> 5] is 1 (invert: 0,
+        grep -v); `bits` is what match_corpus_bits and contains_corpus_bits return, or any bitmap in that layout.  -> (rows
+        int64[nsel], out_off int64[nsel + 1], out uint8): rows[k] is the number of the k-th selected line and out[out_off[k] :
+        out_off[k + 1]] its bytes - with its '\n' where keep_newline is set and the text has it: `out` is then a corpus again.  No
+        offsets array of the corpus is built.  Waits for the number of rows and for the output's size."""
+        n = self.num_lines
+        with _on(self.device, stream):
+            s = _stream_ptr(stream)
+            rank, nsel = _filter_rank(bits, n, invert, self.device, s)
+            return _filter_column(self.data, nsel, lambda rows, length, src: _L.rrx_filter_corpus_sizes(self._h, _ptr(bits), int(bool(invert)), int(bool(keep_newline)),
+                                                                                                        _ptr(rank), rows, length, src, s), self.device, s)
 
 
 class Items:
@@ -1001,6 +1067,51 @@ class RRegex:
             s = _stream_ptr(stream)
             return self._pieces_one_call(items.data.device, items.num_items, items.data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
                                          _L.rrx_split_longest_items(self._h, items._h, lo, po, pc, out, cp, npc, tot, s))
+
+    def _filter_one_call(self, dev, n, nbytes, cap, rows_cap, call):
+        """A one-call filter entry, repeated with the exact sizes if a cap was too small -> (rows int64[nrows], out_off int64[nrows + 1], out uint8)."""
+        import torch
+        cap = int(cap) if cap is not None else nbytes
+        rows_cap = int(rows_cap) if rows_cap is not None else n
+        while True:
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            rows = torch.empty(rows_cap, dtype=torch.int64, device=dev)
+            out_off = torch.empty(rows_cap + 1, dtype=torch.int64, device=dev)
+            nrows, total = C.c_size_t(0), C.c_size_t(0)
+            _check(call(_ptr(rows), _ptr(out_off), rows_cap, _ptr(out), cap, C.byref(nrows), C.byref(total)))
+            if nrows.value <= rows_cap and total.value <= cap:
+                break
+            cap, rows_cap = max(cap, total.value), max(rows_cap, nrows.value)
+        return rows[:nrows.value], out_off[:nrows.value + 1], out[:total.value]
+
+    def filter_contains_extents(self, data, offsets, trim=0, invert=False, cap=None, rows_cap=None, stream=None):
+        """SELECT col WHERE col RLIKE p on a string column (rrx_filter_contains_extents): the items data[offsets[i] : offsets[i+1] -
+        trim] that CONTAIN a match (invert: that do not) as a new column -> (rows int64[nrows], out_off int64[nrows + 1], out uint8):
+        rows[k] is the number of the k-th surviving item, out[out_off[k] : out_off[k + 1]] its bytes; the separators are not copied.
+        cap / rows_cap: bytes and rows to provide for at first (default: the size of `data`, every item); the call is repeated with
+        the exact sizes if the column is larger."""
+        n, d, b, o = _batch(data, offsets)
+        with _on(d, stream):
+            s = _stream_ptr(stream)
+            return self._filter_one_call(data.device, n, data.numel(), cap, rows_cap, lambda rows, oo, rc, out, cp, nr, tot:
+                                         _L.rrx_filter_contains_extents(self._h, d, b, o, n, trim, int(bool(invert)), rows, oo, rc, out, cp, nr, tot, s))
+
+    def filter_contains_items(self, items, invert=False, cap=None, rows_cap=None, stream=None):
+        """The same for an indexed batch (rrx_filter_contains_items: contains runs stripe-wise where the batch admits it)."""
+        with _on(items.device, stream):
+            s = _stream_ptr(stream)
+            return self._filter_one_call(items.data.device, items.num_items, items.data.numel(), cap, rows_cap, lambda rows, oo, rc, out, cp, nr, tot:
+                                         _L.rrx_filter_contains_items(self._h, items._h, int(bool(invert)), rows, oo, rc, out, cp, nr, tot, s))
+
+    def filter_contains_corpus(self, corpus, invert=False, keep_newline=True, cap=None, rows_cap=None, stream=None):
+        """grep (invert: grep -v) on a '\n'-corpus (rrx_filter_contains_corpus): the lines that contain a match, in the shape
+        filter_contains_extents returns - with their '\n' where keep_newline is set and the text has it, so that `out` is a corpus
+        again and `grep p1 | grep p2` needs no host step."""
+        with _on(corpus.device, stream):
+            s = _stream_ptr(stream)
+            return self._filter_one_call(corpus.data.device, corpus.num_lines, corpus.num_bytes, cap, rows_cap, lambda rows, oo, rc, out, cp, nr, tot:
+                                         _L.rrx_filter_contains_corpus(self._h, corpus._h, int(bool(invert)), int(bool(keep_newline)), rows, oo, rc, out, cp, nr,
+                                                                       tot, s))
 
     def match_string(self, data, stream=None):
         """ONE device-resident string of any length (regex.h:156-159); '\n' is an ordinary character.  -> bool"""

@@ -451,6 +451,28 @@ int pieces_sizes(const uint64_t *off, size_t nitems, uint32_t trim, const uint64
                  bool gaps, uint64_t *list_off, uint32_t *piece_len, uint64_t *piece_src, uint32_t *too_long, void *stream);
 int pieces_fill(const uint8_t *bytes, const uint64_t *piece_src, const uint64_t *piece_off, size_t npieces, uint8_t *out, void *stream);
 
+// ---- the rows a result bitmap selects, as a new column: kernels_filter.hip
+// Any bitmap in the result layout (bit i & 31 of word i >> 5 = row i).  invert == false: a row is selected iff its bit is 1;
+// true: iff it is 0; the bits of the last word beyond nbits are never selected.
+// bitmap_rank: rank[w] = the selected rows in front of word w, w = 0 .. nwords (rank[nwords] = all of them), plain numbers; the array
+// holds bitmap_rank_words(nbits) u64 words - behind the nwords + 1 entries the chunk sums of scan_counts and the popcount words it
+// scans.  Launches only (and one 8-byte memset): capturable.  nbits == 0: rank[0] = 0.
+// filter_items (a lane per row, at most kFilterMaxBlocks workgroups of kThreads lanes, then the grid strides) and filter_corpus (a
+// lane per stripe of the corpus' index, nlines = its line count): for the k-th selected row - k its rank - row[k] = its number,
+// piece_src[k] = the absolute offset of its first byte (off[i]; the line's start), piece_len[k] = its length saturated at ~0u (the
+// item without `trim`, 0 where trim exceeds it; the line without its '\n', plus 1 with keep_newline where the line has one in the
+// text): exactly the slots 0 .. rank[nwords] - 1, plain stores, nothing to clear; what pieces_fill takes once piece_len is prefixed.
+// row may be null (not stored).  too_long as for pieces_sizes.  filter_corpus reads no byte at or beyond nbytes and, for a lane
+// without a selected line, no byte at all.
+constexpr size_t kFilterMaxBlocks = kReplaceMaxBlocks;
+size_t bitmap_rank_words(size_t nbits);
+int bitmap_rank(const uint32_t *bits, size_t nbits, bool invert, uint64_t *rank, void *stream);
+int filter_items(const uint64_t *off, size_t nitems, uint32_t trim, const uint32_t *bits, bool invert, const uint64_t *rank, uint64_t *row, uint32_t *piece_len,
+                 uint64_t *piece_src, uint32_t *too_long, void *stream);
+int filter_corpus(const uint8_t *bytes, size_t nbytes, uint32_t stripe, const uint64_t *stripe_base, size_t nstripes, size_t nlines, const uint32_t *bits,
+                  bool invert, bool keep_newline, const uint64_t *rank, uint64_t *row, uint32_t *piece_len, uint64_t *piece_src, uint32_t *too_long,
+                  void *stream);
+
 // ---- one long string on the plain DFA: kernels_long.hip
 // One long string (regex.h:156-159 consumes it byte by byte): the string is cut into chunks, every chunk is stepped
 // from EVERY table state at once (lane = (chunk, start state); the lanes of a chunk read the same text), which yields

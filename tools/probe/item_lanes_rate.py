@@ -72,6 +72,15 @@ items (offsets = the line starts, trim 1: the '\\n' is the separator):
                   A difference of two medians counts only beyond the sum of the two spreads [ms].  One child per text, this tree
                   alone; the lines go to `--out` as well.
 
+  filter          the rows a bitmap selects, written as a new column (kernels_filter.hip) on the keyword-log and the e-mail text: a
+                  device-to-device copy of the column beside rrx_pieces_fill of EVERY line (the invert of an all-zero bitmap) - the
+                  fill's share of a plain copy -, then on the pattern's real contains bitmap rrx_bitmap_rank, rrx_filter_sizes,
+                  rrx_filter_corpus_sizes and rrx_pieces_fill one by one, the two generic routes whole, the route a caller took
+                  before with torch (rrx_bitmap_to_bytes, nonzero, index, cumsum, rrx_pieces_fill), contains alone and the three
+                  one-call forms rrx_filter_contains_*; every route must give the same column before anything is timed, all calls
+                  alternate inside one process.  A difference of two medians counts only beyond the sum of the two spreads [ms].
+                  It takes no parent: one child per text, this tree alone; the lines go to `--out` as well.
+
 A yardstick stands in only for a parent that lacks the entry (its wrapper shows it): a later parent runs the entry itself, and both
 sides must find the same.
 
@@ -89,6 +98,7 @@ between its two medians and its own spread - and whether each of the tree's medi
     python tools/probe/item_lanes_rate.py --entry multi_contains [--launches 15] [--scale 1.0] [--out profiles/multi_contains_items_rate.txt]
     python tools/probe/item_lanes_rate.py --entry multi_contains_corpus [--launches 15] [--scale 1.0] [--out profiles/multi_contains_corpus_rate.txt]
     python tools/probe/item_lanes_rate.py --entry search_longest_corpus [--launches 15] [--scale 1.0] [--out profiles/search_longest_corpus_rate.txt]
+    python tools/probe/item_lanes_rate.py --entry filter [--launches 15] [--scale 1.0] [--out profiles/filter_rate.txt]
 """
 import argparse
 import json
@@ -100,7 +110,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CONFIGS = (("url", "U2", 1 << 30), ("email", "EMAIL", 1 << 30), ("kwlog", "K1000C", 1 << 30))
 ENTRIES = ("match", "contains", "search", "search_all", "search_longest", "search_all_longest", "extract_group", "replace", "pieces", "one_call", "replace_groups",
-           "multi_contains", "multi_contains_corpus", "search_longest_corpus")
+           "multi_contains", "multi_contains_corpus", "search_longest_corpus", "filter")
 MULTI_KS = (1, 4, 16, 32)                      # --entry multi_contains: the sizes of the keyword sets
 MULTI_KEYWORDS = ["k%d" % (61 * j + 17) for j in range(32)]     # k17, k78, ... k1908: the text's tokens are k1 .. k2000
 GROUPED = {"EMAIL": r"[A-Za-z0-9._]+@([A-Za-z0-9.]+)"}      # --entry extract_group: the patterns that need a group put in; group 1 everywhere
@@ -151,6 +161,8 @@ def child(tree, entry, kind, pkey, nbytes, launches):
         return multi_contains_corpus_child(rr, kind, dev, off, n, launches)
     if entry == "search_longest_corpus":
         return search_longest_corpus_child(rr, r, kind, dev, off, n, launches)
+    if entry == "filter":
+        return filter_child(rr, r, kind, dev, off, n, launches)
 
     if entry in ("match", "contains"):
         slices = [off[k:k + SLICE + 1] for k in range(0, n, SLICE)]
@@ -462,6 +474,138 @@ def search_longest_corpus_child(rr, r, kind, dev, off, n, launches):
     line["corpus_over_first"] = round(med["corpus"] / med["first"], 4)
     line["corpus_beats_items"] = bool(med["items"] - med["corpus"] > spread["items"] + spread["corpus"])     # beyond the sum of the two spreads
     line["items_beats_corpus"] = bool(med["corpus"] - med["items"] > spread["items"] + spread["corpus"])
+    print(json.dumps(line), flush=True)
+
+
+def filter_child(rr, r, kind, dev, off, n, launches):
+    """The rows a bitmap selects, written as a new column (rrx_bitmap_rank, rrx_filter_sizes, rrx_filter_corpus_sizes, rrx_pieces_fill,
+    rrx_filter_contains_*), all alternating: (a) copy = a device-to-device copy of the column, fill_all = rrx_pieces_fill of EVERY line
+    (the invert of an all-zero bitmap; the output is the text); (b) on the pattern's real contains bitmap: rank, items_select,
+    corpus_select and fill one by one, the two generic routes whole (rank, select, torch.cumsum, the size read back, fill), the route a
+    caller takes today with torch (rrx_bitmap_to_bytes, nonzero, index, cumsum, the size read back, rrx_pieces_fill), contains alone on
+    the corpus and on the indexed batch, and the three one-call forms; one JSON line."""
+    import ctypes as C
+    import torch
+    L, stream = rr._L, rr._stream_ptr(None)
+    nbytes = int(dev.numel())
+    corpus = rr.Corpus(dev)
+    assert corpus.num_lines == n
+    items = rr.Items(dev, off, trim=1)
+    nw = (n + 31) // 32
+    p = lambda t: C.c_void_p(t.data_ptr())
+    rank_words = L.rrx_bitmap_rank_words(n)
+    rank = torch.empty(rank_words, dtype=torch.int64, device="cuda")
+    row, length, src = (torch.empty(n, dtype=torch.int64, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda"),
+                        torch.empty(n, dtype=torch.int64, device="cuda"))
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    out, copy_to = torch.empty(nbytes, dtype=torch.uint8, device="cuda"), torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    as_bytes = torch.empty((n + 15) // 16 * 16, dtype=torch.uint8, device="cuda")
+
+    def do_rank(bits, invert):
+        rr._check(L.rrx_bitmap_rank(0, p(bits), n, invert, p(rank), rank_words, stream))
+
+    def do_select(bits, invert, keep, of_items):
+        if of_items:
+            rr._check(L.rrx_filter_sizes(0, p(off), n, 1, p(bits), invert, p(rank), p(row), p(length), p(src), stream))
+        else:
+            rr._check(L.rrx_filter_corpus_sizes(corpus._h, p(bits), invert, keep, p(rank), p(row), p(length), p(src), stream))
+
+    def prefix(nsel):
+        torch.cumsum(length[:nsel].to(torch.int64) & 0xFFFFFFFF, dim=0, out=out_off[1:nsel + 1])
+        return int(out_off[nsel].item())
+
+    def do_fill(nsel):
+        rr._check(L.rrx_pieces_fill(0, p(dev), p(src), p(out_off), nsel, p(out), stream))
+
+    def route(bits, of_items):
+        do_rank(bits, 0)
+        nsel = int(rank[nw].item())
+        do_select(bits, 0, 0, of_items)
+        total = prefix(nsel)
+        do_fill(nsel)
+        return nsel, total
+
+    def torch_route(bits):
+        rr._check(L.rrx_bitmap_to_bytes(0, p(bits), n, p(as_bytes), stream))
+        rows = torch.nonzero(as_bytes[:n]).flatten()
+        nsel = rows.numel()
+        start = off[rows]
+        src[:nsel] = start
+        torch.cumsum(off[rows + 1] - 1 - start, dim=0, out=out_off[1:nsel + 1])
+        total = int(out_off[nsel].item())
+        do_fill(nsel)
+        return nsel, total
+
+    # (a) every line selected, its newline kept: the output is the text
+    zeros = torch.zeros(nw, dtype=torch.int32, device="cuda")
+    do_rank(zeros, 1)
+    assert int(rank[nw].item()) == n
+    do_select(zeros, 1, 1, False)
+    assert prefix(n) == nbytes
+    do_fill(n)
+    torch.cuda.synchronize()
+    assert torch.equal(out, dev), "every line selected with its newline is not the text"
+    all_src, all_off = src.clone(), out_off.clone()
+
+    # (b) the pattern's contains bitmap
+    bits = r.contains_corpus_bits(corpus).clone()
+    assert torch.equal(r.contains_items_bits(items), bits), "contains on the corpus and on the indexed batch differ"
+    nsel, total = route(bits, True)
+    torch.cuda.synchronize()
+    want_rows, want_off, want_out = row[:nsel].clone(), out_off[:nsel + 1].clone(), out[:total].clone()
+    for name, got in (("corpus", route(bits, False)), ("torch", torch_route(bits))):
+        torch.cuda.synchronize()
+        assert got == (nsel, total) and torch.equal(out_off[:nsel + 1], want_off) and torch.equal(out[:total], want_out), "the %s route differs from the items route" % name
+    assert torch.equal(row[:nsel], want_rows)
+    nrows, tot = C.c_size_t(0), C.c_size_t(0)
+    one_tail = lambda: (p(row), p(out_off), n, p(out), nbytes, C.byref(nrows), C.byref(tot), stream)
+    one = {"one_call_extents": lambda: rr._check(L.rrx_filter_contains_extents(r._h, 0, p(dev), p(off), n, 1, 0, *one_tail())),
+           "one_call_items": lambda: rr._check(L.rrx_filter_contains_items(r._h, items._h, 0, *one_tail())),
+           "one_call_corpus": lambda: rr._check(L.rrx_filter_contains_corpus(r._h, corpus._h, 0, 0, *one_tail()))}
+    for name, call in one.items():
+        call()
+        torch.cuda.synchronize()
+        assert (nrows.value, tot.value) == (nsel, total) and torch.equal(out[:total], want_out) and torch.equal(row[:nsel], want_rows), name + " differs from the items route"
+
+    def select_alone(of_items):
+        do_select(bits, 0, 0, of_items)
+
+    def fill_all():
+        rr._check(L.rrx_pieces_fill(0, p(dev), p(all_src), p(all_off), n, p(out), stream))
+
+    do_rank(bits, 0)                                   # (rank, src and out_off of the selection stay as the single stages need them)
+    select_alone(True)
+    prefix(nsel)
+    calls = {"copy": lambda: copy_to.copy_(dev), "fill_all": fill_all, "rank": lambda: do_rank(bits, 0), "items_select": lambda: select_alone(True),
+             "corpus_select": lambda: select_alone(False), "fill": lambda: do_fill(nsel), "items_route": lambda: route(bits, True),
+             "corpus_route": lambda: route(bits, False), "torch_route": lambda: torch_route(bits),
+             "contains_corpus": lambda: r.contains_corpus_bits(corpus, out=zeros), "contains_items": lambda: r.contains_items_bits(items, out=zeros)}
+    calls.update(one)
+    for call in calls.values():
+        call()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in calls}
+    for _ in range(launches):
+        for k, call in calls.items():                       # alternating: every call has the others right beside it
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); call(); b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    spread = {k: max(v) - min(v) for k, v in ms.items()}
+    line = {"config": kind, "entry": "filter", "bytes": nbytes, "lines": n, "stripe": corpus.stripe, "selected": nsel, "selected_bytes": total, "launches": launches}
+    for k in calls:
+        line[k + "_ms"] = round(med[k], 4)
+        line[k + "_spread_ms"] = round(spread[k], 4)
+    line["copy_GB/s"] = round(nbytes / med["copy"] / 1e6, 1)
+    line["fill_all_GB/s"] = round(nbytes / med["fill_all"] / 1e6, 1)
+    line["fill_all_share_of_copy"] = round(med["copy"] / med["fill_all"], 4)
+    line["fill_GB/s"] = round(total / med["fill"] / 1e6, 1)
+    beats = lambda x, y: bool(med[y] - med[x] > spread[x] + spread[y])       # beyond the sum of the two spreads
+    for x, y in (("corpus_select", "items_select"), ("corpus_route", "items_route"), ("corpus_route", "torch_route"), ("items_route", "torch_route"),
+                 ("one_call_corpus", "one_call_items"), ("one_call_items", "one_call_extents")):
+        line[x + "_over_" + y] = round(med[x] / med[y], 4)
+        line[x + "_beats_" + y], line[y + "_beats_" + x] = beats(x, y), beats(y, x)
     print(json.dumps(line), flush=True)
 
 
@@ -793,6 +937,36 @@ def search_longest_corpus_main(a):
             f.write(json.dumps(x) + "\n")
 
 
+def filter_main(a):
+    """One child per text - the keyword log and the e-mail text -, this tree alone (the parent has no such entry); the lines to a.out."""
+    lines = []
+    for kind, pkey, nbytes in (c for c in CONFIGS if c[0] in ("kwlog", "email")):
+        n = int(nbytes * a.scale) // 4096 * 4096
+        env = dict(os.environ)
+        env.pop("RRX_LIB", None)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--entry", "filter", "--launches", str(a.launches), "--child", ROOT, kind, pkey, str(n)],
+                           env=env, timeout=600, stdout=subprocess.PIPE, text=True)
+        sys.stdout.write(p.stdout)
+        sys.stdout.flush()
+        if p.returncode:                       # a fault or a time limit: nothing more is started on the device
+            raise SystemExit("child failed with %d: filter %s" % (p.returncode, kind))
+        lines.append(json.loads(p.stdout.strip().splitlines()[-1]))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("tools/probe/item_lanes_rate.py --entry filter --launches %d --scale %g: medians of device-event times per call [ms], all calls\n"
+                "alternating in one process per text; x_spread_ms = max - min.  copy = a device-to-device copy of the column; fill_all =\n"
+                "rrx_pieces_fill of every line with its newline (the invert of an all-zero bitmap: the output is the text).  On the pattern's\n"
+                "contains bitmap: rank = rrx_bitmap_rank, items_select = rrx_filter_sizes (trim 1), corpus_select = rrx_filter_corpus_sizes,\n"
+                "fill = rrx_pieces_fill of the selected lines; items_route / corpus_route = rank, the count read back, select, torch.cumsum, the\n"
+                "size read back, fill; torch_route = what a caller did before: rrx_bitmap_to_bytes, torch.nonzero, indexing the offsets, cumsum,\n"
+                "the size read back, rrx_pieces_fill (it needs the offsets array, which a corpus does not have); contains_* = the bitmap alone;\n"
+                "one_call_* = rrx_filter_contains_extents / _items / _corpus, contains included.  All routes and one-call forms gave the same\n"
+                "column before timing.  GB/s = bytes written per second.  x_beats_y = the medians differ by more than the sum of the two\n"
+                "spreads [ms].\n" % (max(a.launches, 12), a.scale))
+        for x in lines:
+            f.write(json.dumps(x) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entry", choices=ENTRIES, required=True)
@@ -807,7 +981,7 @@ def main():
         return child(tree, a.entry, kind, pkey, int(nbytes), max(a.launches, 12))
     if a.out is None:
         stem = {"replace_groups": "replace_template_items", "multi_contains_corpus": "multi_contains_corpus",
-                "search_longest_corpus": "search_longest_corpus"}.get(a.entry, a.entry + "_items")
+                "search_longest_corpus": "search_longest_corpus", "filter": "filter"}.get(a.entry, a.entry + "_items")
         a.out = os.path.join(ROOT, "profiles", stem + "_rate.txt")
     if a.entry == "replace":
         return replace_main(a)
@@ -823,6 +997,8 @@ def main():
         return multi_contains_corpus_main(a)
     if a.entry == "search_longest_corpus":
         return search_longest_corpus_main(a)
+    if a.entry == "filter":
+        return filter_main(a)
     assert os.path.exists(os.path.join(a.old, "roaringregex_amd", "librrx.so")), "build the parent commit under %s first" % a.old
     # a parent that has the entry runs the entry itself: the yardsticks are for the commit that added it
     yardstick = a.entry in YARDSTICK and NEWER[a.entry] not in open(os.path.join(a.old, "roaringregex_amd", "__init__.py")).read()
