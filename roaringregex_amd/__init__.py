@@ -288,6 +288,130 @@ def _span_pair(n, device):
     return torch.empty(n, dtype=torch.int32, device=device), torch.empty(n, dtype=torch.int32, device=device)
 
 
+def _out(out, n, dtype, device):
+    """The output of an entry that writes n words of `dtype`: a fresh tensor, or the caller's `out` - on the device, of that dtype,
+    contiguous, n entries at least - cut to n."""
+    import torch
+    if out is None:
+        return torch.empty(n, dtype=dtype, device=device)
+    assert out.is_cuda and out.dtype == dtype and out.is_contiguous() and out.numel() >= n
+    return out[:n]
+
+
+def _bits_to_bytes(bits, n, out, device, stream):
+    """One byte per bit of the first n bits of a result bitmap (rrx_bitmap_to_bytes), into `out` as _out takes it."""
+    import torch
+    out = _out(out, n, torch.uint8, device)
+    _check(_L.rrx_bitmap_to_bytes(device.index, _ptr(bits), n, _ptr(out), _stream_ptr(stream)))
+    return out
+
+
+def _check_match_list(n, first, start, end):
+    """What every entry on a match list asks of it: `first` with n + 1 entries, start and end of one length."""
+    import torch
+    assert first.is_cuda and first.dtype in (torch.int64, torch.uint64) and first.is_contiguous() and first.numel() == n + 1
+    assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() for t in (start, end)) and start.numel() == end.numel()
+
+
+def _no_null(start, end, device):
+    """(start, end), or one word in place of both where they are empty or not there: the entries take no null array, even where the
+    lists are empty."""
+    import torch
+    if start is not None and start.numel():
+        return start, end
+    word = torch.zeros(1, dtype=torch.int32, device=device)
+    return word, word
+
+
+def _offsets_and_bytes(length, device):
+    """From the lengths of a column's entries (32-bit words, unsigned whatever the dtype says) to its offsets and its bytes ->
+    (out_off int64[n + 1], out uint8[total], uninitialised).  Waits for the total."""
+    import torch
+    out_off = torch.zeros(length.numel() + 1, dtype=torch.int64, device=device)
+    torch.cumsum(length.to(torch.int64) & 0xFFFFFFFF, dim=0, out=out_off[1:])
+    return out_off, torch.empty(int(out_off[-1].item()), dtype=torch.uint8, device=device)
+
+
+def _retry(caps, alloc, call):
+    """A one-call entry, repeated with the exact sizes if a cap was too small: alloc(*caps) -> the output tensors, call(tensors, caps)
+    -> the sizes the entry reports, one per cap.  Each cap grows to the reported size.  -> (the tensors, the sizes)"""
+    while True:
+        bufs = alloc(*caps)
+        need = call(bufs, caps)
+        if all(x <= c for x, c in zip(need, caps)):
+            return bufs, need
+        caps = tuple(max(c, x) for x, c in zip(need, caps))
+
+
+def _search_all_two_pass(dev, n, count_call, fill_call):
+    """count, the prefix with torch, fill -> (count, first, start, end), as search_all shapes them."""
+    import torch
+    count = torch.zeros(n, dtype=torch.int32, device=dev)
+    _check(count_call(_ptr(count)))
+    inclusive = torch.cumsum(count, dim=0, dtype=torch.int64)
+    first = inclusive - count
+    start, end = _span_pair(int(inclusive[-1].item()) if n else 0, dev)
+    if start.numel():
+        _check(fill_call(C.c_void_p(first.data_ptr()), C.c_void_p(start.data_ptr()), C.c_void_p(end.data_ptr())))
+    return count, first, start, end
+
+
+def _search_all_one_call(dev, n, cap, call):
+    """The one-call entry, repeated with the exact size if `cap` was too small -> (first[n + 1], start, end)."""
+    import torch
+    first = torch.empty(n + 1, dtype=torch.int64, device=dev)
+
+    def run(bufs, caps):
+        total = C.c_size_t(0)
+        _check(call(C.c_void_p(first.data_ptr()), _ptr(bufs[0]), _ptr(bufs[1]), caps[0], C.byref(total)))
+        return (total.value,)
+    (start, end), (total,) = _retry((int(cap) if cap is not None else 2 * n + 1024,), lambda c: _span_pair(c, dev), run)
+    return first, start[:total], end[:total]
+
+
+def _replace_one_call(dev, n, cap, call):
+    """The one-call replace entry, repeated with the exact size if `cap` was too small -> (out uint8, out_off int64[n + 1])."""
+    import torch
+    out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+
+    def run(bufs, caps):
+        total = C.c_size_t(0)
+        _check(call(_ptr(out_off), _ptr(bufs[0]), caps[0], C.byref(total)))
+        return (total.value,)
+    (out,), (total,) = _retry((cap,), lambda c: (torch.empty(c, dtype=torch.uint8, device=dev),), run)
+    return out[:total], out_off
+
+
+def _pieces_one_call(dev, n, nbytes, cap, pieces_cap, call):
+    """A one-call pieces entry, repeated with the exact sizes if a cap was too small -> (out, piece_off[npieces + 1], list_off[n + 1])."""
+    import torch
+    list_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+
+    def run(bufs, caps):
+        npieces, total = C.c_size_t(0), C.c_size_t(0)
+        _check(call(_ptr(list_off), _ptr(bufs[1]), caps[1], _ptr(bufs[0]), caps[0], C.byref(npieces), C.byref(total)))
+        return total.value, npieces.value
+    caps = (int(cap) if cap is not None else nbytes, int(pieces_cap) if pieces_cap is not None else 2 * n)
+    (out, piece_off), (total, npieces) = _retry(caps, lambda c, pc: (torch.empty(c, dtype=torch.uint8, device=dev),
+                                                                     torch.empty(pc + 1, dtype=torch.int64, device=dev)), run)
+    return out[:total], piece_off[:npieces + 1], list_off
+
+
+def _filter_one_call(dev, n, nbytes, cap, rows_cap, call):
+    """A one-call filter entry, repeated with the exact sizes if a cap was too small -> (rows int64[nrows], out_off int64[nrows + 1], out uint8)."""
+    import torch
+
+    def run(bufs, caps):
+        nrows, total = C.c_size_t(0), C.c_size_t(0)
+        _check(call(_ptr(bufs[1]), _ptr(bufs[2]), caps[1], _ptr(bufs[0]), caps[0], C.byref(nrows), C.byref(total)))
+        return total.value, nrows.value
+    caps = (int(cap) if cap is not None else nbytes, int(rows_cap) if rows_cap is not None else n)
+    (out, rows, out_off), (total, nrows) = _retry(caps, lambda c, rc: (torch.empty(c, dtype=torch.uint8, device=dev),
+                                                                       torch.empty(rc, dtype=torch.int64, device=dev),
+                                                                       torch.empty(rc + 1, dtype=torch.int64, device=dev)), run)
+    return rows[:nrows], out_off[:nrows + 1], out[:total]
+
+
 def replace_matches(data, offsets, first, start, end, repl, trim=0, stream=None):
     """regexp_replace from a match list, written on the device (rrx_replace_matches_sizes, a torch.cumsum, rrx_replace_matches_fill):
     item i = data[offsets[i] : offsets[i + 1] - trim]; its matches are start/end[first[i] : first[i + 1]], relative to the item, as
@@ -296,20 +420,15 @@ def replace_matches(data, offsets, first, start, end, repl, trim=0, stream=None)
     separators are not copied.  The lists need not come from a regex of this library.  Waits for the output's size."""
     import torch
     n, d = _batch(data, offsets)[:2]
-    assert first.is_cuda and first.dtype in (torch.int64, torch.uint64) and first.is_contiguous() and first.numel() == n + 1
-    assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() for t in (start, end)) and start.numel() == end.numel()
+    _check_match_list(n, first, start, end)
     assert isinstance(repl, (bytes, bytearray))
     with _on(d, stream):
         s = _stream_ptr(stream)
-        if not start.numel():                      # (the entries take no null array, even where the lists are empty)
-            start = end = torch.zeros(1, dtype=torch.int32, device=data.device)
+        start, end = _no_null(start, end, data.device)
         length = torch.empty(n, dtype=torch.int32, device=data.device)
         pos = torch.empty(start.numel(), dtype=torch.int32, device=data.device)
-        out_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
         _check(_L.rrx_replace_matches_sizes(d, _ptr(offsets), n, trim, _ptr(first), _ptr(start), _ptr(end), len(repl), _ptr(length), _ptr(pos), s))
-        torch.cumsum(length.to(torch.int64) & 0xFFFFFFFF, dim=0, out=out_off[1:])
-        total = int(out_off[-1].item())
-        out = torch.empty(total, dtype=torch.uint8, device=data.device)
+        out_off, out = _offsets_and_bytes(length, data.device)
         rep = torch.frombuffer(bytearray(repl), dtype=torch.uint8).to(data.device) if repl else torch.empty(0, dtype=torch.uint8, device=data.device)
         _check(_L.rrx_replace_matches_fill(d, _ptr(data), _ptr(offsets), n, trim, _ptr(first), _ptr(end), _ptr(pos), _ptr(rep), len(repl), _ptr(out_off),
                                            _ptr(out), s))
@@ -367,8 +486,7 @@ def replace_template(data, offsets, first, start, end, template, ref_start=None,
     import torch
     n, d = _batch(data, offsets)[:2]
     assert isinstance(template, Template)
-    assert first.is_cuda and first.dtype in (torch.int64, torch.uint64) and first.is_contiguous() and first.numel() == n + 1
-    assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() for t in (start, end)) and start.numel() == end.numel()
+    _check_match_list(n, first, start, end)
     nrefs = len(template.refs)
     stride = int(plane_stride) if plane_stride is not None else start.numel()
     if nrefs:
@@ -376,18 +494,13 @@ def replace_template(data, offsets, first, start, end, template, ref_start=None,
         assert stride >= start.numel() and min(ref_start.numel(), ref_end.numel()) >= (nrefs - 1) * stride + start.numel()
     with _on(d, stream):
         s = _stream_ptr(stream)
-        if not start.numel():                      # (the entries take no null array, even where the lists are empty)
-            start = end = torch.zeros(1, dtype=torch.int32, device=data.device)
-        if not nrefs or not ref_start.numel():
-            ref_start = ref_end = torch.zeros(1, dtype=torch.int32, device=data.device)
+        start, end = _no_null(start, end, data.device)
+        ref_start, ref_end = _no_null(ref_start if nrefs else None, ref_end, data.device)
         length = torch.empty(n, dtype=torch.int32, device=data.device)
         pos = torch.empty(start.numel(), dtype=torch.int32, device=data.device)
-        out_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
         _check(_L.rrx_replace_template_sizes(d, _ptr(offsets), n, trim, _ptr(first), _ptr(start), _ptr(end), template._h, _ptr(ref_start), _ptr(ref_end),
                                              stride, _ptr(length), _ptr(pos), s))
-        torch.cumsum(length.to(torch.int64) & 0xFFFFFFFF, dim=0, out=out_off[1:])
-        total = int(out_off[-1].item())
-        out = torch.empty(total, dtype=torch.uint8, device=data.device)
+        out_off, out = _offsets_and_bytes(length, data.device)
         _check(_L.rrx_replace_template_fill(d, _ptr(data), _ptr(offsets), n, trim, _ptr(first), _ptr(start), _ptr(end), _ptr(pos), template._h,
                                             _ptr(ref_start), _ptr(ref_end), stride, _ptr(out_off), _ptr(out), s))
     return out, out_off
@@ -405,24 +518,19 @@ def pieces_of_matches(data, offsets, first, start, end, gaps=False, trim=0, stre
     than the matches: re.split).  The lists need not come from a regex of this library.  Waits for the output's size."""
     import torch
     n, d = _batch(data, offsets)[:2]
-    assert first.is_cuda and first.dtype in (torch.int64, torch.uint64) and first.is_contiguous() and first.numel() == n + 1
-    assert all(t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() for t in (start, end)) and start.numel() == end.numel()
+    _check_match_list(n, first, start, end)
     with _on(d, stream):
         s = _stream_ptr(stream)
         list_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
         if not n:
             return torch.empty(0, dtype=torch.uint8, device=data.device), torch.zeros(1, dtype=torch.int64, device=data.device), list_off
         npieces = int((first[-1] - first[0]).item()) + (n if gaps else 0)
-        if not start.numel():                      # (the entries take no null array, even where the lists are empty)
-            start = end = torch.zeros(1, dtype=torch.int32, device=data.device)
+        start, end = _no_null(start, end, data.device)
         length = torch.empty(max(npieces, 1), dtype=torch.int32, device=data.device)
         src = torch.empty(max(npieces, 1), dtype=torch.int64, device=data.device)
-        piece_off = torch.zeros(npieces + 1, dtype=torch.int64, device=data.device)
         _check(_L.rrx_pieces_sizes(d, _ptr(offsets), n, trim, _ptr(first), _ptr(start), _ptr(end), PIECES_GAPS if gaps else PIECES_MATCHES, _ptr(list_off),
                                    _ptr(length), _ptr(src), s))
-        if npieces:
-            torch.cumsum(length[:npieces].to(torch.int64) & 0xFFFFFFFF, dim=0, out=piece_off[1:])
-        out = torch.empty(int(piece_off[-1].item()), dtype=torch.uint8, device=data.device)
+        piece_off, out = _offsets_and_bytes(length[:npieces], data.device)
         _check(_L.rrx_pieces_fill(d, _ptr(data), _ptr(src), _ptr(piece_off), npieces, _ptr(out), s))
     return out, piece_off, list_off
 
@@ -443,14 +551,12 @@ def _filter_column(data, nsel, sizes, dev, s):
     (rows int64[nsel], out_off int64[nsel + 1], out uint8).  Waits for the output's size."""
     import torch
     rows = torch.empty(nsel, dtype=torch.int64, device=data.device)
-    out_off = torch.zeros(nsel + 1, dtype=torch.int64, device=data.device)
     if not nsel:
-        return rows, out_off, torch.empty(0, dtype=torch.uint8, device=data.device)
+        return rows, torch.zeros(1, dtype=torch.int64, device=data.device), torch.empty(0, dtype=torch.uint8, device=data.device)
     length = torch.empty(nsel, dtype=torch.int32, device=data.device)
     src = torch.empty(nsel, dtype=torch.int64, device=data.device)
     _check(sizes(_ptr(rows), _ptr(length), _ptr(src)))
-    torch.cumsum(length.to(torch.int64) & 0xFFFFFFFF, dim=0, out=out_off[1:])
-    out = torch.empty(int(out_off[-1].item()), dtype=torch.uint8, device=data.device)
+    out_off, out = _offsets_and_bytes(length, data.device)
     _check(_L.rrx_pieces_fill(dev, _ptr(data), _ptr(src), _ptr(out_off), nsel, _ptr(out), s))
     return rows, out_off, out
 
@@ -631,10 +737,7 @@ class RRegex:
         import torch
         nw = _L.rrx_corpus_bitmap_words(corpus._h)
         with _on(corpus.device, stream):
-            if out is None:
-                out = torch.empty(nw, dtype=torch.int32, device=corpus.data.device)
-            assert out.is_cuda and out.dtype == torch.int32 and out.numel() >= nw
-            out = out[:nw]
+            out = _out(out, nw, torch.int32, corpus.data.device)
             _check(_L.rrx_match_corpus(self._h, corpus._h, _ptr(out), _stream_ptr(stream)))
         return out
 
@@ -649,9 +752,7 @@ class RRegex:
             cap_lines = n + 1
         cap_words = (cap_lines + 31) // 32
         with _on(data.device.index, stream):
-            if out is None:
-                out = torch.empty(cap_words, dtype=torch.int32, device=data.device)
-            assert out.is_cuda and out.dtype == torch.int32 and out.numel() >= cap_words
+            out = _out(out, cap_words, torch.int32, data.device)
             nlines = C.c_size_t(0)
             _check(_L.rrx_match_device(self._h, data.device.index, _ptr(data), n,
                                        C.c_void_p(out.data_ptr()), cap_words, C.byref(nlines), _stream_ptr(stream)))
@@ -659,16 +760,8 @@ class RRegex:
 
     def match_corpus(self, corpus, out=None, stream=None):
         """accept[i] = 1 iff line i of the corpus is accepted (one byte per line: bitmap + expansion)."""
-        import torch
-        n = corpus.num_lines
         with _on(corpus.device, stream):
-            bits = self.match_corpus_bits(corpus, stream=stream)
-            if out is None:
-                out = torch.empty(n, dtype=torch.uint8, device=corpus.data.device)
-            assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
-            out = out[:n]
-            _check(_L.rrx_bitmap_to_bytes(corpus.device, _ptr(bits), n, _ptr(out), _stream_ptr(stream)))
-        return out
+            return _bits_to_bytes(self.match_corpus_bits(corpus, stream=stream), corpus.num_lines, out, corpus.data.device, stream)
 
     def contains_corpus_bits(self, corpus, out=None, stream=None):
         """Which lines CONTAIN a match (rrx_contains_corpus): a bitmap of 32-bit words, an int32 tensor like match_corpus_bits',
@@ -677,25 +770,14 @@ class RRegex:
         import torch
         nw = _L.rrx_corpus_bitmap_words(corpus._h)
         with _on(corpus.device, stream):
-            if out is None:
-                out = torch.empty(nw, dtype=torch.int32, device=corpus.data.device)
-            assert out.is_cuda and out.dtype == torch.int32 and out.numel() >= nw
-            out = out[:nw]
+            out = _out(out, nw, torch.int32, corpus.data.device)
             _check(_L.rrx_contains_corpus(self._h, corpus._h, _ptr(out), _stream_ptr(stream)))
         return out
 
     def contains_corpus(self, corpus, out=None, stream=None):
         """contains[i] = 1 iff line i of the corpus contains a match (one byte per line: bitmap + expansion)."""
-        import torch
-        n = corpus.num_lines
         with _on(corpus.device, stream):
-            bits = self.contains_corpus_bits(corpus, stream=stream)
-            if out is None:
-                out = torch.empty(n, dtype=torch.uint8, device=corpus.data.device)
-            assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
-            out = out[:n]
-            _check(_L.rrx_bitmap_to_bytes(corpus.device, _ptr(bits), n, _ptr(out), _stream_ptr(stream)))
-        return out
+            return _bits_to_bytes(self.contains_corpus_bits(corpus, stream=stream), corpus.num_lines, out, corpus.data.device, stream)
 
     def search_corpus(self, corpus, stream=None):
         """Per string the accepted substring [start, end) with the smallest end, then the smallest start, as two int32
@@ -718,50 +800,27 @@ class RRegex:
     def search_all(self, corpus, stream=None):
         """ALL lazy matches of every string, left to right -> (count[n] int32, first[n] int64, start[total] int32,
         end[total] int32): the matches of string i are start/end[first[i] : first[i] + count[i]], relative to the string."""
-        import torch
-        n = corpus.num_lines
-        dev = corpus.data.device
         with _on(corpus.device, stream):
-            count = torch.zeros(n, dtype=torch.int32, device=dev)
-            _check(_L.rrx_search_all_count(self._h, corpus._h, _ptr(count), _stream_ptr(stream)))
-            inclusive = torch.cumsum(count, dim=0, dtype=torch.int64)
-            first = inclusive - count
-            total = int(inclusive[-1].item()) if n else 0
-            start = torch.empty(total, dtype=torch.int32, device=dev)
-            end = torch.empty(total, dtype=torch.int32, device=dev)
-            if total:
-                _check(_L.rrx_search_all_fill(self._h, corpus._h, C.c_void_p(first.data_ptr()), _ptr(start), _ptr(end), _stream_ptr(stream)))
-        return count, first, start, end
+            s = _stream_ptr(stream)
+            return _search_all_two_pass(corpus.data.device, corpus.num_lines,
+                                        lambda c: _L.rrx_search_all_count(self._h, corpus._h, c, s),
+                                        lambda f, st, en: _L.rrx_search_all_fill(self._h, corpus._h, f, st, en, s))
 
     def search_all_fused(self, corpus, cap=None, stream=None):
         """The same result through the one-call entry (rrx_search_all: one pass over the text) ->
         (first[n + 1] int64 CSR offsets, start[total] int32, end[total] int32).  cap: entries to provide for at first
         (default: two per string); the call is repeated with the exact size if there are more."""
-        import torch
-        n = corpus.num_lines
-        dev = corpus.data.device
         with _on(corpus.device, stream):
-            first = torch.empty(n + 1, dtype=torch.int64, device=dev)
-            cap = int(cap) if cap is not None else 2 * n + 1024
-            while True:
-                start = torch.empty(cap, dtype=torch.int32, device=dev)
-                end = torch.empty(cap, dtype=torch.int32, device=dev)
-                total = C.c_size_t(0)
-                _check(_L.rrx_search_all(self._h, corpus._h, C.c_void_p(first.data_ptr()), _ptr(start), _ptr(end), cap, C.byref(total), _stream_ptr(stream)))
-                if total.value <= cap:
-                    break
-                cap = total.value
-        return first, start[:total.value], end[:total.value]
+            s = _stream_ptr(stream)
+            return _search_all_one_call(corpus.data.device, corpus.num_lines, cap,
+                                        lambda f, st, en, cp, tot: _L.rrx_search_all(self._h, corpus._h, f, st, en, cp, tot, s))
 
     def match_items(self, items, out=None, stream=None):
         """One byte per item of an indexed batch (Items)."""
         import torch
         n = items.num_items
         with _on(items.device, stream):
-            if out is None:
-                out = torch.empty(n, dtype=torch.uint8, device=items.data.device)
-            assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
-            out = out[:n]
+            out = _out(out, n, torch.uint8, items.data.device)
             _check(_L.rrx_match_items(self._h, items._h, _ptr(out), _stream_ptr(stream)))
         return out
 
@@ -770,9 +829,7 @@ class RRegex:
         import torch
         n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
-            if out is None:
-                out = torch.empty(n, dtype=torch.uint8, device=data.device)
-            out = out[:n]
+            out = _out(out, n, torch.uint8, data.device)
             _check(_L.rrx_match_extents(self._h, d, b, o, n, trim, _ptr(out), _stream_ptr(stream)))
         return out
 
@@ -784,25 +841,14 @@ class RRegex:
         n = items.num_items
         nw = (n + 31) // 32
         with _on(items.device, stream):
-            if out is None:
-                out = torch.empty(nw, dtype=torch.int32, device=items.data.device)
-            assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= nw
-            out = out[:nw]
+            out = _out(out, nw, torch.int32, items.data.device)
             _check(_L.rrx_contains_items(self._h, items._h, _ptr(out), _stream_ptr(stream)))
         return out
 
     def contains_items(self, items, out=None, stream=None):
         """contains[i] = 1 iff item i of the indexed batch contains a match (one byte per item: bitmap + expansion)."""
-        import torch
-        n = items.num_items
         with _on(items.device, stream):
-            bits = self.contains_items_bits(items, stream=stream)
-            if out is None:
-                out = torch.empty(n, dtype=torch.uint8, device=items.data.device)
-            assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
-            out = out[:n]
-            _check(_L.rrx_bitmap_to_bytes(items.device, _ptr(bits), n, _ptr(out), _stream_ptr(stream)))
-        return out
+            return _bits_to_bytes(self.contains_items_bits(items, stream=stream), items.num_items, out, items.data.device, stream)
 
     def contains_extents_bits(self, data, offsets, trim=0, out=None, stream=None):
         """The same for a batch nobody has indexed (rrx_contains_extents): item i = data[offsets[i] : offsets[i+1] - trim] -> the
@@ -811,25 +857,15 @@ class RRegex:
         n, d, b, o = _batch(data, offsets)
         nw = (n + 31) // 32
         with _on(d, stream):
-            if out is None:
-                out = torch.empty(nw, dtype=torch.int32, device=data.device)
-            assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= nw
-            out = out[:nw]
+            out = _out(out, nw, torch.int32, data.device)
             _check(_L.rrx_contains_extents(self._h, d, b, o, n, trim, _ptr(out), _stream_ptr(stream)))
         return out
 
     def contains_extents(self, data, offsets, trim=0, out=None, stream=None):
         """contains[i] = 1 iff item i = data[offsets[i] : offsets[i+1] - trim] contains a match (one byte per item)."""
-        import torch
         n, d = _batch(data, offsets)[:2]
         with _on(d, stream):
-            bits = self.contains_extents_bits(data, offsets, trim=trim, stream=stream)
-            if out is None:
-                out = torch.empty(n, dtype=torch.uint8, device=data.device)
-            assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= n
-            out = out[:n]
-            _check(_L.rrx_bitmap_to_bytes(d, _ptr(bits), n, _ptr(out), _stream_ptr(stream)))
-        return out
+            return _bits_to_bytes(self.contains_extents_bits(data, offsets, trim=trim, stream=stream), n, out, data.device, stream)
 
     def search_items(self, items, stream=None):
         """Per item of an indexed batch (Items) the accepted substring [start, end) with the smallest end, then the smallest start
@@ -849,35 +885,6 @@ class RRegex:
             _check(_L.rrx_search_extents(self._h, d, b, o, n, trim, _ptr(start), _ptr(end), _stream_ptr(stream)))
         return start, end
 
-    def _search_all_two_pass(self, dev, n, count_call, fill_call):
-        """count, the prefix with torch, fill -> (count, first, start, end), as search_all shapes them."""
-        import torch
-        count = torch.zeros(n, dtype=torch.int32, device=dev)
-        _check(count_call(_ptr(count)))
-        inclusive = torch.cumsum(count, dim=0, dtype=torch.int64)
-        first = inclusive - count
-        total = int(inclusive[-1].item()) if n else 0
-        start = torch.empty(total, dtype=torch.int32, device=dev)
-        end = torch.empty(total, dtype=torch.int32, device=dev)
-        if total:
-            _check(fill_call(C.c_void_p(first.data_ptr()), C.c_void_p(start.data_ptr()), C.c_void_p(end.data_ptr())))
-        return count, first, start, end
-
-    def _search_all_one_call(self, dev, n, cap, call):
-        """The one-call entry, repeated with the exact size if `cap` was too small -> (first[n + 1], start, end)."""
-        import torch
-        first = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        cap = int(cap) if cap is not None else 2 * n + 1024
-        while True:
-            start = torch.empty(cap, dtype=torch.int32, device=dev)
-            end = torch.empty(cap, dtype=torch.int32, device=dev)
-            total = C.c_size_t(0)
-            _check(call(C.c_void_p(first.data_ptr()), _ptr(start), _ptr(end), cap, C.byref(total)))
-            if total.value <= cap:
-                break
-            cap = total.value
-        return first, start[:total.value], end[:total.value]
-
     def search_all_items(self, items, stream=None):
         """ALL matches of every item of an indexed batch (Items), left to right (rrx_search_all_items_count / _fill) ->
         (count[n] int32, first[n] int64, start[total] int32, end[total] int32), shaped as search_all returns them: the matches of
@@ -885,18 +892,18 @@ class RRegex:
         behind match k; '\\n', NUL and bytes >= 0x80 are ordinary text inside an item."""
         with _on(items.device, stream):
             s = _stream_ptr(stream)
-            return self._search_all_two_pass(items.data.device, items.num_items,
-                                             lambda c: _L.rrx_search_all_items_count(self._h, items._h, c, s),
-                                             lambda f, st, en: _L.rrx_search_all_items_fill(self._h, items._h, f, st, en, s))
+            return _search_all_two_pass(items.data.device, items.num_items,
+                                        lambda c: _L.rrx_search_all_items_count(self._h, items._h, c, s),
+                                        lambda f, st, en: _L.rrx_search_all_items_fill(self._h, items._h, f, st, en, s))
 
     def search_all_extents(self, data, offsets, trim=0, stream=None):
         """The same for a batch nobody has indexed (rrx_search_all_extents_count / _fill): item i = data[offsets[i] : offsets[i+1] - trim]."""
         n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
-            return self._search_all_two_pass(data.device, n,
-                                             lambda c: _L.rrx_search_all_extents_count(self._h, d, b, o, n, trim, c, s),
-                                             lambda f, st, en: _L.rrx_search_all_extents_fill(self._h, d, b, o, n, trim, f, st, en, s))
+            return _search_all_two_pass(data.device, n,
+                                        lambda c: _L.rrx_search_all_extents_count(self._h, d, b, o, n, trim, c, s),
+                                        lambda f, st, en: _L.rrx_search_all_extents_fill(self._h, d, b, o, n, trim, f, st, en, s))
 
     def search_all_items_fused(self, items, cap=None, stream=None):
         """The same result through the one-call entry (rrx_search_all_items) -> (first[n + 1] int64 CSR offsets, start[total] int32,
@@ -904,16 +911,16 @@ class RRegex:
         if there are more."""
         with _on(items.device, stream):
             s = _stream_ptr(stream)
-            return self._search_all_one_call(items.data.device, items.num_items, cap,
-                                             lambda f, st, en, cp, tot: _L.rrx_search_all_items(self._h, items._h, f, st, en, cp, tot, s))
+            return _search_all_one_call(items.data.device, items.num_items, cap,
+                                        lambda f, st, en, cp, tot: _L.rrx_search_all_items(self._h, items._h, f, st, en, cp, tot, s))
 
     def search_all_extents_fused(self, data, offsets, trim=0, cap=None, stream=None):
         """The one-call entry for a batch nobody has indexed (rrx_search_all_extents) -> (first[n + 1], start, end)."""
         n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
-            return self._search_all_one_call(data.device, n, cap,
-                                             lambda f, st, en, cp, tot: _L.rrx_search_all_extents(self._h, d, b, o, n, trim, f, st, en, cp, tot, s))
+            return _search_all_one_call(data.device, n, cap,
+                                        lambda f, st, en, cp, tot: _L.rrx_search_all_extents(self._h, d, b, o, n, trim, f, st, en, cp, tot, s))
 
     def search_longest_items(self, items, stream=None):
         """Per item of an indexed batch (Items) the LEFTMOST-LONGEST match [start, end) (rrx_search_longest_items): the smallest start
@@ -950,9 +957,9 @@ class RRegex:
             s = _stream_ptr(stream)
             marks, words = self._search_all_longest_marks(items.data, items.num_items)
             m = C.c_void_p(marks.data_ptr())
-            return self._search_all_two_pass(items.data.device, items.num_items,
-                                             lambda c: _L.rrx_search_all_longest_items_count(self._h, items._h, m, words, c, s),
-                                             lambda f, st, en: _L.rrx_search_all_longest_items_fill(self._h, items._h, m, words, f, st, en, s))
+            return _search_all_two_pass(items.data.device, items.num_items,
+                                        lambda c: _L.rrx_search_all_longest_items_count(self._h, items._h, m, words, c, s),
+                                        lambda f, st, en: _L.rrx_search_all_longest_items_fill(self._h, items._h, m, words, f, st, en, s))
 
     def search_all_longest_extents(self, data, offsets, trim=0, stream=None):
         """The same for a batch nobody has indexed (rrx_search_all_longest_extents_count / _fill): item i = data[offsets[i] : offsets[i+1] - trim]."""
@@ -961,9 +968,9 @@ class RRegex:
             s = _stream_ptr(stream)
             marks, words = self._search_all_longest_marks(data, n)
             m = C.c_void_p(marks.data_ptr())
-            return self._search_all_two_pass(data.device, n,
-                                             lambda c: _L.rrx_search_all_longest_extents_count(self._h, d, b, o, n, trim, m, words, c, s),
-                                             lambda f, st, en: _L.rrx_search_all_longest_extents_fill(self._h, d, b, o, n, trim, m, words, f, st, en, s))
+            return _search_all_two_pass(data.device, n,
+                                        lambda c: _L.rrx_search_all_longest_extents_count(self._h, d, b, o, n, trim, m, words, c, s),
+                                        lambda f, st, en: _L.rrx_search_all_longest_extents_fill(self._h, d, b, o, n, trim, m, words, f, st, en, s))
 
     def search_all_longest_items_fused(self, items, cap=None, stream=None):
         """The same result through the one-call entry (rrx_search_all_longest_items) -> (first[n + 1] int64 CSR offsets, start[total]
@@ -971,29 +978,16 @@ class RRegex:
         size if there are more."""
         with _on(items.device, stream):
             s = _stream_ptr(stream)
-            return self._search_all_one_call(items.data.device, items.num_items, cap,
-                                             lambda f, st, en, cp, tot: _L.rrx_search_all_longest_items(self._h, items._h, f, st, en, cp, tot, s))
+            return _search_all_one_call(items.data.device, items.num_items, cap,
+                                        lambda f, st, en, cp, tot: _L.rrx_search_all_longest_items(self._h, items._h, f, st, en, cp, tot, s))
 
     def search_all_longest_extents_fused(self, data, offsets, trim=0, cap=None, stream=None):
         """The one-call entry for a batch nobody has indexed (rrx_search_all_longest_extents) -> (first[n + 1], start, end)."""
         n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
-            return self._search_all_one_call(data.device, n, cap,
-                                             lambda f, st, en, cp, tot: _L.rrx_search_all_longest_extents(self._h, d, b, o, n, trim, f, st, en, cp, tot, s))
-
-    def _replace_one_call(self, dev, n, cap, call):
-        """The one-call replace entry, repeated with the exact size if `cap` was too small -> (out uint8, out_off int64[n + 1])."""
-        import torch
-        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        while True:
-            out = torch.empty(cap, dtype=torch.uint8, device=dev)
-            total = C.c_size_t(0)
-            _check(call(_ptr(out_off), _ptr(out), cap, C.byref(total)))
-            if total.value <= cap:
-                break
-            cap = total.value
-        return out[:total.value], out_off
+            return _search_all_one_call(data.device, n, cap,
+                                        lambda f, st, en, cp, tot: _L.rrx_search_all_longest_extents(self._h, d, b, o, n, trim, f, st, en, cp, tot, s))
 
     def replace_all_longest_extents(self, data, offsets, repl, trim=0, cap=None, stream=None):
         """regexp_replace on a string column (rrx_replace_all_longest_extents): item i = data[offsets[i] : offsets[i+1] - trim] with
@@ -1004,8 +998,8 @@ class RRegex:
         (n, d, b, o), rep = _batch(data, offsets), bytes(repl)
         with _on(d, stream):
             s = _stream_ptr(stream)
-            return self._replace_one_call(data.device, n, int(cap) if cap is not None else data.numel(),
-                                          lambda f, out, cp, tot: _L.rrx_replace_all_longest_extents(self._h, d, b, o, n, trim, rep, len(rep), f, out, cp, tot, s))
+            return _replace_one_call(data.device, n, int(cap) if cap is not None else data.numel(),
+                                     lambda f, out, cp, tot: _L.rrx_replace_all_longest_extents(self._h, d, b, o, n, trim, rep, len(rep), f, out, cp, tot, s))
 
     def replace_all_longest_items(self, items, repl, cap=None, stream=None):
         """The same for an indexed batch (rrx_replace_all_longest_items) -> (out uint8, out_off int64[n + 1])."""
@@ -1013,24 +1007,8 @@ class RRegex:
         rep = bytes(repl)
         with _on(items.device, stream):
             s = _stream_ptr(stream)
-            return self._replace_one_call(items.data.device, items.num_items, int(cap) if cap is not None else items.data.numel(),
-                                          lambda f, out, cp, tot: _L.rrx_replace_all_longest_items(self._h, items._h, rep, len(rep), f, out, cp, tot, s))
-
-    def _pieces_one_call(self, dev, n, nbytes, cap, pieces_cap, call):
-        """A one-call pieces entry, repeated with the exact sizes if a cap was too small -> (out, piece_off[npieces + 1], list_off[n + 1])."""
-        import torch
-        cap = int(cap) if cap is not None else nbytes
-        pieces_cap = int(pieces_cap) if pieces_cap is not None else 2 * n
-        list_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        while True:
-            out = torch.empty(cap, dtype=torch.uint8, device=dev)
-            piece_off = torch.empty(pieces_cap + 1, dtype=torch.int64, device=dev)
-            npieces, total = C.c_size_t(0), C.c_size_t(0)
-            _check(call(_ptr(list_off), _ptr(piece_off), pieces_cap, _ptr(out), cap, C.byref(npieces), C.byref(total)))
-            if npieces.value <= pieces_cap and total.value <= cap:
-                break
-            cap, pieces_cap = max(cap, total.value), max(pieces_cap, npieces.value)
-        return out[:total.value], piece_off[:npieces.value + 1], list_off
+            return _replace_one_call(items.data.device, items.num_items, int(cap) if cap is not None else items.data.numel(),
+                                     lambda f, out, cp, tot: _L.rrx_replace_all_longest_items(self._h, items._h, rep, len(rep), f, out, cp, tot, s))
 
     def extract_all_longest_extents(self, data, offsets, trim=0, cap=None, pieces_cap=None, stream=None):
         """regexp_extract_all on a string column (rrx_extract_all_longest_extents): EVERY LEFTMOST-LONGEST match of item i =
@@ -1041,15 +1019,15 @@ class RRegex:
         n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
-            return self._pieces_one_call(data.device, n, data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
-                                         _L.rrx_extract_all_longest_extents(self._h, d, b, o, n, trim, lo, po, pc, out, cp, npc, tot, s))
+            return _pieces_one_call(data.device, n, data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
+                                    _L.rrx_extract_all_longest_extents(self._h, d, b, o, n, trim, lo, po, pc, out, cp, npc, tot, s))
 
     def extract_all_longest_items(self, items, cap=None, pieces_cap=None, stream=None):
         """The same for an indexed batch (rrx_extract_all_longest_items)."""
         with _on(items.device, stream):
             s = _stream_ptr(stream)
-            return self._pieces_one_call(items.data.device, items.num_items, items.data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
-                                         _L.rrx_extract_all_longest_items(self._h, items._h, lo, po, pc, out, cp, npc, tot, s))
+            return _pieces_one_call(items.data.device, items.num_items, items.data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
+                                    _L.rrx_extract_all_longest_items(self._h, items._h, lo, po, pc, out, cp, npc, tot, s))
 
     def split_longest_extents(self, data, offsets, trim=0, cap=None, pieces_cap=None, stream=None):
         """split on a string column (rrx_split_longest_extents): what lies between the leftmost-longest matches of every item, one
@@ -1058,31 +1036,15 @@ class RRegex:
         n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
-            return self._pieces_one_call(data.device, n, data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
-                                         _L.rrx_split_longest_extents(self._h, d, b, o, n, trim, lo, po, pc, out, cp, npc, tot, s))
+            return _pieces_one_call(data.device, n, data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
+                                    _L.rrx_split_longest_extents(self._h, d, b, o, n, trim, lo, po, pc, out, cp, npc, tot, s))
 
     def split_longest_items(self, items, cap=None, pieces_cap=None, stream=None):
         """The same for an indexed batch (rrx_split_longest_items)."""
         with _on(items.device, stream):
             s = _stream_ptr(stream)
-            return self._pieces_one_call(items.data.device, items.num_items, items.data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
-                                         _L.rrx_split_longest_items(self._h, items._h, lo, po, pc, out, cp, npc, tot, s))
-
-    def _filter_one_call(self, dev, n, nbytes, cap, rows_cap, call):
-        """A one-call filter entry, repeated with the exact sizes if a cap was too small -> (rows int64[nrows], out_off int64[nrows + 1], out uint8)."""
-        import torch
-        cap = int(cap) if cap is not None else nbytes
-        rows_cap = int(rows_cap) if rows_cap is not None else n
-        while True:
-            out = torch.empty(cap, dtype=torch.uint8, device=dev)
-            rows = torch.empty(rows_cap, dtype=torch.int64, device=dev)
-            out_off = torch.empty(rows_cap + 1, dtype=torch.int64, device=dev)
-            nrows, total = C.c_size_t(0), C.c_size_t(0)
-            _check(call(_ptr(rows), _ptr(out_off), rows_cap, _ptr(out), cap, C.byref(nrows), C.byref(total)))
-            if nrows.value <= rows_cap and total.value <= cap:
-                break
-            cap, rows_cap = max(cap, total.value), max(rows_cap, nrows.value)
-        return rows[:nrows.value], out_off[:nrows.value + 1], out[:total.value]
+            return _pieces_one_call(items.data.device, items.num_items, items.data.numel(), cap, pieces_cap, lambda lo, po, pc, out, cp, npc, tot:
+                                    _L.rrx_split_longest_items(self._h, items._h, lo, po, pc, out, cp, npc, tot, s))
 
     def filter_contains_extents(self, data, offsets, trim=0, invert=False, cap=None, rows_cap=None, stream=None):
         """SELECT col WHERE col RLIKE p on a string column (rrx_filter_contains_extents): the items data[offsets[i] : offsets[i+1] -
@@ -1093,15 +1055,15 @@ class RRegex:
         n, d, b, o = _batch(data, offsets)
         with _on(d, stream):
             s = _stream_ptr(stream)
-            return self._filter_one_call(data.device, n, data.numel(), cap, rows_cap, lambda rows, oo, rc, out, cp, nr, tot:
-                                         _L.rrx_filter_contains_extents(self._h, d, b, o, n, trim, int(bool(invert)), rows, oo, rc, out, cp, nr, tot, s))
+            return _filter_one_call(data.device, n, data.numel(), cap, rows_cap, lambda rows, oo, rc, out, cp, nr, tot:
+                                    _L.rrx_filter_contains_extents(self._h, d, b, o, n, trim, int(bool(invert)), rows, oo, rc, out, cp, nr, tot, s))
 
     def filter_contains_items(self, items, invert=False, cap=None, rows_cap=None, stream=None):
         """The same for an indexed batch (rrx_filter_contains_items: contains runs stripe-wise where the batch admits it)."""
         with _on(items.device, stream):
             s = _stream_ptr(stream)
-            return self._filter_one_call(items.data.device, items.num_items, items.data.numel(), cap, rows_cap, lambda rows, oo, rc, out, cp, nr, tot:
-                                         _L.rrx_filter_contains_items(self._h, items._h, int(bool(invert)), rows, oo, rc, out, cp, nr, tot, s))
+            return _filter_one_call(items.data.device, items.num_items, items.data.numel(), cap, rows_cap, lambda rows, oo, rc, out, cp, nr, tot:
+                                    _L.rrx_filter_contains_items(self._h, items._h, int(bool(invert)), rows, oo, rc, out, cp, nr, tot, s))
 
     def filter_contains_corpus(self, corpus, invert=False, keep_newline=True, cap=None, rows_cap=None, stream=None):
         """grep (invert: grep -v) on a '\n'-corpus (rrx_filter_contains_corpus): the lines that contain a match, in the shape
@@ -1109,9 +1071,9 @@ class RRegex:
         again and `grep p1 | grep p2` needs no host step."""
         with _on(corpus.device, stream):
             s = _stream_ptr(stream)
-            return self._filter_one_call(corpus.data.device, corpus.num_lines, corpus.num_bytes, cap, rows_cap, lambda rows, oo, rc, out, cp, nr, tot:
-                                         _L.rrx_filter_contains_corpus(self._h, corpus._h, int(bool(invert)), int(bool(keep_newline)), rows, oo, rc, out, cp, nr,
-                                                                       tot, s))
+            return _filter_one_call(corpus.data.device, corpus.num_lines, corpus.num_bytes, cap, rows_cap, lambda rows, oo, rc, out, cp, nr, tot:
+                                    _L.rrx_filter_contains_corpus(self._h, corpus._h, int(bool(invert)), int(bool(keep_newline)), rows, oo, rc, out, cp, nr,
+                                                                  tot, s))
 
     def match_string(self, data, stream=None):
         """ONE device-resident string of any length (regex.h:156-159); '\n' is an ordinary character.  -> bool"""
@@ -1463,13 +1425,10 @@ class RGroup:
         with _on(d, stream):
             start, end = self.extract_extents(data, offsets, trim=trim, stream=stream)
             valid = start >= 0
-            out_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
             if not n:
-                return valid, out_off, torch.empty(0, dtype=torch.uint8, device=data.device)
-            length = torch.where(valid, (end - start).to(torch.int64), torch.zeros((), dtype=torch.int64, device=data.device))
-            torch.cumsum(length, dim=0, out=out_off[1:])
+                return valid, torch.zeros(1, dtype=torch.int64, device=data.device), torch.empty(0, dtype=torch.uint8, device=data.device)
+            out_off, out = _offsets_and_bytes(torch.where(valid, end - start, torch.zeros_like(start)), data.device)
             src = (offsets[:n].to(torch.int64) + torch.where(valid, start, torch.zeros_like(start)).to(torch.int64)).contiguous()
-            out = torch.empty(int(out_off[-1].item()), dtype=torch.uint8, device=data.device)
             _check(_L.rrx_pieces_fill(d, _ptr(data), _ptr(src), _ptr(out_off), n, _ptr(out), _stream_ptr(stream)))
         return valid, out_off, out
 
@@ -1491,8 +1450,8 @@ def replace_groups_longest_extents(groups, template, data, offsets, trim=0, cap=
     n, d, b, o = _batch(data, offsets)
     with _on(d, stream):
         s = _stream_ptr(stream)
-        return RRegex._replace_one_call(None, data.device, n, int(cap) if cap is not None else data.numel(),
-                                        lambda f, out, cp, tot: _L.rrx_replace_groups_longest_extents(h, len(groups), tpl._h, d, b, o, n, trim, f, out, cp, tot, s))
+        return _replace_one_call(data.device, n, int(cap) if cap is not None else data.numel(),
+                                 lambda f, out, cp, tot: _L.rrx_replace_groups_longest_extents(h, len(groups), tpl._h, d, b, o, n, trim, f, out, cp, tot, s))
 
 
 def replace_groups_longest_items(groups, template, items, cap=None, stream=None):
@@ -1501,8 +1460,8 @@ def replace_groups_longest_items(groups, template, items, cap=None, stream=None)
     h = _group_handles(groups)
     with _on(items.device, stream):
         s = _stream_ptr(stream)
-        return RRegex._replace_one_call(None, items.data.device, items.num_items, int(cap) if cap is not None else items.data.numel(),
-                                        lambda f, out, cp, tot: _L.rrx_replace_groups_longest_items(h, len(groups), tpl._h, items._h, f, out, cp, tot, s))
+        return _replace_one_call(items.data.device, items.num_items, int(cap) if cap is not None else items.data.numel(),
+                                 lambda f, out, cp, tot: _L.rrx_replace_groups_longest_items(h, len(groups), tpl._h, items._h, f, out, cp, tot, s))
 
 
 class RMulti:
@@ -1554,10 +1513,7 @@ class RMulti:
     @staticmethod
     def _masks(n, device, out):
         import torch
-        if out is None:
-            out = torch.empty(n, dtype=torch.int32, device=device)
-        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n
-        return out[:n]
+        return _out(out, n, torch.int32, device)
 
     def contains_extents(self, data, offsets, trim=0, out=None, stream=None):
         """Item i = data[offsets[i] : offsets[i+1] - trim] -> an int32 tensor of n masks, bit k = the item contains a match of
@@ -1603,9 +1559,6 @@ class RMulti:
         n = masks.numel()
         nw = (n + 31) // 32
         with _on(masks.device.index, stream):
-            if out is None:
-                out = torch.empty(nw, dtype=torch.int32, device=masks.device)
-            assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= nw
-            out = out[:nw]
+            out = _out(out, nw, torch.int32, masks.device)
             _check(_L.rrx_multi_plane(masks.device.index, _ptr(masks), n, k, _ptr(out), _stream_ptr(stream)))
         return out

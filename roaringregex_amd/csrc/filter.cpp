@@ -1,7 +1,7 @@
 // filter.cpp — the rows a result bitmap selects, written as a new column: the generic entries on any bitmap (rrx_bitmap_rank,
 // rrx_filter_sizes for an offsets column, rrx_filter_corpus_sizes for the lines of a corpus; the bytes are rrx_pieces_fill's) and the
-// one-call "grep" forms rrx_filter_contains_* - the pattern's contains bitmap of the call's own, its rank, the selected rows' triples,
-// a scan of their lengths, the cap rule and the fill (kernels_filter.hip, kernels_pieces_items.hip).
+// one-call "grep" forms rrx_filter_contains_* - the pattern's contains bitmap of the call's own, its rank, then the tail every sized
+// column shares (items.hpp: SizedColumn) around the selected rows' triples and the fill (kernels_filter.hip, kernels_pieces_items.hip).
 #include <functional>
 
 #include "items.hpp"
@@ -21,9 +21,8 @@ struct FilterOut { uint64_t *d_row, *d_out_off; size_t rows_cap; void *d_out; si
 
 bool filter_out_ok(const FilterOut &o) { return o.d_out_off && o.nrows && o.total && (!o.rows_cap || o.d_row) && (!o.cap || o.d_out); }
 
-// contains into a bitmap of the call's own, its rank, the number of selected rows read back; then their triples, the scan of the
-// lengths - into the caller's offsets if they hold them, into an array of the call's own otherwise: the total is exact either way -
-// and, if both caps hold, the bytes.  The sizes kernel raises a device word where a row has 2^30 bytes or more.
+// contains into a bitmap of the call's own, its rank, the number of selected rows read back; then the column's tail (items.hpp:
+// SizedColumn): the selected rows' triples, the scan of their lengths and, if both caps hold, the bytes.
 int filter_one_call(const FilterSource &s, bool invert, const FilterOut &o, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     *o.nrows = *o.total = 0;
@@ -46,34 +45,18 @@ int filter_one_call(const FilterSource &s, bool invert, const FilterOut &o, void
         HIP_TRY(hipStreamSynchronize(st));
     }
     *o.nrows = (size_t)nsel;
-    if (!nsel) { HIP_TRY(hipMemsetAsync(o.d_out_off, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
+    if (!nsel) return empty_batch({o.d_out_off}, stream);
     const bool rows_fit = nsel <= o.rows_cap;
-    // (the last word of d_len is the flag)
-    DeviceArray<uint32_t> d_len;
-    DeviceArray<uint64_t> d_src, d_sums, d_own_off;
-    hipError_t he = d_len.alloc(s.device, (nsel + 1) * sizeof(uint32_t));
+    SizedColumn col("filter", "a selected row of 2^30 bytes or more: use the contains entry and the generic entries rrx_bitmap_rank, rrx_filter_sizes / rrx_filter_corpus_sizes and rrx_pieces_fill");
+    DeviceArray<uint64_t> d_src;
+    hipError_t he = col.alloc(s.device, nsel, o.d_out_off, rows_fit);
     if (he == hipSuccess) he = d_src.alloc(s.device, nsel * sizeof(uint64_t));
-    if (he == hipSuccess) he = d_sums.alloc(s.device, dev::scan_scratch_words(nsel) * sizeof(uint64_t));
-    if (he == hipSuccess && !rows_fit) he = d_own_off.alloc(s.device, (nsel + 1) * sizeof(uint64_t));
     if (he != hipSuccess) return hip_fail(he, "hipMalloc(filter rows)");
-    uint64_t *out_off = rows_fit ? o.d_out_off : (uint64_t *)d_own_off;
-    uint32_t *d_flag = d_len + nsel;
-    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st));
-    rc = s.sizes(d_bits, d_rank, rows_fit ? o.d_row : nullptr, d_len, d_src, d_flag, stream);
+    rc = col.sizes([&](uint32_t *d_len, uint32_t *d_flag) { return s.sizes(d_bits, d_rank, rows_fit ? o.d_row : nullptr, d_len, d_src, d_flag, stream); },
+                   o.total, stream);
     if (rc) return rc;
-    uint64_t tot = 0;
-    uint32_t flag = 0;
-    rc = scan_total(d_len, out_off, d_sums, nsel, stream, "filter sizes and scan launch", "filter scan", &tot, d_flag, &flag);
-    if (rc) return rc;
-    if (flag) return fail(RRX_ERR_UNSUPPORTED, "a selected row of 2^30 bytes or more: use the contains entry and the generic entries rrx_bitmap_rank, rrx_filter_sizes / rrx_filter_corpus_sizes and rrx_pieces_fill");
-    *o.total = (size_t)tot;
-    if (rows_fit && tot && tot <= o.cap) {                                       // a column beyond either cap: not a byte of it is written
-        const int le = dev::pieces_fill(s.bytes, d_src, out_off, nsel, static_cast<uint8_t *>(o.d_out), stream);
-        if (le) return hip_fail((hipError_t)le, "pieces_fill launch");
-        he = hipStreamSynchronize(st);
-        if (he != hipSuccess) return hip_fail(he, "filter fill");
-    }
-    return RRX_OK;
+    return col.fill(o.cap, [&] { return launched(dev::pieces_fill(s.bytes, d_src, col.off, nsel, static_cast<uint8_t *>(o.d_out), stream), "pieces_fill launch"); },
+                    stream);
 }
 int filter_items_one_call(const ItemBatch &b, std::function<int(uint32_t *, void *)> contains, bool invert, const FilterOut &o, void *stream) {
     const FilterSource s{b.device, b.bytes, b.nitems, std::move(contains),

@@ -129,12 +129,13 @@ int group_extract(const rrx_group *g, const ItemBatch &b, ItemMarks m, uint32_t 
 
 
 // regexp_replace with group references in one call: rrx_replace_all_longest_*'s steps with the spans of the referenced groups between
-// the match list and the sizes - one plane per referenced group, each from its own handle - and the template's two passes in place
-// of the literal ones.  groups[g - 1]: the handle of group g of ONE pattern; the first one there is searches.
+// the match list and the column's tail (items.hpp: SizedColumn) - one plane per referenced group, each from its own handle - and the
+// template's two passes in place of the literal ones.  groups[g - 1]: the handle of group g of ONE pattern; the first one there is searches.
 int replace_groups_one_call(const rrx_group *const *groups, size_t ngroups, const rrx_template *tpl, const ItemBatch &b, uint64_t *d_out_off, void *d_out,
                             size_t cap, size_t *total, void *stream) {
-    const auto &[device, bytes, off, nitems, trim] = b;
-    if (!groups || !tpl || !total || !d_out_off || (nitems && (!off || (cap && !d_out)))) return fail(RRX_ERR_ARG, "null argument");
+    const int device = b.device;
+    const size_t nitems = b.nitems;
+    if (!groups || !tpl || !total || !d_out_off || (nitems && (!b.off || (cap && !d_out)))) return fail(RRX_ERR_ARG, "null argument");
     const rrx_group *lead = nullptr;
     for (size_t k = 0; k < ngroups; k++) {
         if (!groups[k]) continue;
@@ -146,22 +147,22 @@ int replace_groups_one_call(const rrx_group *const *groups, size_t ngroups, cons
         if ((size_t)ref > ngroups || !groups[ref - 1]) return fail(RRX_ERR_ARG, "the template references group " + std::to_string(ref) + ", which has no handle");
     const rrx_regex *re = lead->whole;
     *total = 0;
-    hipStream_t st = (hipStream_t)stream;
     int rc = search_longest_tables_on(re, device);
     if (rc) return rc;
-    if (!nitems) { HIP_TRY(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
+    if (!nitems) return empty_batch({d_out_off}, stream);
     dev::TemplateDevice t;
     rc = tpl->on(device, &t);
     if (rc) return rc;
     LongestMatchList m;
     rc = m.count(re, b, "hipMalloc(replace prefix)", stream);
     if (rc) return rc;
-    // (one word more than the lists need: the generic kernels are never handed a null array; the last word of d_len is the flag)
+    // (one word more than the lists need: the generic kernels are never handed a null array)
     const size_t nplanes = tpl->t.refs.size(), stride = m.nmatches;
-    DeviceArray<uint32_t> d_pos, d_len, d_ref_start, d_ref_end;
+    SizedColumn col("replace", "an output item of 2^30 bytes or more: use rrx_search_all_longest_extents, rrx_group_spans_list_extents and the two passes rrx_replace_template_sizes / _fill");
+    DeviceArray<uint32_t> d_pos, d_ref_start, d_ref_end;
     hipError_t he = m.alloc_lists(device);
     if (he == hipSuccess) he = d_pos.alloc(device, (m.nmatches + 1) * sizeof(uint32_t));
-    if (he == hipSuccess) he = d_len.alloc(device, (nitems + 1) * sizeof(uint32_t));
+    if (he == hipSuccess) he = col.alloc(device, nitems, d_out_off, true, m.c.sums);          // (the first scan's scratch: the stream orders the two)
     if (he == hipSuccess) he = d_ref_start.alloc(device, (nplanes * stride + 1) * sizeof(uint32_t));
     if (he == hipSuccess) he = d_ref_end.alloc(device, (nplanes * stride + 1) * sizeof(uint32_t));
     if (he != hipSuccess) return hip_fail(he, "hipMalloc(replace lists)");
@@ -173,24 +174,16 @@ int replace_groups_one_call(const rrx_group *const *groups, size_t ngroups, cons
                               stream);
         if (rc) return rc;
     }
-    uint32_t *d_flag = d_len + nitems;
-    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st));
-    int le = dev::replace_template_sizes(t, off, nitems, trim, m.first, m.start, m.end, d_ref_start, d_ref_end, stride, d_len, d_pos, d_flag, stream);
-    if (le) return hip_fail((hipError_t)le, "replace sizes and scan launch");
-    uint64_t tot = 0;
-    uint32_t flag = 0;
-    rc = scan_total(d_len, d_out_off, m.c.sums, nitems, stream, "replace sizes and scan launch", "replace scan", &tot, d_flag, &flag);
+    rc = col.sizes([&](uint32_t *d_len, uint32_t *d_flag) {
+        return launched(dev::replace_template_sizes(t, b.off, nitems, b.trim, m.first, m.start, m.end, d_ref_start, d_ref_end, stride, d_len, d_pos, d_flag, stream),
+                        "replace sizes and scan launch");
+    }, total, stream);
     if (rc) return rc;
-    if (flag) return fail(RRX_ERR_UNSUPPORTED, "an output item of 2^30 bytes or more: use rrx_search_all_longest_extents, rrx_group_spans_list_extents and the two passes rrx_replace_template_sizes / _fill");
-    *total = (size_t)tot;
-    if (tot && tot <= cap) {                                                     // a column beyond cap: not a byte of it is written
-        le = dev::replace_template_fill(t, bytes, off, nitems, trim, m.first, m.start, m.end, d_pos, d_ref_start, d_ref_end, stride, d_out_off,
-                                        static_cast<uint8_t *>(d_out), stream);
-        if (le) return hip_fail((hipError_t)le, "replace_template_fill launch");
-        he = hipStreamSynchronize(st);
-        if (he != hipSuccess) return hip_fail(he, "replace fill");
-    }
-    return RRX_OK;
+    return col.fill(cap, [&] {
+        return launched(dev::replace_template_fill(t, b.bytes, b.off, nitems, b.trim, m.first, m.start, m.end, d_pos, d_ref_start, d_ref_end, stride, d_out_off,
+                                                   static_cast<uint8_t *>(d_out), stream),
+                        "replace_template_fill launch");
+    }, stream);
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // item_columns.cpp — new columns from the matches of explicit items: regexp_replace (rrx_replace_matches_* from any match list,
 // rrx_replace_all_longest_* in one call) and the list<binary> columns of regexp_extract_all and split (rrx_pieces_* from any match
 // list, rrx_extract_all_longest_* / rrx_split_longest_* in one call).  A one-call entry is the leftmost-longest match list of the
-// call's own (items.hpp: LongestMatchList), then what is the column's: sizes, a second scan, the cap rule and the fill.
+// call's own (items.hpp: LongestMatchList), then the tail every sized column shares (items.hpp: SizedColumn - sizes, a second scan,
+// the cap rule and the fill) around the two launches that are the column's.
 #include <cstring>
 
 #include "items.hpp"
@@ -58,49 +59,41 @@ int rrx_replace_matches_fill(int device, const void *d_bytes, const uint64_t *d_
                                       rep_len, d_out_off, static_cast<uint8_t *>(d_out), stream),
                     "replace_fill launch");
 }
-// Every leftmost-longest match replaced, in one call: the match list, then sizes, a second scan (the lengths into d_out_off, on the
-// first scan's scratch: the stream orders them) and - if the column fits `cap` - the bytes.  The sizes kernel raises a device word
-// where an output item has 2^30 bytes or more (the scan carries 30 bits); it is read back with the total.
+// Every leftmost-longest match replaced, in one call: the match list, then the column's tail (items.hpp: SizedColumn) - the output
+// items' lengths, their scan into d_out_off and, if the column fits `cap`, the bytes.
 static int replace_all_longest_one_call(const rrx_regex *re, const ItemBatch &b, const void *rep, uint32_t rep_len, uint64_t *d_out_off, void *d_out,
                                         size_t cap, size_t *total, void *stream) {
-    const auto &[device, bytes, off, nitems, trim] = b;
+    const int device = b.device;
+    const size_t nitems = b.nitems;
     if (!batch_args_ok(re, b, {}) || !total || !d_out_off || (rep_len && !rep) || (nitems && cap && !d_out)) return fail(RRX_ERR_ARG, "null argument");
     *total = 0;
-    hipStream_t st = (hipStream_t)stream;
     int rc = search_longest_tables_on(re, device);
     if (rc) return rc;
-    if (!nitems) { HIP_TRY(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
+    if (!nitems) return empty_batch({d_out_off}, stream);
     LongestMatchList m;
     rc = m.count(re, b, "hipMalloc(replace prefix)", stream);
     if (rc) return rc;
-    // (one word more than the lists need: the generic kernels are never handed a null array; the last word of d_len is the flag)
-    DeviceArray<uint32_t> d_pos, d_len;
+    // (one word more than the lists need: the generic kernels are never handed a null array)
+    SizedColumn col("replace", "an output item of 2^30 bytes or more: use rrx_search_all_longest_extents and the two passes rrx_replace_matches_sizes / _fill");
+    DeviceArray<uint32_t> d_pos;
     DeviceArray<uint8_t> d_rep;
     hipError_t he = m.alloc_lists(device);
     if (he == hipSuccess) he = d_pos.alloc(device, (m.nmatches + 1) * sizeof(uint32_t));
-    if (he == hipSuccess) he = d_len.alloc(device, (nitems + 1) * sizeof(uint32_t));
+    if (he == hipSuccess) he = col.alloc(device, nitems, d_out_off, true, m.c.sums);          // (the first scan's scratch: the stream orders the two)
     if (he == hipSuccess && rep_len) he = d_rep.alloc(device, rep_len);
     if (he != hipSuccess) return hip_fail(he, "hipMalloc(replace lists)");
-    if (rep_len) HIP_TRY(hipMemcpyAsync(d_rep, rep, rep_len, hipMemcpyHostToDevice, st));      // (the call does not return before a synchronise: `rep` stays valid)
+    // (the call does not return before a synchronise: `rep` stays valid)
+    if (rep_len) HIP_TRY(hipMemcpyAsync(d_rep, rep, rep_len, hipMemcpyHostToDevice, (hipStream_t)stream));
     rc = m.fill(re, b, stream);
     if (rc) return rc;
-    uint32_t *d_flag = d_len + nitems;
-    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st));
-    int le = dev::replace_sizes(off, nitems, trim, m.first, m.start, m.end, rep_len, d_len, d_pos, d_flag, stream);
-    if (le) return hip_fail((hipError_t)le, "replace sizes and scan launch");
-    uint64_t tot = 0;
-    uint32_t flag = 0;
-    rc = scan_total(d_len, d_out_off, m.c.sums, nitems, stream, "replace sizes and scan launch", "replace scan", &tot, d_flag, &flag);
+    rc = col.sizes([&](uint32_t *d_len, uint32_t *d_flag) {
+        return launched(dev::replace_sizes(b.off, nitems, b.trim, m.first, m.start, m.end, rep_len, d_len, d_pos, d_flag, stream), "replace sizes and scan launch");
+    }, total, stream);
     if (rc) return rc;
-    if (flag) return fail(RRX_ERR_UNSUPPORTED, "an output item of 2^30 bytes or more: use rrx_search_all_longest_extents and the two passes rrx_replace_matches_sizes / _fill");
-    *total = (size_t)tot;
-    if (tot && tot <= cap) {                                                     // a column beyond cap: not a byte of it is written
-        le = dev::replace_fill(bytes, off, nitems, trim, m.first, m.end, d_pos, d_rep, rep_len, d_out_off, static_cast<uint8_t *>(d_out), stream);
-        if (le) return hip_fail((hipError_t)le, "replace_fill launch");
-        he = hipStreamSynchronize(st);
-        if (he != hipSuccess) return hip_fail(he, "replace fill");
-    }
-    return RRX_OK;
+    return col.fill(cap, [&] {
+        return launched(dev::replace_fill(b.bytes, b.off, nitems, b.trim, m.first, m.end, d_pos, d_rep, rep_len, d_out_off, static_cast<uint8_t *>(d_out), stream),
+                        "replace_fill launch");
+    }, stream);
 }
 int rrx_replace_all_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                                     const void *rep, uint32_t rep_len, uint64_t *d_out_off, void *d_out, size_t cap, size_t *total, void *stream) {
@@ -198,58 +191,37 @@ int rrx_pieces_fill(int device, const void *d_bytes, const uint64_t *d_piece_src
     return launched(dev::pieces_fill(static_cast<const uint8_t *>(d_bytes), d_piece_src, d_piece_off, npieces, static_cast<uint8_t *>(d_out), stream),
                     "pieces_fill launch");
 }
-// The pieces of every leftmost-longest match list, in one call: the match list, then sizes, a second scan (the piece lengths into
-// the piece offsets - the caller's array if it holds them, one of the call's own otherwise: the total is exact either way) and - if
-// both caps hold - the bytes.  The number of pieces follows from the number of matches on the host.  The sizes kernel raises a
-// device word where a piece has 2^30 bytes or more.
+// The pieces of every leftmost-longest match list, in one call: the match list, then the column's tail (items.hpp: SizedColumn) -
+// the piece lengths, their scan into the piece offsets and, if both caps hold, the bytes.  The number of pieces follows from the
+// number of matches on the host.
 static int pieces_all_longest_one_call(const rrx_regex *re, const ItemBatch &b, bool gaps, uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap,
                                        void *d_out, size_t cap, size_t *npieces, size_t *total, void *stream) {
-    const auto &[device, bytes, off, nitems, trim] = b;
+    const int device = b.device;
+    const size_t nitems = b.nitems;
     if (!batch_args_ok(re, b, {}) || !npieces || !total || !d_list_off || !d_piece_off || (nitems && cap && !d_out)) return fail(RRX_ERR_ARG, "null argument");
     *npieces = *total = 0;
-    hipStream_t st = (hipStream_t)stream;
     int rc = search_longest_tables_on(re, device);
     if (rc) return rc;
-    if (!nitems) {
-        HIP_TRY(hipMemsetAsync(d_list_off, 0, sizeof(uint64_t), st));
-        HIP_TRY(hipMemsetAsync(d_piece_off, 0, sizeof(uint64_t), st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return RRX_OK;
-    }
+    if (!nitems) return empty_batch({d_list_off, d_piece_off}, stream);
     LongestMatchList m;
     rc = m.count(re, b, "hipMalloc(pieces prefix)", stream);
     if (rc) return rc;
     const size_t np = m.nmatches + (gaps ? nitems : 0);
     *npieces = np;
-    // (one word more than the lists need: the generic kernels are never handed a null array; the last word of d_len is the flag)
-    DeviceArray<uint32_t> d_len;
-    DeviceArray<uint64_t> d_src, d_sums, d_own_off;
+    // (one word more than the lists need: the generic kernels are never handed a null array)
+    SizedColumn col("pieces", "a piece of 2^30 bytes or more: use rrx_search_all_longest_extents and the two passes rrx_pieces_sizes / _fill");
+    DeviceArray<uint64_t> d_src;
     hipError_t he = m.alloc_lists(device);
-    if (he == hipSuccess) he = d_len.alloc(device, (np + 2) * sizeof(uint32_t));
+    if (he == hipSuccess) he = col.alloc(device, np, d_piece_off, np <= pieces_cap);
     if (he == hipSuccess) he = d_src.alloc(device, (np + 1) * sizeof(uint64_t));
-    if (he == hipSuccess) he = d_sums.alloc(device, dev::scan_scratch_words(np) * sizeof(uint64_t));
-    if (he == hipSuccess && np > pieces_cap) he = d_own_off.alloc(device, (np + 1) * sizeof(uint64_t));
     if (he != hipSuccess) return hip_fail(he, "hipMalloc(pieces lists)");
-    uint64_t *piece_off = np > pieces_cap ? (uint64_t *)d_own_off : d_piece_off;
     rc = m.fill(re, b, stream);
     if (rc) return rc;
-    uint32_t *d_flag = d_len + np + 1;
-    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st));
-    int le = dev::pieces_sizes(off, nitems, trim, m.first, m.start, m.end, gaps, d_list_off, d_len, d_src, d_flag, stream);
-    if (le) return hip_fail((hipError_t)le, "pieces sizes and scan launch");
-    uint64_t tot = 0;
-    uint32_t flag = 0;
-    rc = scan_total(d_len, piece_off, d_sums, np, stream, "pieces sizes and scan launch", "pieces scan", &tot, d_flag, &flag);
+    rc = col.sizes([&](uint32_t *d_len, uint32_t *d_flag) {
+        return launched(dev::pieces_sizes(b.off, nitems, b.trim, m.first, m.start, m.end, gaps, d_list_off, d_len, d_src, d_flag, stream), "pieces sizes and scan launch");
+    }, total, stream);
     if (rc) return rc;
-    if (flag) return fail(RRX_ERR_UNSUPPORTED, "a piece of 2^30 bytes or more: use rrx_search_all_longest_extents and the two passes rrx_pieces_sizes / _fill");
-    *total = (size_t)tot;
-    if (np <= pieces_cap && tot && tot <= cap) {                                 // a column beyond either cap: not a byte of it is written
-        le = dev::pieces_fill(bytes, d_src, piece_off, np, static_cast<uint8_t *>(d_out), stream);
-        if (le) return hip_fail((hipError_t)le, "pieces_fill launch");
-        he = hipStreamSynchronize(st);
-        if (he != hipSuccess) return hip_fail(he, "pieces fill");
-    }
-    return RRX_OK;
+    return col.fill(cap, [&] { return launched(dev::pieces_fill(b.bytes, d_src, col.off, np, static_cast<uint8_t *>(d_out), stream), "pieces_fill launch"); }, stream);
 }
 int rrx_extract_all_longest_extents(const rrx_regex *re, int device, const void *d_bytes, const uint64_t *d_off, size_t nitems, uint32_t trim,
                                     uint64_t *d_list_off, uint64_t *d_piece_off, size_t pieces_cap, void *d_out, size_t cap, size_t *npieces, size_t *total,

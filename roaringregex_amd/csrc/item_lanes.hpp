@@ -1,8 +1,8 @@
 // item_lanes.hpp — what the lane-per-item kernels share: the span of an item, the wave-per-64-items grid-stride loop,
 // match_extents_kernel itself, and the host half of their launchers.  Included by the units that hold such a kernel only:
 // kernels_table.hip and kernels_nfa.inc (match_extents_kernel), kernels_contains_items.hip, kernels_search_items.hip,
-// kernels_search_all_items.hip, kernels_search_longest_items.hip, kernels_search_all_longest_items.hip, kernels_replace_items.hip,
-// kernels_replace_template_items.hip, kernels_pieces_items.hip (no walk in these three: their kernels take the span, the loop and the
+// kernels_search_all_items.hip, kernels_search_longest_items.hip, kernels_search_all_longest_items.hip, kernels_replace_items.hip and
+// kernels_replace_template_items.hip (through replace_sweep.hpp), kernels_pieces_items.hip (no walk in these three: their kernels take the span, the loop and the
 // launcher), kernels_group_items.hip and kernels_multi_items.hip (contains_extents_kernel's walk on a product table) - and by
 // kernels_search_longest_corpus.hip, a lane-per-STRIPE kernel, for the launcher, the result constants and the placement rule of the
 // two plain tables alone.

@@ -131,7 +131,7 @@ int all_one_call(const AllMatches &f, const rrx_regex *re, const ItemBatch &b, u
     hipStream_t st = (hipStream_t)stream;
     int rc = f.tables(re, b.device);
     if (rc) return rc;
-    if (!b.nitems) { HIP_TRY(hipMemsetAsync(d_first, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
+    if (!b.nitems) return empty_batch({d_first}, stream);
     MatchCounts c;
     rc = count_scan(f, re, b, c, d_first, total, stream);
     if (rc) return rc;

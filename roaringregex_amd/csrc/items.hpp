@@ -1,6 +1,7 @@
-// items.hpp — what the units of the explicit-items entries share (items.cpp, item_search.cpp, item_columns.cpp, group.cpp; the scan
-// step also search.cpp): the batch as every lane-per-item path takes it, the argument check of an entry on a batch, the two
-// read-backs of the one-call entries, the tables step, and the leftmost-longest match list of a call's own.
+// items.hpp — what the units of the explicit-items entries share (items.cpp, item_search.cpp, item_columns.cpp, group.cpp, filter.cpp;
+// the scan step and the empty-batch answer also search.cpp): the batch as every lane-per-item path takes it, the argument check of an
+// entry on a batch, the two read-backs of the one-call entries, the tail of the one-call entries that write a sized column
+// (SizedColumn: sizes, scan, cap rule, fill), the tables step, and the leftmost-longest match list of a call's own.
 #pragma once
 #include <initializer_list>
 
@@ -48,6 +49,60 @@ inline int scan_total(const uint32_t *d_count, uint64_t *d_prefix, uint64_t *d_s
     if (he == hipSuccess) he = hipStreamSynchronize(st);
     return he == hipSuccess ? RRX_OK : hip_fail(he, text);
 }
+
+// What a one-call entry answers for a batch without items: entry 0 of every offsets array it returns, zero.  One synchronise.
+inline int empty_batch(std::initializer_list<uint64_t *> offsets, void *stream) {
+    for (uint64_t *d_off : offsets) HIP_TRY(hipMemsetAsync(d_off, 0, sizeof(uint64_t), (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return RRX_OK;
+}
+
+// The tail of a one-call entry that writes a variable-size column of n entries: their lengths, the scan of the lengths into the
+// offsets, the cap rule and the fill.  THE CAP RULE: the total is exact whatever the caps; a column beyond a cap - its n entries
+// beyond the caller's offsets array (`fits` false), or its bytes beyond `cap` - is not written, not a byte of it.
+//   alloc()  the lengths (n words, one at the very least: the generic kernels are never handed a null array) with the flag word
+//            behind them; the scan's scratch unless the caller has one of scan_scratch_words(n) to lend (d_sums); offsets of the
+//            call's own (n + 1 entries) where the caller's do not hold the column.  The caller reports a failure with its own lists.
+//   sizes()  the flag zeroed, the caller's launch - it fills the lengths and raises the flag where an entry has 2^30 bytes or more:
+//            the scan carries 30 bits -, scan_total with the flag; a raised flag is refused with `too_long`.  Leaves *total.
+//   fill()   the caller's launch and its one synchronise, only where every cap holds and there is a byte to write.
+// Both launches return what the entry is to return (launched(...)).  `word`: "replace", "pieces", "filter" in the error texts.
+struct SizedColumn {
+    const char *const word, *const too_long;
+    SizedColumn(const char *word_, const char *too_long_) : word(word_), too_long(too_long_) {}
+    size_t n = 0, total = 0;
+    bool fits = true;
+    DeviceArray<uint32_t> len;
+    DeviceArray<uint64_t> own_sums, own_off;
+    uint64_t *sums = nullptr, *off = nullptr;
+    hipError_t alloc(int device, size_t n_, uint64_t *d_off, bool fits_, uint64_t *d_sums = nullptr) {
+        n = n_, fits = fits_, off = d_off, sums = d_sums;
+        hipError_t he = len.alloc(device, ((n ? n : 1) + 1) * sizeof(uint32_t));
+        if (he == hipSuccess && !sums) { he = own_sums.alloc(device, rrx::dev::scan_scratch_words(n) * sizeof(uint64_t)); sums = own_sums; }
+        if (he == hipSuccess && !fits) { he = own_off.alloc(device, (n + 1) * sizeof(uint64_t)); off = own_off; }
+        return he;
+    }
+    template <class Launch> int sizes(Launch &&launch, size_t *total_out, void *stream) {
+        const std::string w = word;
+        uint32_t *d_flag = len + (n ? n : 1), flag = 0;
+        HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), (hipStream_t)stream));
+        int rc = launch(static_cast<uint32_t *>(len), d_flag);
+        if (rc) return rc;
+        uint64_t tot = 0;
+        rc = scan_total(len, off, sums, n, stream, (w + " sizes and scan launch").c_str(), (w + " scan").c_str(), &tot, d_flag, &flag);
+        if (rc) return rc;
+        if (flag) return fail(RRX_ERR_UNSUPPORTED, too_long);
+        *total_out = total = (size_t)tot;
+        return RRX_OK;
+    }
+    template <class Launch> int fill(size_t cap, Launch &&launch, void *stream) {
+        if (!fits || !total || total > cap) return RRX_OK;
+        const int rc = launch();
+        if (rc) return rc;
+        const hipError_t he = hipStreamSynchronize((hipStream_t)stream);
+        return he == hipSuccess ? RRX_OK : hip_fail(he, (std::string(word) + " fill").c_str());
+    }
+};
 
 // The tables of one of a regex' searches on `device` (`tables`: rrx_regex::search_item_tables, ::search_longest_tables ...), uploaded
 // at their first use, and `device` made current: what every entry of that search begins with, on an empty batch too - a regex

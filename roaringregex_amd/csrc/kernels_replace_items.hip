@@ -2,125 +2,45 @@
 // rrx_replace_all_longest_*): from a column (bytes, offsets, trim), a match list per item (the CSR arrays every rrx_search_all* entry
 // returns) and a literal replacement R of rep_len bytes to the new column.  No table, no regex: the kernels do not know where a list
 // came from.  Output item i = t[0:s_0] + R + t[e_0:s_1] + R + ... + R + t[e_{m-1}:], t = the item without its separator.
-// Two kernels, the two passes of every CSR result: SIZES (a lane per item) and FILL (a wave per 64 items, driven by OUTPUT bytes).
-#include "item_lanes.hpp"
+// Two kernels, the two passes of every CSR result: SIZES (a lane per item) and FILL (a wave per 64 items, driven by OUTPUT bytes);
+// both are described in replace_sweep.hpp, which the template unit shares.
+#include "replace_sweep.hpp"
 
 namespace rrx {
 namespace dev {
 namespace {
 
-// SIZES.  One lane per item (item_lanes.hpp: the loop, the item's span), walking its matches in order: pos[slot] = where the R of
-// that match begins inside the OUTPUT item = s_k - (what the matches before it removed) + k * rep_len, len[i] = the output item's
-// length, saturated at ~0u.  `shift` is (k * rep_len - removed) mod 2^64.  Every one of the nitems words of `len` and exactly the
-// slots first[i] .. first[i + 1] of `pos` are written with plain stores; a lane is as slow as its item has matches, and its loads of
-// match_start / match_end are scattered.  too_long (may be null): set to 1 by every lane whose item's output has 2^30 bytes or
-// more - the same value from every lane, a plain store (the one-call form zeroes the word and reads it back: scan_counts carries 30 bits).
+// The literal replacement: the same rep_len bytes behind every match.
+struct LiteralReplacement {
+    const uint8_t *__restrict__ rep;
+    uint32_t rep_len;
+    __device__ __forceinline__ bool holds(uint64_t, uint64_t at, uint64_t q, uint64_t, bool &in_rep, uint64_t &origin, uint64_t &lim, uint64_t &len) const {
+        len = rep_len;
+        if (q - at >= rep_len) return false;
+        in_rep = true;
+        origin = at;
+        if (at + rep_len < lim) lim = at + rep_len;
+        return true;
+    }
+    __device__ __forceinline__ uint32_t byte(uint64_t at) const { return rep[at]; }
+};
+
+// SIZES (replace_sweep.hpp: replace_sizes_walk): pos[slot] = s_k - (what the matches before it removed) + k * rep_len.
 __global__ __launch_bounds__(kThreads) void replace_sizes_kernel(const uint64_t *__restrict__ off, size_t nitems, uint32_t trim,
                                                                  const uint64_t *__restrict__ first, const uint32_t *__restrict__ match_start,
                                                                  const uint32_t *__restrict__ match_end, uint32_t rep_len, uint32_t *__restrict__ len,
                                                                  uint32_t *__restrict__ pos, uint32_t *__restrict__ too_long) {
-    for_each_wave_pass(nitems, [&](size_t first_item, uint32_t lane) {
-        const size_t i = first_item + lane;
-        if (i >= nitems) return;
-        const auto [b, e] = item_span(off, i, trim);
-        const uint64_t f0 = first[i], f1 = first[i + 1];
-        uint64_t shift = 0;
-        for (uint64_t slot = f0; slot < f1; slot++) {
-            const uint64_t s = match_start[slot], en = match_end[slot];
-            pos[slot] = (uint32_t)(s + shift);
-            shift += (uint64_t)rep_len - (en - s);
-        }
-        uint64_t total = (uint64_t)(e - b) + shift;
-        if ((int64_t)total < 0) total = 0;                   // (a list that removes more than the item holds: not a list of this item)
-        len[i] = total > 0xffffffffu ? 0xffffffffu : (uint32_t)total;
-        if (too_long && total >= ((uint64_t)1 << 30)) *too_long = 1;
-    });
+    replace_sizes_walk(off, nitems, trim, first, match_start, match_end, len, pos, too_long, [=](uint64_t, uint64_t) { return (uint64_t)rep_len; });
 }
 
-// FILL.  Driven by output bytes: a lane-per-item copy loop stores 64 scattered bytes per instruction, this one 256 contiguous ones.
-// A wave takes the 64 consecutive items of a pass, F .. F + 63.  Lane l stages out_off[min(F + l, nitems)] into the wave's own LDS
-// row (entry 64: the pass's end; the entries behind the last item repeat it, so they are never found), then the wave sweeps the
-// pass's output range [lo, hi) = [out_off[F], out_off[min(F + 64, nitems)]) in turns of 256 bytes, lane l the four bytes of one
-// dword ALIGNED BY ADDRESS: the sweep starts at the dword that holds out + lo, `mis` bytes before it.  A dword that lies wholly
-// inside [lo, hi) is stored as one; the partial first and last dwords byte by byte - the neighbouring wave owns the rest of them.
-// For an output byte q (locate): its item = the last staged offset <= q (six steps over the 64 entries: items with empty output drop
-// out); r = q - out_off[item]; k = how many of the item's pos entries are <= r (a binary search over its slots, mostly zero or one
-// step); k = 0: byte r of the item; else, j the last such slot and d = r - pos[j]: R[d] if d < rep_len, else byte
-// match_end[j] + d - rep_len of the item.  A source offset at or beyond the item's end gives 0: no byte outside an item is read,
-// whatever the lists hold, and nothing outside [lo, hi) is written.  What locate found holds up to `lim`, the end of the segment
-// (the item's output, the R, the text up to the next R): the bytes of a dword behind the first reuse it while q < lim.
-// The span and first[] of an item are read from global memory (L1/L2 hits: neighbouring lanes ask for the same item).
-// No atomics, no memset; every lane of a wave makes every turn of the pass loop, none returns early (the row is the wave's).
-constexpr uint32_t kWavesPerBlock = kThreads / 64;
-// a value that every lane of the wave holds alike, into scalar registers (what comes out of LDS is a vector register to the compiler)
-__device__ __forceinline__ uint64_t wave_uniform(uint64_t v) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
+// FILL (replace_sweep.hpp: replace_fill_sweep): d = r - pos[j]: R[d] if d < rep_len, else byte match_end[j] + d - rep_len of the item.
 __global__ __launch_bounds__(kThreads, 8) void replace_fill_kernel(const uint8_t *__restrict__ bytes, const uint64_t *__restrict__ off, size_t nitems,
                                                                 uint32_t trim, const uint64_t *__restrict__ first,
                                                                 const uint32_t *__restrict__ match_end, const uint32_t *__restrict__ pos,
                                                                 const uint8_t *__restrict__ rep, uint32_t rep_len,
                                                                 const uint64_t *__restrict__ out_off, uint8_t *__restrict__ out) {
     __shared__ uint64_t staged[kWavesPerBlock][65];
-    uint64_t *row = staged[threadIdx.x >> 6];
-    for_each_wave_pass(nitems, [&](size_t first_of_lane, uint32_t lane) {
-        const size_t first_item = wave_uniform(first_of_lane);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (the previous pass has read the row)
-        __builtin_amdgcn_wave_barrier();
-        row[lane] = out_off[first_item + lane < nitems ? first_item + lane : nitems];
-        if (lane == 0) row[64] = out_off[first_item + 64 < nitems ? first_item + 64 : nitems];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint64_t lo = wave_uniform(row[0]), hi = wave_uniform(row[64]);
-        if (hi <= lo) return;
-        const uint32_t mis = (uint32_t)((reinterpret_cast<uintptr_t>(out) + lo) & 3u);
-        const uint64_t span = (hi - lo) + mis;                      // the sweep: bytes [0, span) from the aligned dword of out + lo on
-        for (uint64_t rel = (uint64_t)lane * 4; rel < span; rel += 256) {
-            const uint32_t c0 = rel < mis ? mis - (uint32_t)rel : 0u;                         // (rel < mis: rel == 0)
-            const uint32_t c1 = span - rel < 4 ? (uint32_t)(span - rel) : 4u;
-            // the segment that holds the byte located last: output bytes below lim; R[q - origin] or byte q - origin of the item at b
-            uint64_t lim = 0, origin = 0, b = 0, item_len = 0;
-            bool in_rep = false;
-            auto locate = [&](uint64_t q) {
-                uint32_t idx = 0;
-#pragma unroll
-                for (uint32_t step = 32; step; step >>= 1)
-                    if (row[idx + step] <= q) idx += step;
-                const uint64_t o0 = row[idx], o1 = row[idx + 1], r = q - o0;
-                const auto [ib, ie] = item_span(off, first_item + idx, trim);
-                b = ib;
-                item_len = ie - ib;
-                const uint64_t f0 = first[first_item + idx], f1 = first[first_item + idx + 1];
-                uint64_t below = f0, above = f1 > f0 ? f1 : f0;     // slots below `below` have pos <= r, those from `above` on pos > r
-                while (below < above) {
-                    const uint64_t mid = below + ((above - below) >> 1);
-                    if (pos[mid] <= r) below = mid + 1;
-                    else above = mid;
-                }
-                lim = o1;
-                if (below < f1) { const uint64_t next = o0 + pos[below]; if (next < lim) lim = next; }
-                in_rep = false;
-                origin = o0;
-                if (below > f0) {
-                    const uint64_t at = o0 + pos[below - 1];         // where the R of slot j begins in the output
-                    if (q - at < rep_len) { in_rep = true; origin = at; if (at + rep_len < lim) lim = at + rep_len; }
-                    else origin = at + rep_len - match_end[below - 1];
-                }
-            };
-            uint32_t word = 0;
-            for (uint32_t c = c0; c < c1; c++) {
-                const uint64_t q = lo + (rel + c - mis);
-                if (c == c0 || q >= lim) locate(q);
-                const uint64_t at = q - origin;
-                const uint32_t v = in_rep ? rep[at] : at < item_len ? bytes[b + at] : 0u;
-                word |= v << (8 * c);
-            }
-            uint8_t *dst = out + lo + (rel - mis);                   // (4-byte aligned; below out + lo only where c0 > 0: not stored to)
-            if (c0 == 0 && c1 == 4) *reinterpret_cast<uint32_t *>(dst) = word;
-            else for (uint32_t c = c0; c < c1; c++) dst[c] = (uint8_t)(word >> (8 * c));
-        }
-    });
+    replace_fill_sweep(staged[threadIdx.x >> 6], bytes, off, nitems, trim, first, match_end, pos, LiteralReplacement{rep, rep_len}, out_off, out);
 }
 
 }  // namespace

@@ -127,7 +127,7 @@ int rrx_search_all(const rrx_regex *re, const rrx_corpus *c, uint64_t *d_first, 
     int rc = search_begin(re, c, stream, &ct);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (!c->nlines) { HIP_TRY(hipMemsetAsync(d_first, 0, sizeof(uint64_t), st)); HIP_TRY(hipStreamSynchronize(st)); return RRX_OK; }
+    if (!c->nlines) return empty_batch({d_first}, stream);
     if (ct) {
         const size_t sb = dev::search_all_scratch_bytes(c->nchunks);
         {

@@ -331,3 +331,32 @@ def test_the_cap_protocol():
             else:
                 assert np.array_equal(g.written((indexed, cap)), want[0]), (indexed, cap)
     assert L.rrx_replace_all_longest_extents(r._h, 0, ptr(dev), ptr(doff), n, 1, rep, len(rep), ptr(out_off), None, 5, C.byref(tot), s) == 2      # RRX_ERR_ARG: cap > 0 and no d_out
+
+
+TOO_LONG = b"an output item of 2^30 bytes or more: use rrx_search_all_longest_extents and the two passes rrx_replace_matches_sizes / _fill"
+
+
+@pytest.mark.parametrize("indexed", [False, True])
+def test_an_output_item_of_2_30_bytes_is_refused(indexed):
+    """The flag word of the one-call form: one item of 65536 b"a", every byte a match of `a`.  A replacement of 16383 bytes gives an
+    output item of 65536 * 16383 = 2^30 - 65536 bytes, the largest the scan carries; one of 16384 bytes gives exactly 2^30 and is
+    refused, the total left 0.  cap = 0 and no d_out: nothing of that size is allocated.  The flag is the call's own and zeroed per
+    call: the next call on the same regex goes through."""
+    L, s = rr._L, rr._stream_ptr(None)
+    r = rr.RRegex("a")
+    dev, doff = to_dev(*pack([b"a" * 65536], 0))
+    handle = rr.Items(dev, doff, trim=0)
+
+    def call(rep):
+        tot, out_off = C.c_size_t(99), torch.full((2,), -7, dtype=torch.int64, device="cuda")
+        if indexed:
+            rc = L.rrx_replace_all_longest_items(r._h, handle._h, rep, len(rep), ptr(out_off), None, 0, C.byref(tot), s)
+        else:
+            rc = L.rrx_replace_all_longest_extents(r._h, 0, ptr(dev), ptr(doff), 1, 0, rep, len(rep), ptr(out_off), None, 0, C.byref(tot), s)
+        torch.cuda.synchronize()
+        return rc, tot.value, out_off.cpu().tolist()
+
+    assert call(b"r" * 16383) == (0, 65536 * 16383, [0, 65536 * 16383])
+    rc, total, _ = call(b"r" * 16384)
+    assert (rc, total) == (4, 0) and L.rrx_last_error() == TOO_LONG                        # RRX_ERR_UNSUPPORTED
+    assert call(b"r") == (0, 65536, [0, 65536])

@@ -491,3 +491,26 @@ def test_the_cap_protocol_and_degenerate_batches(handles):
     first, start, end = groups[0].regex.search_all_longest_extents_fused(dev, doff, trim=1)
     got = void[0].spans_list_extents(dev, doff, first, start, end, trim=1)
     assert bool((got[0] == -1).all()) and bool((got[1] == -1).all()) and got[0].numel() == int(first[-1]) > 0
+
+
+def test_an_output_item_of_2_30_bytes_is_refused():
+    """test_replace_items_gpu's case on the template's sizes kernel: one item of 65536 b"a", (a) matching every byte, a template that
+    is a literal of 16383 bytes (2^30 - 65536 output bytes: accepted) and of 16384 (exactly 2^30: refused, the total left 0), cap = 0
+    and no d_out; the flag is the call's own: the next call goes through."""
+    L, s = rr._L, rr._stream_ptr(None)
+    groups = [rr.RGroup("(a)", 1)]
+    h = rr._group_handles(groups)
+    dev, doff = to_dev(*pack([b"a" * 65536], 0))
+
+    def call(repl):
+        tpl, tot, out_off = rr.Template(repl), C.c_size_t(99), torch.full((2,), -7, dtype=torch.int64, device="cuda")
+        rc = L.rrx_replace_groups_longest_extents(h, 1, tpl._h, 0, ptr(dev), ptr(doff), 1, 0, ptr(out_off), None, 0, C.byref(tot), s)
+        torch.cuda.synchronize()
+        return rc, tot.value, out_off.cpu().tolist()
+
+    assert call(b"r" * 16383) == (0, 65536 * 16383, [0, 65536 * 16383])
+    rc, total, _ = call(b"r" * 16384)
+    assert (rc, total) == (4, 0)                                                           # RRX_ERR_UNSUPPORTED
+    assert L.rrx_last_error() == (b"an output item of 2^30 bytes or more: use rrx_search_all_longest_extents, rrx_group_spans_list_extents and the two "
+                                  b"passes rrx_replace_template_sizes / _fill")
+    assert call(b"r") == (0, 65536, [0, 65536])
